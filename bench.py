@@ -9,6 +9,17 @@ One "step" = one pass of the whole hot path over one synthetic minibatch already
 mean-subtract(+mixup) -> forward -> softmax-CE(+label smoothing) -> backward -> [gradient all-reduce]
 -> momentum-SGD.  Weak scaling: the per-GPU batch is fixed as N grows.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the step mode).  Every other
+leg described below -- the eager, single-stream, gradient-exchange and recipe legs, the N > 1 exchange leg and per-rank
+clocks, the per-class HIP-event figures, the step bound, the per-step detail and the CPU baseline -- runs only with `--full`
+(the `--no-*` switches still skip single legs of a full run).
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32 .npy files (about 34 MB for the default workload):
+loss_rows (the per-image losses train_step returns), logits, bn_moving_stats (every moving mean / variance), and
+weights_sample / momentum_sample (the fp32 master weights and momentum slots after the update, at the same
+2^22 positions of the parameter arena drawn once with a fixed seed; the whole arena when it is smaller).  Inputs, weight
+initialisation and mixup draws are seeded, so two builds run with the same arguments can be compared file by file.
+
 The timed region is the product as it ships: the weight gradients run beside the input-gradient chain and the big branch of
 each BigLittle stage beside the little one, on side streams; and the step is RECORDED once after the warm-up
 (Trainer.capture -- what a default Trainer does on its own after three eager steps) and replayed from the library's launch tape -- the same ~910 kernel launches on the same streams, issued
@@ -19,7 +30,7 @@ so the per-class figures below come from instrumented eager single-stream steps 
 is the rate of the same steps with every kernel on one stream (--single-stream times that instead).  `step_detail` gives, per
 timed step, the GPU time between step ends and the host time spent enqueueing the step.
 
-Extra objects on the line:
+Extra objects on the line (--full):
   roofline      what BASELINE.json's north_star names: the 3x3-convolution CLASS (every 3x3 fprop, input-gradient and
                 weight-gradient launch of a step, time-weighted) against the gfx950 dense bf16 MFMA peak (2.5 PFLOP/s,
                 MI355X_MICROARCH.md): achieved = the class's algorithmic FLOPs / its HIP-event time.  `dominant_layer` keeps
@@ -224,6 +235,34 @@ def cpu_baseline(workload, budget_s=25.0, hard_timeout_s=200.0):
             'sample': 'CPU oracle did not finish a batch-4 step sample within %.0f s on this host' % hard_timeout_s}
 
 
+DUMP_SAMPLE = 1 << 22     # arena positions of weights_sample / momentum_sample (16 MB each in float32)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, tr, loss_rows):
+  """What the last step computed, as float32 .npy files under out_dir (module docstring: --dump-outputs)."""
+  import numpy as np
+  import torch
+  os.makedirs(out_dir, exist_ok=True)
+  if loss_rows.is_cuda:
+    torch.cuda.synchronize()
+  a, m = tr.model.arena, tr.model
+  n = a.total_elems
+  if n > DUMP_SAMPLE:
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    idx = torch.from_numpy(idx).to(a.w32.device)
+    w, mom = a.w32.index_select(0, idx), a.m32.index_select(0, idx)
+  else:
+    w, mom = a.w32, a.m32
+  arrays = {'loss_rows': loss_rows,
+            'logits': m.logits_padded.reshape(-1, m.ldc)[:, :tr.p.num_classes],
+            'bn_moving_stats': a.state,
+            'weights_sample': w,
+            'momentum_sample': mom}
+  for name, t in arrays.items():
+    np.save(os.path.join(out_dir, name + '.npy'), t.detach().float().cpu().numpy())
+
+
 def _flush_c_stdio():
   try:
     import ctypes
@@ -358,8 +397,19 @@ def main():
                   help='TEST ONLY (tests/test_bench_dryrun_cpu.py): run the control flow of this script -- rank-0 build, '
                        'rendezvous, GradSync, barriers, MAX-reduce of the elapsed time, the JSON line -- on CPU over gloo with '
                        'the test double of the C ABI and a tiny batch; the number it prints means nothing')
+  ap.add_argument('--full', action='store_true',
+                  help='also run every extra leg (eager / single-stream / gradient-exchange / recipe steps, N > 1 exchange leg, '
+                       'per-class and roofline figures, step bound, per-step detail, CPU baseline); a plain run times the '
+                       'steps and nothing else')
+  ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                  help='write what the last timed step computed to DIR/<name>.npy (float32; see the module docstring)')
   args = ap.parse_args()
+  if not args.full:
+    args.no_roofline = args.no_cpu_baseline = args.no_gradsync = args.no_recipe = True
+    if args.dump_convs:
+      ap.error('--dump-convs needs --full (the per-conv times come from its instrumented steps)')
 
+  import numpy as np
   import torch
   import torch.distributed as dist
   import __graft_entry__
@@ -432,7 +482,8 @@ def main():
     dp_info = _dp_plan(tr.grad_sync, world, 'gloo (REHEARSAL on one GPU)' if args.rehearsal_one_gpu else ('gloo (dry run)' if dry else 'RCCL (torch.distributed nccl)'))
   g = torch.Generator(device=dev).manual_seed(1 + rank)
   images, labels, nin = make_inputs(hp, g)
-  lam1 = tr.sample_mixup_lambdas(nin // 2) if hp.mixup_type else None
+  # seeded draws: the same arguments give the same inputs in every run (--dump-outputs compares two builds)
+  lam1 = tr.sample_mixup_lambdas(nin // 2, rng=np.random.default_rng(1 + rank)) if hp.mixup_type else None
 
   def step():
     return tr.train_step(images, labels, lam1)
@@ -505,23 +556,26 @@ def main():
   kern0 = ops.L().asm_launch_count() if not dry else 0
   # per-step diagnostics that cost two clock reads and one event record per step: how long the HOST took to enqueue each
   # step and when the GPU finished it -- a timed region that is slow because the host fell behind (a busy box) reads
-  # differently from one where the GPU ran slowly, and either shows as its first / last steps
+  # differently from one where the GPU ran slowly, and either shows as its first / last steps (--full only)
   step_host, step_ev = [], []
+  detail = args.full and not dry
   t0 = time.time()
   for _ in range(args.steps):
     h0 = time.perf_counter()
     rows = step()
-    if not dry:
+    if detail:
       ev = torch.cuda.Event(enable_timing=True)
       ev.record()
       step_ev.append(ev)
-    step_host.append(time.perf_counter() - h0)
+      step_host.append(time.perf_counter() - h0)
   sync()
   el = time.time() - t0
   abi_calls = (ops.abi_calls() - calls0) / max(args.steps, 1)
   kernels_per_step = ((ops.L().asm_launch_count() - kern0) / max(args.steps, 1)) if not dry else None
   ops.set_conv_timer(None)
-  if world > 1:
+  if args.dump_outputs and rank == 0:     # before any other leg moves the weights on
+    dump_outputs(args.dump_outputs, tr, rows)
+  if world > 1 and args.full:
     # An N-rank line a reader can verify at a glance: who took part (gathered over the process group itself), what each
     # rank's own clock said, and how much of the gradient exchange was NOT hidden behind the backward pass at this N --
     # the same K steps again in the same step mode with the exchange detached (ranks then drift apart: the leg comes after
@@ -569,7 +623,7 @@ def main():
   eager_leg = None
   if taped:
     tr.release_graph()          # the legs below instrument or re-wire the eager step
-    if world == 1:              # the same K steps enqueued launch by launch by the Python host code, same streams: for the record
+    if world == 1 and args.full:   # the same K steps enqueued launch by launch by the Python host code, same streams: for the record
       step()
       sync()
       t1 = time.time()
@@ -675,87 +729,88 @@ def main():
                                '%s' % (args.steps, 'timed region (single stream)' if args.single_stream else
                                        'single-stream leg (`single_stream`): beside another stream\'s kernels a duration '
                                        'is not a property of the kernel')}
-    try:
-      sb = step_bound(args.workload, B)
-      ms_step = 1000.0 * el / args.steps
-      st_obj = {'bound_ms': round(sb['bound_ms'], 3), 'frac_of_bound': round(sb['bound_ms'] / ms_step, 4),
-                'algorithmic_tflop': round(sb['flops'] / 1e12, 3), 'algorithmic_gb': round(sb['bytes'] / 1e9, 2),
-                'achieved_tflops': round(sb['flops'] / (ms_step * 1e-3) / 1e12, 1),
-                'peaks': {'mfma_tflops': MFMA_BF16_PEAK_TFLOPS, 'hbm_gbs': HBM_PEAK_GBS}}
-      if class_sum is not None:
-        convs, classes = class_sum
-        f33 = sum(conv_flops(k) * v[0] for k, v in convs.items() if k[6] == 3 and k[7] == 3)
-        t33 = sum(v[1] for k, v in convs.items() if k[6] == 3 and k[7] == 3)
-        tall = sum(v[1] for v in convs.values())
-        # algorithmic bytes of the class: every launch reads its input and filter once and writes its output once (bf16;
-        # a weight gradient reads x and dy and writes fp32 dW) -- what `traffic` (counter bytes) is to be held against
-        def conv_bytes(k):
-          kind, N_, H_, W_, C_, K_, R_, S_, st_ = k
-          Ho_ = H_ if st_ == 1 else (H_ - 1) // st_ + 1
-          Wo_ = W_ if st_ == 1 else (W_ - 1) // st_ + 1
-          io = 2.0 * (N_ * H_ * W_ * C_ + N_ * Ho_ * Wo_ * K_)
-          return io + (4.0 if kind == 'wgrad' else 2.0) * R_ * S_ * C_ * K_
-        b33 = sum(conv_bytes(k) * v[0] for k, v in convs.items() if k[6] == 3 and k[7] == 3)
-        st_obj['conv3x3_class'] = {'ms_per_step': round(t33, 3), 'tflops': round(f33 / (t33 * 1e-3) / 1e12, 1),
-                                   'algorithmic_bytes_per_step': int(b33),
-                                   'frac_of_mfma_peak': round(f33 / (t33 * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
-                                   'launches': sum(v[0] for k, v in convs.items() if k[6] == 3 and k[7] == 3)}
-        f11 = sum(conv_flops(k) * v[0] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1)
-        t11 = sum(v[1] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1)
-        b11 = sum(conv_bytes(k) * v[0] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1)
-        if t11 > 0:
-          # the 1x1 class (conv1 / conv3 / projections on maps larger than 1 x 1) is bandwidth-bound on the large maps and
-          # matrix-bound on the small ones: both fractions are given; its bound is the per-layer max of the two
-          st_obj['conv1x1_class'] = {'ms_per_step': round(t11, 3), 'tflops': round(f11 / (t11 * 1e-3) / 1e12, 1),
-                                     'algorithmic_bytes_per_step': int(b11), 'gbs_in_out_once': round(b11 / (t11 * 1e-3) / 1e9, 1),
-                                     'frac_of_mfma_peak': round(f11 / (t11 * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
-                                     'frac_of_hbm_peak': round(b11 / (t11 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                     'bound_ms': round(sum(max(conv_flops(k) / (MFMA_BF16_PEAK_TFLOPS * 1e12), conv_bytes(k) / (HBM_PEAK_GBS * 1e9))
-                                                           * v[0] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1) * 1e3, 3),
-                                     'launches': sum(v[0] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1),
-                                     'note': 'in + out once: the fan-in addend a conv1 input gradient also reads is not counted'}
-        st_obj['conv_all_ms_per_step'] = round(tall, 3)
-        if 'bn' in classes:
-          nb, tb, wb = classes['bn']
-          st_obj['bn_class'] = {'ms_per_step': round(tb, 3), 'algorithmic_gb': round(wb / 1e9, 2),
-                                'gbs': round(wb / (tb * 1e-3) / 1e9, 1),
-                                'frac_of_hbm_peak': round(wb / (tb * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), 'calls': nb}
-        st_obj['class_source'] = 'HIP events around every conv / batch-norm-family call of %d instrumented steps after the timed region' % INSTR
-        cls_traffic = {}
-        try:
-          cls_traffic = json.load(open(os.path.join(ROOT, 'profiles', CLASS_TRAFFIC_FILE)))
-        except (OSError, ValueError):
-          pass
-        c33 = st_obj['conv3x3_class']
-        out['roofline'] = {
-            'bound': 'mfma', 'achieved': c33['tflops'], 'peak': MFMA_BF16_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-            'frac': c33['frac_of_mfma_peak'], 'traffic': cls_traffic.get('conv3x3_class_bytes_per_step'),
-            'algorithmic_bytes': c33['algorithmic_bytes_per_step'],
-            'kernel': '3x3 convolution class: every 3x3 fprop / input-gradient / weight-gradient launch of a step (%d launches, '
-                      '%.3f ms, %.1f algorithmic GFLOP), time-weighted' % (c33['launches'], c33['ms_per_step'], f33 / 1e9),
-            'traffic_source': 'profiles/%s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --single-stream`, '
-                              'tools/profile_round.sh; not measured in this run)' % CLASS_TRAFFIC_FILE,
-            'dominant_layer': dominant_obj}
-        if 'conv1x1_class' in st_obj:
-          c11 = st_obj['conv1x1_class']
-          out['roofline']['conv1x1'] = {'bound': 'hbm / mfma per layer', 'ms_per_step': c11['ms_per_step'], 'bound_ms': c11['bound_ms'],
-                                        'frac': round(c11['bound_ms'] / c11['ms_per_step'], 4), 'achieved_tflops': c11['tflops'],
-                                        'achieved_gbs': c11['gbs_in_out_once'],
-                                        'kernel': '1x1 convolution class: every 1x1 fprop / input-gradient / weight-gradient launch on maps '
-                                                  'larger than 1 x 1 (%d launches); frac = sum of per-layer max(flops / 2.5 PFLOP/s, '
-                                                  'bytes / 8 TB/s) over the class time' % c11['launches']}
-        if 'bn_class' in st_obj:
-          bc = st_obj['bn_class']
-          out['roofline']['hbm'] = {'bound': 'hbm', 'achieved': bc['gbs'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                                    'frac': bc['frac_of_hbm_peak'], 'traffic': cls_traffic.get('bn_class_bytes_per_step'),
-                                    'kernel': 'batch-norm family (statistics finalize, apply, backward reduce / apply, the SK '
-                                              'unit\'s on-the-fly forms): %.2f algorithmic GB in %.3f ms per step' % (
-                                                  bc['algorithmic_gb'], bc['ms_per_step'])}
-      elif dominant_obj is not None:
-        out['roofline'] = dict({'bound': 'mfma', 'peak': MFMA_BF16_PEAK_TFLOPS, 'unit': 'TFLOP/s'}, **dominant_obj)
-      out['step'] = st_obj
-    except Exception as e:   # reporting extras must never lose the measured number
-      out['step'] = {'error': repr(e)}
+    if args.full:   # the per-layer bound (a shape walk of the model) and the class figures of the instrumented steps
+      try:
+        sb = step_bound(args.workload, B)
+        ms_step = 1000.0 * el / args.steps
+        st_obj = {'bound_ms': round(sb['bound_ms'], 3), 'frac_of_bound': round(sb['bound_ms'] / ms_step, 4),
+                  'algorithmic_tflop': round(sb['flops'] / 1e12, 3), 'algorithmic_gb': round(sb['bytes'] / 1e9, 2),
+                  'achieved_tflops': round(sb['flops'] / (ms_step * 1e-3) / 1e12, 1),
+                  'peaks': {'mfma_tflops': MFMA_BF16_PEAK_TFLOPS, 'hbm_gbs': HBM_PEAK_GBS}}
+        if class_sum is not None:
+          convs, classes = class_sum
+          f33 = sum(conv_flops(k) * v[0] for k, v in convs.items() if k[6] == 3 and k[7] == 3)
+          t33 = sum(v[1] for k, v in convs.items() if k[6] == 3 and k[7] == 3)
+          tall = sum(v[1] for v in convs.values())
+          # algorithmic bytes of the class: every launch reads its input and filter once and writes its output once (bf16;
+          # a weight gradient reads x and dy and writes fp32 dW) -- what `traffic` (counter bytes) is to be held against
+          def conv_bytes(k):
+            kind, N_, H_, W_, C_, K_, R_, S_, st_ = k
+            Ho_ = H_ if st_ == 1 else (H_ - 1) // st_ + 1
+            Wo_ = W_ if st_ == 1 else (W_ - 1) // st_ + 1
+            io = 2.0 * (N_ * H_ * W_ * C_ + N_ * Ho_ * Wo_ * K_)
+            return io + (4.0 if kind == 'wgrad' else 2.0) * R_ * S_ * C_ * K_
+          b33 = sum(conv_bytes(k) * v[0] for k, v in convs.items() if k[6] == 3 and k[7] == 3)
+          st_obj['conv3x3_class'] = {'ms_per_step': round(t33, 3), 'tflops': round(f33 / (t33 * 1e-3) / 1e12, 1),
+                                     'algorithmic_bytes_per_step': int(b33),
+                                     'frac_of_mfma_peak': round(f33 / (t33 * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+                                     'launches': sum(v[0] for k, v in convs.items() if k[6] == 3 and k[7] == 3)}
+          f11 = sum(conv_flops(k) * v[0] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1)
+          t11 = sum(v[1] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1)
+          b11 = sum(conv_bytes(k) * v[0] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1)
+          if t11 > 0:
+            # the 1x1 class (conv1 / conv3 / projections on maps larger than 1 x 1) is bandwidth-bound on the large maps and
+            # matrix-bound on the small ones: both fractions are given; its bound is the per-layer max of the two
+            st_obj['conv1x1_class'] = {'ms_per_step': round(t11, 3), 'tflops': round(f11 / (t11 * 1e-3) / 1e12, 1),
+                                       'algorithmic_bytes_per_step': int(b11), 'gbs_in_out_once': round(b11 / (t11 * 1e-3) / 1e9, 1),
+                                       'frac_of_mfma_peak': round(f11 / (t11 * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+                                       'frac_of_hbm_peak': round(b11 / (t11 * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                       'bound_ms': round(sum(max(conv_flops(k) / (MFMA_BF16_PEAK_TFLOPS * 1e12), conv_bytes(k) / (HBM_PEAK_GBS * 1e9))
+                                                             * v[0] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1) * 1e3, 3),
+                                       'launches': sum(v[0] for k, v in convs.items() if k[6] == 1 and k[7] == 1 and k[2] > 1),
+                                       'note': 'in + out once: the fan-in addend a conv1 input gradient also reads is not counted'}
+          st_obj['conv_all_ms_per_step'] = round(tall, 3)
+          if 'bn' in classes:
+            nb, tb, wb = classes['bn']
+            st_obj['bn_class'] = {'ms_per_step': round(tb, 3), 'algorithmic_gb': round(wb / 1e9, 2),
+                                  'gbs': round(wb / (tb * 1e-3) / 1e9, 1),
+                                  'frac_of_hbm_peak': round(wb / (tb * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), 'calls': nb}
+          st_obj['class_source'] = 'HIP events around every conv / batch-norm-family call of %d instrumented steps after the timed region' % INSTR
+          cls_traffic = {}
+          try:
+            cls_traffic = json.load(open(os.path.join(ROOT, 'profiles', CLASS_TRAFFIC_FILE)))
+          except (OSError, ValueError):
+            pass
+          c33 = st_obj['conv3x3_class']
+          out['roofline'] = {
+              'bound': 'mfma', 'achieved': c33['tflops'], 'peak': MFMA_BF16_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+              'frac': c33['frac_of_mfma_peak'], 'traffic': cls_traffic.get('conv3x3_class_bytes_per_step'),
+              'algorithmic_bytes': c33['algorithmic_bytes_per_step'],
+              'kernel': '3x3 convolution class: every 3x3 fprop / input-gradient / weight-gradient launch of a step (%d launches, '
+                        '%.3f ms, %.1f algorithmic GFLOP), time-weighted' % (c33['launches'], c33['ms_per_step'], f33 / 1e9),
+              'traffic_source': 'profiles/%s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --single-stream`, '
+                                'tools/profile_round.sh; not measured in this run)' % CLASS_TRAFFIC_FILE,
+              'dominant_layer': dominant_obj}
+          if 'conv1x1_class' in st_obj:
+            c11 = st_obj['conv1x1_class']
+            out['roofline']['conv1x1'] = {'bound': 'hbm / mfma per layer', 'ms_per_step': c11['ms_per_step'], 'bound_ms': c11['bound_ms'],
+                                          'frac': round(c11['bound_ms'] / c11['ms_per_step'], 4), 'achieved_tflops': c11['tflops'],
+                                          'achieved_gbs': c11['gbs_in_out_once'],
+                                          'kernel': '1x1 convolution class: every 1x1 fprop / input-gradient / weight-gradient launch on maps '
+                                                    'larger than 1 x 1 (%d launches); frac = sum of per-layer max(flops / 2.5 PFLOP/s, '
+                                                    'bytes / 8 TB/s) over the class time' % c11['launches']}
+          if 'bn_class' in st_obj:
+            bc = st_obj['bn_class']
+            out['roofline']['hbm'] = {'bound': 'hbm', 'achieved': bc['gbs'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                                      'frac': bc['frac_of_hbm_peak'], 'traffic': cls_traffic.get('bn_class_bytes_per_step'),
+                                      'kernel': 'batch-norm family (statistics finalize, apply, backward reduce / apply, the SK '
+                                                'unit\'s on-the-fly forms): %.2f algorithmic GB in %.3f ms per step' % (
+                                                    bc['algorithmic_gb'], bc['ms_per_step'])}
+        elif dominant_obj is not None:
+          out['roofline'] = dict({'bound': 'mfma', 'peak': MFMA_BF16_PEAK_TFLOPS, 'unit': 'TFLOP/s'}, **dominant_obj)
+        out['step'] = st_obj
+      except Exception as e:   # reporting extras must never lose the measured number
+        out['step'] = {'error': repr(e)}
     out['streams'] = ('single (ASM_WGRAD_STREAM=0 ASM_BL_STREAMS=0)' if args.single_stream else
                       'product default: the weight gradients and the big branch of each BigLittle stage on side streams')
     if len(step_ev) >= 2:

@@ -10,7 +10,7 @@ run() { # label, dir, extra args...
 }
 for i in 1 2 3; do
   run round3_tree _r3
-  run this_tree_recorded_step .
-  run this_tree_eager . --eager
+  run this_tree_recorded_step . --full
+  run this_tree_eager . --eager --full
 done
 cat $out

@@ -6,7 +6,7 @@ out=gpurun_out/host_contention.log
 run() { # label, competitors
   pids=""
   for i in $(seq 1 $2); do taskset -c 2 python -c "while True: pass" & pids="$pids $!"; done
-  r=$(taskset -c 2 python bench.py --steps ${STEPS:-20} --warmup ${WARM:-5} --no-cpu-baseline --no-roofline --no-gradsync $3 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d.get('streams_autotune'), d.get('step_detail'))")
+  r=$(taskset -c 2 python bench.py --full --steps ${STEPS:-20} --warmup ${WARM:-5} --no-cpu-baseline --no-roofline --no-gradsync $3 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d.get('streams_autotune'), d.get('step_detail'))")
   for p in $pids; do kill $p; done
   echo "$1 $r" >> $out
 }

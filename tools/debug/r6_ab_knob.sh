@@ -3,7 +3,7 @@ KV=$1; REPS=${2:-3}
 for rep in $(seq $REPS); do
   for on in 0 1; do
     if [ $on = 1 ]; then export $KV; tag="$KV"; else unset ${KV%%=*}; tag="default"; fi
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-recipe --no-gradsync 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-recipe --no-gradsync 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s=d['step']

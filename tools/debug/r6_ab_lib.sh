@@ -3,7 +3,7 @@ OLD_LIB=$1; REPS=${2:-3}
 for rep in $(seq $REPS); do
   for v in new old; do
     if [ $v = old ]; then export ASM_HIP_LIB=$OLD_LIB; else unset ASM_HIP_LIB; fi
-    timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-recipe --no-gradsync 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-recipe --no-gradsync 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s=d['step']

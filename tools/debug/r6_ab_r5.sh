@@ -3,7 +3,7 @@
 # then on the GPU box: bash tools/debug/r6_ab_r5.sh
 for rep in 1 2 3; do
   for t in _r5 .; do
-    (cd $t && timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-recipe --no-gradsync 2>/dev/null | python -c "
+    (cd $t && timeout 300 python bench.py $([ $t = . ] && echo --full) --steps 20 --warmup 5 --no-cpu-baseline --no-recipe --no-gradsync 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 s=d['step']
