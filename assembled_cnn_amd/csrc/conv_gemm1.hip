@@ -15,8 +15,8 @@
 // and two workgroups per CU.  A workgroup of these layers spends its life in prologue (address decode, first round trip),
 // 2 - 32 K steps and epilogue (LDS staging, 8 - 16 store passes, the statistics' barriers); what hides one workgroup's
 // prologue and epilogue is another workgroup's K loop on the same CU.  The configurations that win are the SMALL ones --
-// 24 - 72 KB, three to six workgroups per CU -- and the template below exists to provide them per layer (asm_gemm1_try's
-// table); beside the weight-gradient streams' kernels of the training step they gain 2.5 x what they gain alone.
+// 24 - 72 KB, three to six workgroups per CU -- and the template below exists to provide them per layer (kConfigs,
+// auto_cfg); beside the weight-gradient streams' kernels of the training step they gain 2.5 x what they gain alone.
 // Same tiles, fragment layout, (chunk, k) accumulation order and epilogue as igemm2_kernel: bit-identical results.
 #include "common.h"
 #include "igemm_common.h"
@@ -44,7 +44,7 @@ __device__ __forceinline__ void wait_vm_steps(const int r) {
 
 template <int BM, int BN, int BK, int WGM, int WGN, int NS>
 struct Cfg1 {
-  using C = Cfg<BM, BN, BK, WGM, WGN, false, true, 2>;
+  using C = Cfg<BM, BN, BK, WGM, WGN, false, true>;
   static constexpr int STAGE = (BM + BN) * C::ROWB;
   static constexpr int LDS = cmax(cmax(NS * STAGE, C::EPI), C::RED);
   static constexpr int P = C::XP + C::WP;           // LDS-DMA pieces per wave and step
@@ -56,7 +56,7 @@ struct Cfg1 {
 
 template <int BM, int BN, int BK, int WGM, int WGN, bool STATS, int NS, bool PFA, bool POOL, bool BNRED = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void igemm1_kernel(IGemmArgs p) {
-  using C = Cfg<BM, BN, BK, WGM, WGN, false, STATS, 2>;
+  using C = Cfg<BM, BN, BK, WGM, WGN, false, STATS>;
   using C1 = Cfg1<BM, BN, BK, WGM, WGN, NS>;
   constexpr int CPR = C::CPR, RPP = C::RPP, XP = C::XP, WP = C::WP, ROWB = C::ROWB, STAGE = C1::STAGE, P = C1::P;
   constexpr int TM = C::TM, TN = C::TN, WTM = C::WTM, WTN = C::WTN;
@@ -208,27 +208,42 @@ int launch1_one(const IGemmArgs& a, hipStream_t st) {
   if (hipError_t e = asm_ensure_dyn_lds(kern, C1::LDS, attr_done); e != hipSuccess)
     ASM_FAIL(ASM_EHIP, "igemm1_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
   ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(64 * WGM * WGN), C1::LDS, st, a);
-  asm_last_conv_kernel = 1;
   ASM_CHECK_LAUNCH("igemm1_kernel");
   return ASM_OK;
 }
 
-// returns 1 if this tile does not fit the layer
 template <int BM, int BN, int BK, int WGM, int WGN, int NS>
-int launch1_cfg(IGemmArgs& a, bool stats, hipStream_t st) {
-  if (a.Ci % BK != 0 && a.Ci > BK) return 1;
-  a.n_tiles_n = cdiv(a.Co, BN);
-  a.n_blocks = cdiv(a.M, BM) * a.n_tiles_n;
-  a.kchunks = cdiv(a.Ci, BK);
-  a.fd_ntn = make_fastdiv((unsigned)a.n_tiles_n);
-  const int pfa_env = asm_tune().igemm_pfa;   // the addend-prefetching epilogue, chosen as igemm2 does (launch2_cfg)
-  const bool pfa = a.addend != nullptr && !a.y_strided && (pfa_env >= 0 ? pfa_env != 0 : (BM == 256 || a.n_blocks <= 1024));
-  if (stats && a.red_y) return launch1_one<BM, BN, BK, WGM, WGN, true, NS, false, false, true>(a, st);
-  if (stats) return launch1_one<BM, BN, BK, WGM, WGN, true, NS, false, false>(a, st);
-  if (a.pool_dy) return launch1_one<BM, BN, BK, WGM, WGN, false, NS, false, true>(a, st);
-  if (pfa) return launch1_one<BM, BN, BK, WGM, WGN, false, NS, true, false>(a, st);
-  return launch1_one<BM, BN, BK, WGM, WGN, false, NS, false, false>(a, st);
+int launch1(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
+  switch (L.epi) {
+    case EPI_BNRED: return launch1_one<BM, BN, BK, WGM, WGN, true, NS, false, false, true>(a, st);
+    case EPI_STATS: return launch1_one<BM, BN, BK, WGM, WGN, true, NS, false, false>(a, st);
+    case EPI_POOL: return launch1_one<BM, BN, BK, WGM, WGN, false, NS, false, true>(a, st);
+    case EPI_PFA: return launch1_one<BM, BN, BK, WGM, WGN, false, NS, true, false>(a, st);
+    case EPI_PLAIN: return launch1_one<BM, BN, BK, WGM, WGN, false, NS, false, false>(a, st);
+  }
+  return conv_no_variant("igemm1_kernel", L.epi);
 }
+
+// The configurations, by code.  LDS per workgroup -> workgroups per CU.  Round-5 sweep (tools/gemm1_sweep.py,
+// profiles/round5_gemm1_sweep.md): what pays on these layers is MORE RESIDENT WORKGROUPS (one's prologue / epilogue under the
+// others' K loops), not a deeper ring: 128 x 128 x 64 with 3 or 4 stages (one workgroup per CU) LOSES 20 - 60 % against two
+// stages (two per CU).
+struct Config {
+  int code;
+  ConvTile t;
+  int (*launch)(const ConvLaunch&, const IGemmArgs&, hipStream_t);   // launch1<t, ring stages>
+};
+constexpr Config kConfigs[] = {
+    {1, {128, 128, 64, 2, 2}, launch1<128, 128, 64, 2, 2, 2>},    //  64 KB: 2 per CU (igemm2's tile and depth)
+    {5, {128, 128, 32, 2, 2}, launch1<128, 128, 32, 2, 2, 3>},    //  48 KB: 3
+    {8, {256, 128, 64, 4, 2}, launch1<256, 128, 64, 4, 2, 3>},    // 144 KB: 1 (8 waves)
+    {10, {128, 128, 32, 2, 2}, launch1<128, 128, 32, 2, 2, 2>},   //  34 KB: 4
+    {11, {128, 64, 64, 2, 2}, launch1<128, 64, 64, 2, 2, 2>},     //  48 KB: 3
+    {12, {128, 64, 32, 2, 2}, launch1<128, 64, 32, 2, 2, 3>},     //  36 KB: 4
+    {13, {128, 64, 32, 2, 2}, launch1<128, 64, 32, 2, 2, 2>},     //  24 KB: 6
+    {14, {256, 128, 32, 4, 2}, launch1<256, 128, 32, 4, 2, 3>},   //  72 KB: 2 (8 waves each)
+    {16, {128, 256, 32, 2, 2}, launch1<128, 256, 32, 2, 2, 2>},   //  66 KB: 2 (4 waves of 64 x 128)
+};
 
 // Per-layer choice (asm_tuning.gemm1 = -1) for the 1x1 stride-1 layers of Assemble-ResNet-50 at batch 256 -- 65 of its 69
 // (layer, kind) pairs; everything else (other batch sizes, other networks) stays with igemm2.  Built in three steps, every
@@ -291,24 +306,18 @@ int auto_cfg(const IGemmArgs& a, bool stats) {
 
 }  // namespace
 
-// returns 1 when the layer stays with igemm2_kernel; a.fd_howo / a.fd_wo are set by the caller
-int asm_gemm1_try(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st) {
-  if (out_f32 || a.R != 1 || a.S != 1 || a.bn_scale) return 1;
+// the igemm1 configuration of a layer (asm_tuning.gemm1: -1 auto_cfg, n > 0 forced) and its tile; 0: it stays with igemm2
+int asm_gemm1_config(const IGemmArgs& a, bool out_f32, bool stats, ConvTile* t) {
+  if (out_f32 || a.R != 1 || a.S != 1 || a.bn_scale) return 0;
   const int g = asm_tune().gemm1;
   const int code = g < 0 ? auto_cfg(a, stats) : g;
-  switch (code) {
-    // LDS per workgroup -> workgroups per CU.  Round-5 sweep (tools/gemm1_sweep.py, profiles/round5_gemm1_sweep.md): what
-    // pays on these layers is MORE RESIDENT WORKGROUPS (one's prologue / epilogue under the others' K loops), not a deeper
-    // ring: 128 x 128 x 64 with 3 or 4 stages (one workgroup per CU) LOSES 20 - 60 % against two stages (two per CU).
-    case 1: return launch1_cfg<128, 128, 64, 2, 2, 2>(a, stats, st);   //  64 KB: 2 per CU (igemm2's tile and depth)
-    case 5: return launch1_cfg<128, 128, 32, 2, 2, 3>(a, stats, st);   //  48 KB: 3
-    case 8: return launch1_cfg<256, 128, 64, 4, 2, 3>(a, stats, st);   // 144 KB: 1 (8 waves)
-    case 10: return launch1_cfg<128, 128, 32, 2, 2, 2>(a, stats, st);  //  34 KB: 4
-    case 11: return launch1_cfg<128, 64, 64, 2, 2, 2>(a, stats, st);   //  48 KB: 3
-    case 12: return launch1_cfg<128, 64, 32, 2, 2, 3>(a, stats, st);   //  36 KB: 4
-    case 13: return launch1_cfg<128, 64, 32, 2, 2, 2>(a, stats, st);   //  24 KB: 6
-    case 14: return launch1_cfg<256, 128, 32, 4, 2, 3>(a, stats, st);  //  72 KB: 2 (8 waves each)
-    case 16: return launch1_cfg<128, 256, 32, 2, 2, 2>(a, stats, st);  //  66 KB: 2 (4 waves of 64 x 128)
-    default: return 1;
-  }
+  for (const Config& c : kConfigs)
+    if (c.code == code && (a.Ci % c.t.bk == 0 || a.Ci <= c.t.bk)) { *t = c.t; return code; }
+  return 0;
+}
+
+int asm_gemm1_launch(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
+  for (const Config& c : kConfigs)
+    if (c.code == L.gemm1) return c.launch(L, a, st);
+  ASM_FAIL(ASM_EINVAL, "conv: no igemm1 configuration %d", L.gemm1);
 }

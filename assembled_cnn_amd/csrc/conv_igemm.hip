@@ -15,18 +15,19 @@
 // igemm_kernel below is the GENERAL form (any filter size, stride, channel count that is a multiple of 8): global -> LDS by
 // LDS-DMA (global_load_lds_dwordx4), an out-of-image tap or a channel tail reads 16 zero bytes instead.  LDS rows are
 // XOR-swizzled at 16-byte granularity so the ds_read_b128 fragment reads are bank-conflict free.  The workloads' own layers
-// run on the specialised kernels further down (igemm2 / igemm3 / igemm8 / conv_halo, conv_gemm1.hip); the register-staged
-// forms of this kernel (rounds 1 - 5) measured slower than its LDS-DMA form wherever it is still used and were removed.
+// run on the specialised kernels further down (igemm2 / igemm3 / igemm8 / conv_halo, conv_gemm1.hip); plan_conv at the end of
+// this file chooses the kernel of a layer.
 #include "common.h"
 #include "igemm_common.h"
 
 using namespace asm_igemm;
 
-// conv_gemm1.hip: the 1x1 layers as a GEMM with a ring of LDS stages (returns 1 when it does not take the layer)
-int asm_gemm1_try(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st);
-// conv_igemm8.hip: the wide 3x3 stride-1 layers on the wave-staggered multi-phase main loop (returns 1 when it does not take the layer)
-int asm_igemm8_try(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st);
+// conv_gemm1.hip: the 1x1 layers as a GEMM with a ring of LDS stages (configuration code, 0: the layer is not one it takes)
+int asm_gemm1_config(const IGemmArgs& a, bool out_f32, bool stats, ConvTile* t);
+int asm_gemm1_launch(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st);
+// conv_igemm8.hip: the wide 3x3 stride-1 layers on the wave-staggered multi-phase main loop
 bool asm_igemm8_covers(const IGemmArgs& a, bool out_f32);
+int asm_igemm8_launch(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st);
 
 namespace {
 
@@ -34,9 +35,9 @@ namespace {
 __device__ __attribute__((aligned(16))) unsigned g_zero16[4] = {0u, 0u, 0u, 0u};
 
 
-template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS, int MODE, bool BNRED = false>
+template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS, bool BNRED = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void igemm_kernel(IGemmArgs p) {
-  using C = Cfg<BM, BN, BK, WGM, WGN, OUT_F32, STATS, MODE>;
+  using C = Cfg<BM, BN, BK, WGM, WGN, OUT_F32, STATS>;
   constexpr int NT = C::NT, CPR = C::CPR, RPP = C::RPP, XP = C::XP, WP = C::WP, ROWB = C::ROWB, STAGE = C::STAGE;
   constexpr int TM = C::TM, TN = C::TN, WTM = C::WTM, WTN = C::WTN;
 
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_kernel(IGemmArgs p) {
 // Requires R x S in {1x1, 3x3, 7x1, 3x1} and (Ci % BK == 0 or a single chunk); the rest stays on igemm_kernel.
 template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS, int NS>
 struct Cfg2 {
-  using C = Cfg<BM, BN, BK, WGM, WGN, OUT_F32, STATS, 2>;
+  using C = Cfg<BM, BN, BK, WGM, WGN, OUT_F32, STATS>;
   // NS = LDS stages.  A ring of 3-4 stages with counted vmcnt + raw s_barrier (DMA in flight across the barrier) was
   // measured at +-2 % over NS = 2 on every layer class, so only the double buffer is instantiated.
   static constexpr int WROWS = BN;
@@ -227,7 +228,7 @@ struct Cfg2 {
 template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS, int R, int S, int NS, bool PFA = false, bool POOL = false,
           int SCHED = 0, bool BNRED = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void igemm2_kernel(IGemmArgs p) {
-  using C = Cfg<BM, BN, BK, WGM, WGN, OUT_F32, STATS, 2>;
+  using C = Cfg<BM, BN, BK, WGM, WGN, OUT_F32, STATS>;
   using C2 = Cfg2<BM, BN, BK, WGM, WGN, OUT_F32, STATS, NS>;
   constexpr int CPR = C::CPR, RPP = C::RPP, XP = C::XP, WP = C::WP, ROWB = C::ROWB, STAGE = C2::STAGE;
   constexpr int TM = C::TM, TN = C::TN, WTM = C::WTM, WTN = C::WTN;
@@ -455,7 +456,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm2_kernel(IGemmArgs p) {
 template <int BN, bool STATS, bool PFA, int H3_ROWS = 192, int NHB = 2, bool BNRED = false>
 __global__ __launch_bounds__(256) void igemm3_kernel(IGemmArgs p) {
   constexpr int BM = 128, BK = 64, WGM = 2, WGN = 2;
-  using C = Cfg<BM, BN, BK, WGM, WGN, false, STATS, 2>;
+  using C = Cfg<BM, BN, BK, WGM, WGN, false, STATS>;
   constexpr int RPP = C::RPP, ROWB = C::ROWB, WP = C::WP;
   constexpr int TM = C::TM, TN = C::TN, WTM = C::WTM, WTN = C::WTN;
   constexpr int HP = H3_ROWS / RPP;                 // halo pieces per wave and chunk
@@ -629,7 +630,7 @@ __global__ __launch_bounds__(256) void igemm3_kernel(IGemmArgs p) {
 
 template <int BN, bool STATS, bool PFA, int HR = 192, int NHB = 2, bool BNRED = false>
 int launch3_one(const IGemmArgs& a, hipStream_t st) {
-  using C = Cfg<128, BN, 64, 2, 2, false, STATS, 2>;
+  using C = Cfg<128, BN, 64, 2, 2, false, STATS>;
   constexpr int LDS = cmax(cmax(NHB * HR * 128 + 2 * BN * 128, C::EPI), C::RED);
   static_assert(LDS <= 80 * 1024, "two workgroups per CU");
   auto kern = igemm3_kernel<BN, STATS, PFA, HR, NHB, BNRED>;
@@ -637,9 +638,19 @@ int launch3_one(const IGemmArgs& a, hipStream_t st) {
   if (hipError_t e = asm_ensure_dyn_lds(kern, LDS, attr_done); e != hipSuccess)
     ASM_FAIL(ASM_EHIP, "igemm3_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
   ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(256), LDS, st, a);
-  asm_last_conv_kernel = 3;
   ASM_CHECK_LAUNCH("igemm3_kernel");
   return ASM_OK;
+}
+
+template <int HR, int NHB>
+int launch3(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
+  switch (L.epi) {
+    case EPI_BNRED: return launch3_one<128, true, false, HR, NHB, true>(a, st);
+    case EPI_STATS: return launch3_one<128, true, false, HR, NHB>(a, st);
+    case EPI_PFA: return launch3_one<128, false, true, HR, NHB>(a, st);
+    case EPI_PLAIN: return launch3_one<128, false, false, HR, NHB>(a, st);
+  }
+  return conv_no_variant("igemm3_kernel", L.epi);
 }
 
 // is the layer one igemm3_kernel covers?
@@ -653,35 +664,6 @@ bool igemm3_covers(const IGemmArgs& a, bool out_f32) {
   if (a.HoWo != a.Hi * a.Wi || a.Wo != a.Wi || a.M % a.HoWo) return false;
   if (a.x_pix_pitch != a.Ci || a.x_row_pitch != a.Wi * a.Ci || a.x_img_pitch != a.Hi * a.Wi * a.Ci) return false;
   return true;
-}
-
-// returns 1 when the layer is not one igemm3_kernel covers
-int try_igemm3(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st) {
-  if (!igemm3_covers(a, out_f32)) return 1;
-  const bool one_chunk = a.Ci == 64;
-  a.n_tiles_n = cdiv(a.Co, 128);
-  a.n_blocks = (cdiv(a.M, 128) - a.m_tile0) * a.n_tiles_n;
-  a.kchunks = a.Ci / 64;
-  a.fd_ntn = make_fastdiv((unsigned)a.n_tiles_n);
-  const int pfa_env = asm_tune().igemm_pfa;
-  const bool pfa = a.addend != nullptr && (pfa_env >= 0 ? pfa_env != 0 : a.n_blocks <= 1024);
-  const bool bnred = stats && a.red_y;      // an input gradient that also reduces the batch-norm backward sums of its output
-  if (one_chunk) {
-    if (a.Wi <= 30) {
-      if (bnred) return launch3_one<128, true, false, 192, 1, true>(a, st);
-      if (stats) return launch3_one<128, true, false, 192, 1>(a, st);
-      if (pfa) return launch3_one<128, false, true, 192, 1>(a, st);
-      return launch3_one<128, false, false, 192, 1>(a, st);
-    }
-    if (bnred) return launch3_one<128, true, false, 256, 1, true>(a, st);
-    if (stats) return launch3_one<128, true, false, 256, 1>(a, st);
-    if (pfa) return launch3_one<128, false, true, 256, 1>(a, st);
-    return launch3_one<128, false, false, 256, 1>(a, st);
-  }
-  if (bnred) return launch3_one<128, true, false, 192, 2, true>(a, st);
-  if (stats) return launch3_one<128, true, false>(a, st);
-  if (pfa) return launch3_one<128, false, true>(a, st);
-  return launch3_one<128, false, false>(a, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -712,7 +694,7 @@ struct HaloCfg {
 // prefetched into registers while patch i is multiplied and stored, so a workgroup hides its own HBM latency.
 template <int KO, int CI, int WGM, int WGN, bool STATS>
 __global__ __launch_bounds__(256) void conv_halo_kernel(IGemmArgs p) {
-  using C = Cfg<128, KO, CI, WGM, WGN, false, STATS, 2>;
+  using C = Cfg<128, KO, CI, WGM, WGN, false, STATS>;
   using H = HaloCfg<KO, CI>;
   constexpr int TM = C::TM, TN = C::TN, WTM = C::WTM, WTN = C::WTN;
   constexpr int HW_ = 18;                           // halo width in pixels (height 10)
@@ -852,27 +834,21 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(IGemmArgs p) {
   }
 }
 
-template <int KO, int CI, int WGM, int WGN>
-int launch_halo(IGemmArgs& a, bool stats, hipStream_t st) {
+template <int KO, int CI, int WGM, int WGN, bool STATS>
+int launch_halo_one(const IGemmArgs& a, hipStream_t st) {
   using H = HaloCfg<KO, CI>;
-  a.n_tiles_n = 1;
-  const int n_m = a.M / 128;
-  a.n_blocks = n_m < H::PER_CU * 256 ? n_m : H::PER_CU * 256;
-  static bool attr_done[2][ASM_MAX_DEVICES] = {};
-  if (stats) {
-    auto kern = conv_halo_kernel<KO, CI, WGM, WGN, true>;
-    if (hipError_t e = asm_ensure_dyn_lds(kern, H::LDS, attr_done[1]); e != hipSuccess)
-      ASM_FAIL(ASM_EHIP, "conv_halo_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-    ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(256), H::LDS, st, a);
-  } else {
-    auto kern = conv_halo_kernel<KO, CI, WGM, WGN, false>;
-    if (hipError_t e = asm_ensure_dyn_lds(kern, H::LDS, attr_done[0]); e != hipSuccess)
-      ASM_FAIL(ASM_EHIP, "conv_halo_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-    ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(256), H::LDS, st, a);
-  }
-  asm_last_conv_kernel = 4;
+  auto kern = conv_halo_kernel<KO, CI, WGM, WGN, STATS>;
+  static bool attr_done[ASM_MAX_DEVICES] = {};
+  if (hipError_t e = asm_ensure_dyn_lds(kern, H::LDS, attr_done); e != hipSuccess)
+    ASM_FAIL(ASM_EHIP, "conv_halo_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
+  ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(256), H::LDS, st, a);
   ASM_CHECK_LAUNCH("conv_halo_kernel");
   return ASM_OK;
+}
+
+template <int KO, int CI, int WGM, int WGN>
+int launch_halo(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
+  return L.epi == EPI_STATS ? launch_halo_one<KO, CI, WGM, WGN, true>(a, st) : launch_halo_one<KO, CI, WGM, WGN, false>(a, st);
 }
 
 // is the layer one the halo kernel covers?
@@ -883,16 +859,6 @@ bool halo_covers(const IGemmArgs& a, bool out_f32) {
   if (!((a.tsign > 0 && a.pad == 1 && a.pad_w == 1) || (a.tsign < 0 && a.pad == -1 && a.pad_w == -1))) return false;
   if (a.wt0 != 0 || a.wtr != 3 || a.wts != 1) return false;
   return (a.Ci == 32 || a.Ci == 64) && (a.Co == 32 || a.Co == 64);
-}
-
-// returns 1 when the layer is not one the halo kernel covers
-int try_halo(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st) {
-  if (!halo_covers(a, out_f32)) return 1;
-  if (a.Ci == 64 && a.Co == 32) return launch_halo<32, 64, 4, 1>(a, stats, st);
-  if (a.Ci == 32 && a.Co == 32) return launch_halo<32, 32, 4, 1>(a, stats, st);
-  if (a.Ci == 32 && a.Co == 64) return launch_halo<64, 32, 2, 2>(a, stats, st);
-  if (a.Ci == 64 && a.Co == 64) return launch_halo<64, 64, 2, 2>(a, stats, st);
-  return 1;
 }
 
 template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS, int R, int S, int NS = 2, bool PFA = false, bool POOL = false,
@@ -911,168 +877,212 @@ int launch2_one(const IGemmArgs& a, hipStream_t st) {
   if (hipError_t e = asm_ensure_dyn_lds(kern, C::LDS, attr_done); e != hipSuccess)
     ASM_FAIL(ASM_EHIP, "igemm2_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
   ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(NTHR), C::LDS, st, a);
-  asm_last_conv_kernel = 2;
   ASM_CHECK_LAUNCH("igemm2_kernel");
   return ASM_OK;
 }
 
-// returns 1 if this (tile, tap shape) has no igemm2 instantiation
-template <int BM, int BN, int BK, int WGM, int WGN>
-int launch2_cfg(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st) {
-  a.n_tiles_n = cdiv(a.Co, BN);
-  a.n_blocks = (cdiv(a.M, BM) - a.m_tile0) * a.n_tiles_n;     // (m_tile0 != 0 only on the way to a 128-row tile)
-  a.kchunks = cdiv(a.Ci, BK);
-  a.fd_ntn = make_fastdiv((unsigned)a.n_tiles_n);
-  if (a.Ci % BK != 0 && a.kchunks != 1) return 1;
-  // addend-prefetching epilogue (see igemm_epilogue): where a launch is one round of few workgroups, or one 256-row
-  // workgroup per CU anyway; ASM_IGEMM_PFA=0 / 1 forces it off / on (tests, A/B)
-  const int pfa_env = asm_tune().igemm_pfa;
-  const bool pfa = a.addend != nullptr && !a.y_strided &&
-                   (pfa_env >= 0 ? pfa_env != 0 : (BM == 256 || a.n_blocks <= 1024));
-  if (a.R == 1 && a.S == 1) {
-    if (out_f32) return launch2_one<BM, BN, BK, WGM, WGN, true, false, 1, 1>(a, st);
-    if (stats && a.red_y) return launch2_one<BM, BN, BK, WGM, WGN, false, true, 1, 1, 2, false, false, 0, true>(a, st);
-    if (stats) return launch2_one<BM, BN, BK, WGM, WGN, false, true, 1, 1>(a, st);
-    if (a.pool_dy) return launch2_one<BM, BN, BK, WGM, WGN, false, false, 1, 1, 2, false, true>(a, st);
-    if (pfa) return launch2_one<BM, BN, BK, WGM, WGN, false, false, 1, 1, 2, true>(a, st);
-    return launch2_one<BM, BN, BK, WGM, WGN, false, false, 1, 1>(a, st);
-  }
-  if (out_f32) return 1;
-  if (a.R == 3 && a.S == 3) {
-    if (stats) return launch2_one<BM, BN, BK, WGM, WGN, false, true, 3, 3>(a, st);
-    if (pfa) return launch2_one<BM, BN, BK, WGM, WGN, false, false, 3, 3, 2, true>(a, st);
-    return launch2_one<BM, BN, BK, WGM, WGN, false, false, 3, 3>(a, st);
-  }
-  if (!stats) {   // parity classes of a stride-2 3x3 input gradient (asm_conv2d_dgrad)
-    if (a.R == 1 && a.S == 2) return launch2_one<BM, BN, BK, WGM, WGN, false, false, 1, 2>(a, st);
-    if (a.R == 2 && a.S == 1) return launch2_one<BM, BN, BK, WGM, WGN, false, false, 2, 1>(a, st);
-    if (a.R == 2 && a.S == 2) return launch2_one<BM, BN, BK, WGM, WGN, false, false, 2, 2>(a, st);
-  }
-  if constexpr (BK == 32 && BM == 128 && BN <= 64) {   // the two stems (R = k, S = 1 over the 4-channel halo buffer)
-    if (a.R == 7 && a.S == 1) {
-      if (stats) return launch2_one<BM, BN, BK, WGM, WGN, false, true, 7, 1>(a, st);
-      return launch2_one<BM, BN, BK, WGM, WGN, false, false, 7, 1>(a, st);
-    }
-    if (a.R == 3 && a.S == 1) {
-      if (stats) return launch2_one<BM, BN, BK, WGM, WGN, false, true, 3, 1>(a, st);
-      return launch2_one<BM, BN, BK, WGM, WGN, false, false, 3, 1>(a, st);
-    }
-  }
-  return 1;
+// the epilogue variants igemm2_kernel is instantiated with (launch2) for an R x S tap shape on a BM x BN x BK tile: every one
+// for the 1x1 layers; the 3x3 layers without f32 output, pooled gradient or batch-norm backward sums; the parity classes of a
+// stride-2 3x3 input gradient (1x2, 2x1, 2x2) plain; the two stems (7x1, 3x1 over the 4-channel halo buffer) on the small tiles
+constexpr unsigned igemm2_variants(int R, int S, int BM, int BN, int BK) {
+  if (R == 1 && S == 1)
+    return epi_bit(EPI_F32) | epi_bit(EPI_BNRED) | epi_bit(EPI_STATS) | epi_bit(EPI_POOL) | epi_bit(EPI_PFA) | epi_bit(EPI_PLAIN);
+  if (R == 3 && S == 3) return epi_bit(EPI_STATS) | epi_bit(EPI_PFA) | epi_bit(EPI_PLAIN);
+  if ((R == 1 && S == 2) || (R == 2 && S == 1) || (R == 2 && S == 2)) return epi_bit(EPI_PLAIN);
+  if ((R == 7 || R == 3) && S == 1 && BK == 32 && BM == 128 && BN <= 64) return epi_bit(EPI_STATS) | epi_bit(EPI_PLAIN);
+  return 0;
 }
 
-template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS, int MODE, bool BNRED = false>
+template <int BM, int BN, int BK, int WGM, int WGN, int R, int S>
+int launch2_rs(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
+  constexpr unsigned has = igemm2_variants(R, S, BM, BN, BK);
+  if constexpr ((has >> EPI_F32) & 1)
+    if (L.epi == EPI_F32) return launch2_one<BM, BN, BK, WGM, WGN, true, false, R, S>(a, st);
+  if constexpr ((has >> EPI_BNRED) & 1)
+    if (L.epi == EPI_BNRED) return launch2_one<BM, BN, BK, WGM, WGN, false, true, R, S, 2, false, false, 0, true>(a, st);
+  if constexpr ((has >> EPI_STATS) & 1)
+    if (L.epi == EPI_STATS) return launch2_one<BM, BN, BK, WGM, WGN, false, true, R, S>(a, st);
+  if constexpr ((has >> EPI_POOL) & 1)
+    if (L.epi == EPI_POOL) return launch2_one<BM, BN, BK, WGM, WGN, false, false, R, S, 2, false, true>(a, st);
+  if constexpr ((has >> EPI_PFA) & 1)
+    if (L.epi == EPI_PFA) return launch2_one<BM, BN, BK, WGM, WGN, false, false, R, S, 2, true>(a, st);
+  if constexpr ((has >> EPI_PLAIN) & 1)
+    if (L.epi == EPI_PLAIN) return launch2_one<BM, BN, BK, WGM, WGN, false, false, R, S>(a, st);
+  return conv_no_variant("igemm2_kernel", L.epi);
+}
+
+template <int BM, int BN, int BK, int WGM, int WGN>
+struct Launch2 {
+  static int run(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
+    if (a.R == 1 && a.S == 1) return launch2_rs<BM, BN, BK, WGM, WGN, 1, 1>(L, a, st);
+    if (a.R == 3 && a.S == 3) return launch2_rs<BM, BN, BK, WGM, WGN, 3, 3>(L, a, st);
+    if (a.R == 1 && a.S == 2) return launch2_rs<BM, BN, BK, WGM, WGN, 1, 2>(L, a, st);
+    if (a.R == 2 && a.S == 1) return launch2_rs<BM, BN, BK, WGM, WGN, 2, 1>(L, a, st);
+    if (a.R == 2 && a.S == 2) return launch2_rs<BM, BN, BK, WGM, WGN, 2, 2>(L, a, st);
+    if (a.R == 7 && a.S == 1) return launch2_rs<BM, BN, BK, WGM, WGN, 7, 1>(L, a, st);
+    if (a.R == 3 && a.S == 1) return launch2_rs<BM, BN, BK, WGM, WGN, 3, 1>(L, a, st);
+    return conv_no_variant("igemm2_kernel", L.epi);
+  }
+};
+
+template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS, bool BNRED = false>
 int launch_one(const IGemmArgs& a, hipStream_t st) {
-  using C = Cfg<BM, BN, BK, WGM, WGN, OUT_F32, STATS, MODE>;
-  auto kern = igemm_kernel<BM, BN, BK, WGM, WGN, OUT_F32, STATS, MODE, BNRED>;
+  using C = Cfg<BM, BN, BK, WGM, WGN, OUT_F32, STATS>;
+  auto kern = igemm_kernel<BM, BN, BK, WGM, WGN, OUT_F32, STATS, BNRED>;
   static bool attr_done[ASM_MAX_DEVICES] = {};
   if (hipError_t e = asm_ensure_dyn_lds(kern, C::LDS, attr_done); e != hipSuccess)
     ASM_FAIL(ASM_EHIP, "igemm_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
   ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(C::NT), C::LDS, st, a);
-  asm_last_conv_kernel = 0;
   ASM_CHECK_LAUNCH("igemm_kernel");
   return ASM_OK;
 }
 
-template <int BM, int BN, int BK, int WGM, int WGN, int MODE>
-int launch_mode(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st) {
-  a.n_tiles_n = cdiv(a.Co, BN);
-  a.n_blocks = cdiv(a.M, BM) * a.n_tiles_n;
-  a.kchunks = cdiv(a.Ci, BK);
-  if (out_f32) return launch_one<BM, BN, BK, WGM, WGN, true, false, MODE>(a, st);
-  if (stats && a.red_y) return launch_one<BM, BN, BK, WGM, WGN, false, true, MODE, true>(a, st);
-  if (stats) return launch_one<BM, BN, BK, WGM, WGN, false, true, MODE>(a, st);
-  return launch_one<BM, BN, BK, WGM, WGN, false, false, MODE>(a, st);
-}
-
-// ASM_IGEMM_MODE != 0 / ASM_IGEMM_TILE (1 = 128-row tiles, 3 = 256x256) force a choice (tests, tuning).
 template <int BM, int BN, int BK, int WGM, int WGN>
-int launch_cfg(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st) {
-  return launch_mode<BM, BN, BK, WGM, WGN, 2>(a, out_f32, stats, st);
-}
-
-// which of the specialised 3x3 kernels launch() would try for a layer (the knobs included)
-struct Sel3 {
-  bool bigv, to_igemm3, try8, try3;
+struct LaunchGeneral {
+  static int run(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
+    switch (L.epi) {
+      case EPI_F32: return launch_one<BM, BN, BK, WGM, WGN, true, false>(a, st);
+      case EPI_BNRED: return launch_one<BM, BN, BK, WGM, WGN, false, true, true>(a, st);
+      case EPI_STATS: return launch_one<BM, BN, BK, WGM, WGN, false, true>(a, st);
+      case EPI_PLAIN: return launch_one<BM, BN, BK, WGM, WGN, false, false>(a, st);
+    }
+    return conv_no_variant("igemm_kernel", L.epi);
+  }
 };
-Sel3 select_3x3(const IGemmArgs& a) {
-  const int ftile = asm_tune().igemm_tile, h3 = asm_tune().igemm3, h8 = asm_tune().igemm8;
-  const bool heavy = a.Ci % 64 == 0 && (long long)a.R * a.S * a.Ci >= 512;
-  const long long b256v = (long long)cdiv(a.M, 256) * cdiv(a.Co, 256);
-  Sel3 r;
-  r.bigv = heavy && a.Co >= 256 && b256v >= 192;
-  if (ftile == 1) r.bigv = false;
-  if (ftile == 3 && a.Ci % 64 == 0) r.bigv = true;
-  // (the short-reduction layers on >= 768 tiles stay on igemm3: 28x28x128 -> 256 forward 127 us there, 131 us on igemm8)
-  r.to_igemm3 = h3 && b256v >= 768 && a.Ci <= 128;
-  r.try8 = ftile == 0 && ((h8 == 1 && r.bigv && !r.to_igemm3) || h8 == 2);
-  r.try3 = ftile == 0 && h3 && (h3 == 2 || !r.bigv || r.to_igemm3);
-  return r;
+
+// the plan's tile as template arguments (the seven tiles of pick_tile)
+template <template <int, int, int, int, int> class F>
+int on_tile(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
+  const ConvTile& t = L.t;
+  if (t.bm == 256) return F<256, 256, 64, 4, 2>::run(L, a, st);
+  if (t.bn == 32) return t.bk == 64 ? F<128, 32, 64, 4, 1>::run(L, a, st) : F<128, 32, 32, 4, 1>::run(L, a, st);
+  if (t.bn == 64) return t.bk == 64 ? F<128, 64, 64, 2, 2>::run(L, a, st) : F<128, 64, 32, 2, 2>::run(L, a, st);
+  return t.bk == 64 ? F<128, 128, 64, 2, 2>::run(L, a, st) : F<128, 128, 32, 2, 2>::run(L, a, st);
 }
 
-// An input gradient that also reduces the batch-norm backward sums of its output (IGemmArgs::red_y) needs the BNRED instantiation
-// of whatever kernel runs it: for the 3x3 layers those exist for igemm8 and igemm3.  Would launch() end up on one of them?
-bool bnred_3x3_supported(const IGemmArgs& a) {
-  if (asm_tune().igemm_mode != 0 || asm_tune().igemm_tile != 0) return false;
-  if (halo_covers(a, false)) return false;       // launch() would send it to conv_halo_kernel: no such instantiation there
-  const Sel3 s3 = select_3x3(a);
-  return (s3.try8 && asm_igemm8_covers(a, false)) || (s3.try3 && igemm3_covers(a, false));
+// ---- the plan ----
+// what a launch writes: bf16, f32, bf16 + the batch-norm statistics, bf16 + the batch-norm backward sums (IGemmArgs::red_y)
+enum class ConvOut { bf16, f32, stats, bnred };
+
+// The MFMA-bound layers (K = R*S*C >= 512) go on 256 x 256 / 8 waves once there are >= 192 such tiles (C >= 256 outputs);
+// asm_tuning.igemm_tile = 1 / 3 forces 128-row tiles / 256 x 256 (where Ci % 64 == 0).
+bool tile256(const IGemmArgs& a) {
+  const int ftile = asm_tune().igemm_tile;
+  if (ftile == 1) return false;
+  if (ftile == 3 && a.Ci % 64 == 0) return true;
+  const long long b256 = (long long)cdiv(a.M, 256) * cdiv(a.Co, 256);
+  return a.Ci % 64 == 0 && (long long)a.R * a.S * a.Ci >= 512 && a.Co >= 256 && b256 >= 192;
 }
 
-int launch(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st, bool igemm2_only = false) {
-  // Measured on MI355X (tools/conv_bench.py, Assemble-ResNet-50 shapes, batch 256):
-  //  * HBM-bound layers (1x1, and everything at 112x112): LDS-DMA staging + the smallest footprint wins
-  //    (3-8 workgroups per CU hide the load round trip of the very short K loops);
-  //  * MFMA-bound layers (K = R*S*C >= 512): 256x256 / 8 waves wins once there are >= 192 such tiles (C>=256 outputs).
-  // 1x1 layers stage 32 channels per step (smallest footprint: the bandwidth-bound ones want many workgroups per CU) --
-  // except deep reductions on few tiles (7x7 / 14x14 / 28x28 maps), where each of the K / 32 steps is an exposed DMA
-  // round trip behind a barrier: up to 4000 tiles of 128 x 128 they take 64-channel steps (tools/conv_bench.py, all 1x1
-  // shapes of the network: fprop 2.36 -> 2.31 ms, input gradients 2.11 -> 2.03 ms per step).  (3x3 layers on 128-row tiles
-  // with 32-channel steps -- half the LDS, four workgroups per CU -- measured slower and were removed in round 6.)
-  const long long t128_all = (long long)cdiv(a.M, 128) * cdiv(a.Co, 128);
-  constexpr long long bk64_tiles = 4000;
-  const bool bk64 = a.Ci % 64 == 0 && (a.R * a.S > 1 || (a.Ci >= 256 && t128_all <= bk64_tiles));
-  const bool heavy = a.Ci % 64 == 0 && (long long)a.R * a.S * a.Ci >= 512;
-  const int fmode = asm_tune().igemm_mode, ftile = asm_tune().igemm_tile;
-  a.fd_howo = make_fastdiv((unsigned)a.HoWo);
-  a.fd_wo = make_fastdiv((unsigned)a.Wo);
-  const bool v2 = true;     // (asm_tuning.igemm_mode != 0 is what sends a layer to the general kernel)
-  if (a.pool_dy && !(v2 && fmode == 0 && !out_f32 && !stats && a.R == 1 && a.S == 1 && !a.y_strided))
-    ASM_FAIL(ASM_ENOTSUP, "conv dgrad_pooled: only the 1x1 stride-1 igemm2 path folds an average-pool backward in");
-  // only igemm8 and igemm3 have that instantiation for a 3x3 (in the bandwidth-bound halo kernel of the 112-wide maps the y reads
-  // cost 0.22 ms per step and saved 0.09 of reduce passes: measured, removed)
-  const bool bnred3 = stats && a.red_y && a.R * a.S > 1;
-  if (v2 && fmode == 0 && ftile == 0 && !bnred3) {
-    const int rc = try_halo(a, out_f32, stats, st);
-    if (rc != 1) return rc;
+// The tile of igemm2 and of the general kernel.  Measured on MI355X (tools/conv_bench.py, Assemble-ResNet-50 shapes, batch 256):
+//  * HBM-bound layers (1x1, and everything at 112x112): LDS-DMA staging + the smallest footprint wins
+//    (3-8 workgroups per CU hide the load round trip of the very short K loops);
+//  * MFMA-bound layers: tile256.
+// 1x1 layers stage 32 channels per step (smallest footprint: the bandwidth-bound ones want many workgroups per CU) --
+// except deep reductions on few tiles (7x7 / 14x14 / 28x28 maps), where each of the K / 32 steps is an exposed DMA
+// round trip behind a barrier: up to 4000 tiles of 128 x 128 they take 64-channel steps (tools/conv_bench.py, all 1x1
+// shapes of the network: fprop 2.36 -> 2.31 ms, input gradients 2.11 -> 2.03 ms per step).
+ConvTile pick_tile(const IGemmArgs& a) {
+  const long long t128 = (long long)cdiv(a.M, 128) * cdiv(a.Co, 128);
+  const bool bk64 = a.Ci % 64 == 0 && (a.R * a.S > 1 || (a.Ci >= 256 && t128 <= 4000));
+  if (a.Co <= 32) return bk64 ? ConvTile{128, 32, 64, 4, 1} : ConvTile{128, 32, 32, 4, 1};
+  if (a.Co <= 64) return bk64 ? ConvTile{128, 64, 64, 2, 2} : ConvTile{128, 64, 32, 2, 2};
+  if (tile256(a)) return ConvTile{256, 256, 64, 4, 2};
+  return bk64 ? ConvTile{128, 128, 64, 2, 2} : ConvTile{128, 128, 32, 2, 2};
+}
+
+unsigned family_variants(int family, const IGemmArgs& a, const ConvTile& t) {
+  switch (family) {
+    case FAM_GENERAL: return epi_bit(EPI_F32) | epi_bit(EPI_BNRED) | epi_bit(EPI_STATS) | epi_bit(EPI_PLAIN);
+    case FAM_IGEMM2: return igemm2_variants(a.R, a.S, t.bm, t.bn, t.bk);
+    case FAM_HALO: return epi_bit(EPI_STATS) | epi_bit(EPI_PLAIN);
+    case FAM_GEMM1: return epi_bit(EPI_BNRED) | epi_bit(EPI_STATS) | epi_bit(EPI_POOL) | epi_bit(EPI_PFA) | epi_bit(EPI_PLAIN);
+    default: return epi_bit(EPI_BNRED) | epi_bit(EPI_STATS) | epi_bit(EPI_PFA) | epi_bit(EPI_PLAIN);   // igemm3, igemm8
   }
-  if (v2 && fmode == 0 && ftile == 0 && a.R == 1 && a.S == 1 && asm_tune().gemm1 != 0) {
-    const int rc = asm_gemm1_try(a, out_f32, stats, st);   // ring-pipelined GEMM form of the 1x1 layers (conv_gemm1.hip)
-    if (rc != 1) return rc;
+}
+
+// One launch of `family` on tile t over row tiles m_tile0 .. cdiv(M, BM) - 1, with its epilogue variant.  The addend-prefetching
+// epilogue (PFA, see igemm_epilogue) goes where a launch is one round of few workgroups (<= 1024), on every 256-row tile (one
+// workgroup per CU anyway: igemm8, igemm2's 256 x 256) and never on a strided output (parity classes); asm_tuning.igemm_pfa =
+// 0 / 1 forces it off / on wherever the family has the variant.
+ConvLaunch tiled(int family, ConvTile t, const IGemmArgs& a, ConvOut out, int M, int m_tile0) {
+  ConvLaunch L = {};
+  L.family = family; L.t = t; L.M = M; L.m_tile0 = m_tile0;
+  L.n_tiles_n = cdiv(a.Co, t.bn);
+  L.n_blocks = (cdiv(M, t.bm) - m_tile0) * L.n_tiles_n;
+  L.kchunks = cdiv(a.Ci, t.bk);
+  const unsigned has = family_variants(family, a, t);
+  const int pfa_env = asm_tune().igemm_pfa;
+  const bool pfa = (has & epi_bit(EPI_PFA)) && a.addend != nullptr && !a.y_strided &&
+                   (pfa_env >= 0 ? pfa_env != 0 : (t.bm == 256 || L.n_blocks <= 1024));
+  const int want = out == ConvOut::f32 ? EPI_F32 : out == ConvOut::bnred ? EPI_BNRED : out == ConvOut::stats ? EPI_STATS
+                   : a.pool_dy ? EPI_POOL : pfa ? EPI_PFA : EPI_PLAIN;
+  L.epi = (has & epi_bit(want)) ? want : -1;
+  if (family == FAM_IGEMM3) {   // a layer with one 64-channel chunk has one halo buffer, of 192 rows up to 30 pixels wide
+    L.nhb = a.Ci == 64 ? 1 : 2;
+    L.hr = a.Ci == 64 && a.Wi > 30 ? 256 : 192;
   }
-  if (v2 && fmode == 0) {
-    int rc;
-    const Sel3 s3 = select_3x3(a);
-    const bool bigv = s3.bigv;
+  return L;
+}
+
+ConvPlan single(const ConvLaunch& L) { return ConvPlan{1, {L, {}}, nullptr}; }
+ConvPlan no_plan(const char* why) { return ConvPlan{0, {}, why}; }
+
+// The kernel of a forward / input-gradient layer: family, tile, epilogue variant, grid.  Pure: reads the arguments,
+// asm_tuning and the CU count only.  Where a family's coverage predicate accepts the layer, it takes it, in this order:
+// conv_halo (the narrow 112-wide 3x3 layers), igemm1 (the 1x1 layers of conv_gemm1.hip's table), igemm8 / igemm3 (3x3 stride 1),
+// igemm2 (the gather-free general form), the general kernel.  asm_tuning.igemm_mode = 1 sends every layer to the general kernel,
+// igemm_tile != 0 keeps the specialised families out.
+ConvPlan plan_conv(const IGemmArgs& a, ConvOut out) {
+  const asm_tuning& tu = asm_tune();
+  const bool f32 = out == ConvOut::f32, stats = out == ConvOut::stats || out == ConvOut::bnred;
+  const bool k1 = a.R == 1 && a.S == 1;
+  // the batch-norm backward sums of a 3x3 input gradient: only igemm8 and igemm3 have that instantiation (in the bandwidth-bound
+  // halo kernel of the 112-wide maps the y reads cost 0.22 ms per step and saved 0.09 of reduce passes: measured, removed)
+  const bool bnred3 = out == ConvOut::bnred && !k1;
+  if (a.pool_dy && (tu.igemm_mode != 0 || out != ConvOut::bf16 || !k1 || a.y_strided))
+    return no_plan("conv dgrad_pooled: only the 1x1 stride-1 igemm2 path folds an average-pool backward in");
+  if (tu.igemm_mode == 0 && tu.igemm_tile == 0) {
+    if (halo_covers(a, f32)) {
+      if (bnred3) return no_plan("conv dgrad_bnred: no kernel with the batch-norm sums for this 3x3 layer");
+      const int ko = a.Co, ci = a.Ci;
+      ConvLaunch L = tiled(FAM_HALO, ConvTile{128, ko, ci, ko == 32 ? 4 : 2, ko == 32 ? 1 : 2}, a, out, a.M, 0);
+      const int per_cu = ko == 32 ? (ci == 32 ? HaloCfg<32, 32>::PER_CU : HaloCfg<32, 64>::PER_CU)
+                                  : (ci == 32 ? HaloCfg<64, 32>::PER_CU : HaloCfg<64, 64>::PER_CU);
+      L.n_blocks = a.M / 128 < per_cu * 256 ? a.M / 128 : per_cu * 256;    // persistent: at most per_cu rounds of the chip
+      return single(L);
+    }
+    ConvTile t1;
+    if (const int code = asm_gemm1_config(a, f32, stats, &t1)) {   // the ring-pipelined GEMM form of the 1x1 layers
+      ConvLaunch L = tiled(FAM_GEMM1, t1, a, out, a.M, 0);
+      L.gemm1 = code;
+      return single(L);
+    }
     // igemm3_kernel (128 x 128 tiles, activation rows resident across the taps, two workgroups per CU) against igemm2
     // (tools/conv_bench.py --iters 50, same box, steady state): it wins wherever igemm2 would run 128-row tiles
     // (28x28x128 -> 256 input gradient 124 -> 112 us, 7x7x256 -> 512 37 -> 35 / 48.6 -> 40, 7x7x512 -> 1024 input gradient
     // 114 -> 108, 14x14x128 -> 256 input gradient 35.8 -> 33.2) and on the 784-tile short-reduction forward layer
     // (28x28x128 -> 256: 131 -> 117.5); against the 256 x 256 tile it loses 3 - 15 % where that tile fills the chip
-    // (its 8-wave loop reads 0.75 instead of 1 LDS fragment per MFMA and has half the barriers), so those stay.
-    // asm_tuning.igemm3 = 2 forces it wherever the shape allows (tests).
-    // (asm_tuning.igemm3 = 4 -- also the deep 14- / 7-wide layers of the 256 x 256 tile on igemm3 -- measured 0.2 ms slower in the
-    // step in rounds 5 and 6 and was removed.)
-    // igemm8_kernel: the layers of the 256 x 256 tile on the wave-staggered multi-phase loop (bit-identical results)
-    const int h8 = asm_tune().igemm8;
-    if (s3.try8) {
+    // (its 8-wave loop reads 0.75 instead of 1 LDS fragment per MFMA and has half the barriers), so those stay -- on
+    // igemm8_kernel, the 256 x 256 tile on the wave-staggered multi-phase loop (bit-identical results).
+    // asm_tuning.igemm3 = 2 forces igemm3 wherever the shape allows, igemm8 = 2 igemm8.
+    const int h3 = tu.igemm3, h8 = tu.igemm8;
+    const ConvTile t128 = {128, 128, 64, 2, 2};           // igemm3's tile
+    const bool big = tile256(a);
+    const long long b256 = (long long)cdiv(a.M, 256) * cdiv(a.Co, 256);
+    // (the short-reduction layers on >= 768 tiles stay on igemm3: 28x28x128 -> 256 forward 127 us there, 131 us on igemm8)
+    const bool to_igemm3 = h3 && b256 >= 768 && a.Ci <= 128;
+    const bool cov3 = h3 && igemm3_covers(a, f32);
+    if (((h8 == 1 && big && !to_igemm3) || h8 == 2) && asm_igemm8_covers(a, f32)) {
+      const ConvTile t8 = {256, 256, 64, 2, 4};
       // The ragged last round.  One 128 KB workgroup per CU: n tiles take ceil(n / CUs) rounds, and 784 tiles on 256 CUs
       // (14x14x512 -> 1024 and 28x28x128 -> 256 at batch 256) spend a whole round on their last 16.  When the tail is short,
-      // the row tiles of the full rounds go to igemm8 and the remaining rows to the 128 x 128 kernels (igemm3 / igemm2: four
-      // times the workgroups, two per CU, the same accumulation order -- the tensor stays bit-identical): 3 rounds + one
-      // small round (~0.3 of a big one when there is at most one small tile per CU, ~0.5 per round of two) instead of 4.
-      // Measured (14x14x512 -> 1024 forward, same box): 490.2 us igemm2, 455.5 us split (three igemm8 rounds ~355 us + ~100 us
-      // for the 64 small tiles, which run one per CU and are latency-bound: 72 lock-step steps).
+      // the row tiles of the full rounds go to igemm8 and the remaining rows to the 128 x 128 kernels (igemm3, else igemm2's
+      // 128 x 128 x 64: four times the workgroups, two per CU, the same accumulation order -- the tensor stays bit-identical):
+      // 3 rounds + one small round (~0.3 of a big one when there is at most one small tile per CU, ~0.5 per round of two)
+      // instead of 4.  Measured (14x14x512 -> 1024 forward, same box): 490.2 us igemm2, 455.5 us split (three igemm8 rounds
+      // ~355 us + ~100 us for the 64 small tiles, which run one per CU and are latency-bound: 72 lock-step steps).  The batch-norm
+      // backward sums need igemm3 for the rest.
       const int cus = asm_num_cus();
       const int nt8 = cdiv(a.Co, 256), mt8 = cdiv(a.M, 256);
       const long long n8 = (long long)nt8 * mt8;
@@ -1080,48 +1090,52 @@ int launch(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st, bool igemm2_o
       const long long rem = n8 - (long long)m_full * nt8;              // 256 x 256 tiles left over
       const double small = 4 * rem <= cus ? 0.3 : 0.5 * (double)((4 * rem + 2 * cus - 1) / (2 * cus));
       const double split_cost = (double)((long long)m_full * nt8 / cus) + small, whole_cost = (double)((n8 + cus - 1) / cus);
-      if (h8 == 1 && m_full > 0 && rem > 0 && split_cost < whole_cost - 0.15 && (!bnred3 || igemm3_covers(a, out_f32))) {
-        IGemmArgs head = a;
-        head.M = m_full * 256;            // rows of the full rounds (the gather itself is bounded by the tensor, not by M)
-        rc = asm_igemm8_try(head, out_f32, stats, st);
-        if (rc == ASM_OK) {
-          IGemmArgs tail = a;
-          tail.m_tile0 = m_full * 2;      // in 128-row tiles
-          rc = try_igemm3(tail, out_f32, stats, st);
-          if (rc == 1) rc = launch2_cfg<128, 128, 64, 2, 2>(tail, out_f32, stats, st);
-          if (rc == 1) ASM_FAIL(ASM_EINVAL, "conv: no 128-row kernel for the last rows of an igemm8 layer");
-          return rc;
-        }
-        if (rc != 1) return rc;
-      } else {
-        rc = asm_igemm8_try(a, out_f32, stats, st);
-        if (rc != 1) return rc;
+      if (h8 == 1 && m_full > 0 && rem > 0 && split_cost < whole_cost - 0.15 && (cov3 || !bnred3)) {
+        // (the head's gather is bounded by the tensor, not by M)
+        return ConvPlan{2, {tiled(FAM_IGEMM8, t8, a, out, m_full * 256, 0),
+                            tiled(cov3 ? FAM_IGEMM3 : FAM_IGEMM2, t128, a, out, a.M, m_full * 2)},
+                        nullptr};
       }
+      return single(tiled(FAM_IGEMM8, t8, a, out, a.M, 0));
     }
-    if (s3.try3) {
-      rc = try_igemm3(a, out_f32, stats, st);
-      if (rc != 1) return rc;
-    }
-    if (bnred3) ASM_FAIL(ASM_ENOTSUP, "conv dgrad_bnred: no kernel with the batch-norm sums for this 3x3 layer");
-    if (a.Co <= 32) rc = bk64 ? launch2_cfg<128, 32, 64, 4, 1>(a, out_f32, stats, st) : launch2_cfg<128, 32, 32, 4, 1>(a, out_f32, stats, st);
-    else if (a.Co <= 64) rc = bk64 ? launch2_cfg<128, 64, 64, 2, 2>(a, out_f32, stats, st) : launch2_cfg<128, 64, 32, 2, 2>(a, out_f32, stats, st);
-    else if (bigv) rc = launch2_cfg<256, 256, 64, 4, 2>(a, out_f32, stats, st);
-    else rc = bk64 ? launch2_cfg<128, 128, 64, 2, 2>(a, out_f32, stats, st) : launch2_cfg<128, 128, 32, 2, 2>(a, out_f32, stats, st);
-    if (rc != 1 || igemm2_only) return rc;
-    if (a.pool_dy) ASM_FAIL(ASM_ENOTSUP, "conv dgrad_pooled: no igemm2 instantiation for this shape");
+    if (cov3 && (h3 == 2 || !big || to_igemm3)) return single(tiled(FAM_IGEMM3, t128, a, out, a.M, 0));
   }
-  if (igemm2_only) return 1;
-  if (a.Co <= 32) return bk64 ? launch_cfg<128, 32, 64, 4, 1>(a, out_f32, stats, st)
-                              : launch_cfg<128, 32, 32, 4, 1>(a, out_f32, stats, st);
-  if (a.Co <= 64) return bk64 ? launch_cfg<128, 64, 64, 2, 2>(a, out_f32, stats, st)
-                              : launch_cfg<128, 64, 32, 2, 2>(a, out_f32, stats, st);
-  const long long b256 = (long long)cdiv(a.M, 256) * cdiv(a.Co, 256);
-  bool big = heavy && a.Co >= 256 && b256 >= 192;
-  if (ftile == 1) big = false;
-  if (ftile == 3 && a.Ci % 64 == 0) big = true;
-  if (big) return launch_cfg<256, 256, 64, 4, 2>(a, out_f32, stats, st);
-  return bk64 ? launch_cfg<128, 128, 64, 2, 2>(a, out_f32, stats, st)
-              : launch_cfg<128, 128, 32, 2, 2>(a, out_f32, stats, st);
+  if (bnred3) return no_plan("conv dgrad_bnred: no kernel with the batch-norm sums for this 3x3 layer");
+  const ConvTile t = pick_tile(a);
+  if (tu.igemm_mode == 0) {
+    const ConvLaunch L = tiled(FAM_IGEMM2, t, a, out, a.M, 0);
+    if (L.epi >= 0 && (a.Ci % t.bk == 0 || a.Ci <= t.bk)) return single(L);
+    if (a.pool_dy) return no_plan("conv dgrad_pooled: no igemm2 instantiation for this shape");
+  }
+  return single(tiled(FAM_GENERAL, t, a, out, a.M, 0));
+}
+
+// the dispatcher: each launch of the plan on its template instantiation
+int run_plan(const ConvPlan& p, IGemmArgs a, hipStream_t st) {
+  if (p.n == 0) ASM_FAIL(ASM_ENOTSUP, "%s", p.why);
+  a.fd_howo = make_fastdiv((unsigned)a.HoWo);
+  a.fd_wo = make_fastdiv((unsigned)a.Wo);
+  for (int i = 0; i < p.n; ++i) {
+    const ConvLaunch& L = p.l[i];
+    a.M = L.M; a.m_tile0 = L.m_tile0; a.n_tiles_n = L.n_tiles_n; a.n_blocks = L.n_blocks; a.kchunks = L.kchunks;
+    a.fd_ntn = make_fastdiv((unsigned)L.n_tiles_n);
+    int rc;
+    switch (L.family) {
+      case FAM_GENERAL: rc = on_tile<LaunchGeneral>(L, a, st); break;
+      case FAM_GEMM1: rc = asm_gemm1_launch(L, a, st); break;
+      case FAM_IGEMM2: rc = on_tile<Launch2>(L, a, st); break;
+      case FAM_IGEMM3: rc = L.nhb == 2 ? launch3<192, 2>(L, a, st) : L.hr == 192 ? launch3<192, 1>(L, a, st) : launch3<256, 1>(L, a, st); break;
+      case FAM_HALO:   // KO = BN output, CI = BK input channels
+        rc = L.t.bn == 32 ? (L.t.bk == 64 ? launch_halo<32, 64, 4, 1>(L, a, st) : launch_halo<32, 32, 4, 1>(L, a, st))
+                          : (L.t.bk == 64 ? launch_halo<64, 64, 2, 2>(L, a, st) : launch_halo<64, 32, 2, 2>(L, a, st));
+        break;
+      case FAM_IGEMM8: rc = asm_igemm8_launch(L, a, st); break;
+      default: ASM_FAIL(ASM_EINVAL, "conv: no kernel family %d", L.family);
+    }
+    if (rc != ASM_OK) return rc;
+  }
+  asm_last_conv_kernel = p.l[p.n - 1].family;
+  return ASM_OK;
 }
 
 int check_desc(const asm_conv_desc* d) {
@@ -1159,8 +1173,8 @@ static int fprop_impl(const asm_conv_desc* d, const void* x, const void* w, void
   const int ldy = d->ldy ? d->ldy : d->K;
   ASM_REQUIRE(ldy % (d->out_f32 ? 4 : 8) == 0 && ldy >= d->K, "conv fprop: bad ldy %d", ldy);
   ASM_REQUIRE(!(stats_partial && d->out_f32), "conv fprop: fused statistics need bf16 output");
-  IGemmArgs a;
-  a.x = x; a.w = w; a.y = y; a.addend = residual; a.addend_mask = nullptr; a.stats = stats_partial;
+  IGemmArgs a = {};
+  a.x = x; a.w = w; a.y = y; a.addend = residual; a.stats = stats_partial;
   a.x_bytes = (unsigned)(xelems * 2);
   a.w_bytes = (unsigned)((int64_t)d->K * d->R * d->S * d->C * 2);
   a.M = d->N * d->Ho * d->Wo;
@@ -1169,15 +1183,12 @@ static int fprop_impl(const asm_conv_desc* d, const void* x, const void* w, void
   a.Co = d->K; a.ldy = ldy;
   a.R = d->R; a.S = d->S;
   a.so = d->stride; a.sd = 1; a.tsign = 1; a.pad = d->pad;
-  a.pad_w = a.pad; a.wt0 = 0; a.wtr = a.S; a.wts = 1; a.y_strided = 0;
-  a.y_base = a.y_img_pitch = a.y_row_pitch = a.y_pix_pitch = 0;
+  a.pad_w = a.pad; a.wt0 = 0; a.wtr = a.S; a.wts = 1;
   a.bn_scale = bn_scale; a.bn_shift = bn_shift; a.bn_relu = relu;
-  a.pool_dy = nullptr; a.pool_k = a.pool_stride = a.pool_pad = a.pool_Hp = a.pool_Wp = a.pool_cv = a.pool_H = 0;
-  a.red_y = nullptr; a.red_mask = nullptr;
   a.x_img_pitch = (int)img_pitch(d); a.x_row_pitch = row_pitch(d); a.x_pix_pitch = pix_pitch(d);
   a.w_row_pitch = d->R * d->S * d->C;
-  a.m_tile0 = 0;
-  return launch(a, d->out_f32 != 0, stats_partial != nullptr, (hipStream_t)stream);
+  const ConvOut out = d->out_f32 ? ConvOut::f32 : stats_partial ? ConvOut::stats : ConvOut::bf16;
+  return run_plan(plan_conv(a, out), a, (hipStream_t)stream);
 }
 
 extern "C" int asm_conv2d_fprop(const asm_conv_desc* d, const void* x, const void* w, void* y,
@@ -1205,6 +1216,23 @@ struct BnRed {      // asm_conv2d_dgrad_bnred: batch-norm backward sums of the g
 static int dgrad_impl(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend,
                       const uint8_t* addend_mask, void* dx, void* stream, const PoolAdd* pool = nullptr,
                       const BnRed* red = nullptr);
+// the input gradient as the generic gather over dy (p = (h + pad - r) / stride when divisible), without its tensors:
+// M = N*H*W rows of dx, N = C, the reduction over K*R*S
+static IGemmArgs dgrad_args(const asm_conv_desc* d) {
+  IGemmArgs a = {};
+  a.x_bytes = (unsigned)((int64_t)d->N * d->Ho * d->Wo * d->K * 2);
+  a.w_bytes = (unsigned)((int64_t)d->K * d->R * d->S * d->C * 2);
+  a.M = d->N * d->H * d->W;
+  a.Hi = d->Ho; a.Wi = d->Wo; a.Ci = d->K;
+  a.Wo = d->W; a.HoWo = d->H * d->W;
+  a.Co = d->C; a.ldy = d->C;
+  a.R = d->R; a.S = d->S;
+  a.so = 1; a.sd = d->stride; a.tsign = -1; a.pad = -d->pad; a.pad_w = a.pad;
+  a.x_img_pitch = d->Ho * d->Wo * d->K; a.x_row_pitch = d->Wo * d->K; a.x_pix_pitch = d->K;
+  a.w_row_pitch = d->R * d->S * d->K;
+  a.wt0 = 0; a.wtr = a.S; a.wts = 1;
+  return a;
+}
 // conv_dgrad_s2.hip: the one-launch 3x3 / stride-2 input gradient (returns 1 when the layer is not one it covers)
 int asm_dgrad_s2_try(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend, const uint8_t* addend_mask,
                      void* dx, void* stream);
@@ -1237,24 +1265,16 @@ extern "C" int asm_conv2d_dgrad_pooled(const asm_conv_desc* d, const void* dy, c
   return dgrad_impl(d, dy, wt, addend, addend_mask, dx, stream, &pa);
 }
 
-// does asm_conv2d_dgrad_bnred cover this layer?  1x1 / stride 1 / no padding (every kernel of that class has the instantiation),
-// and the 3x3 / stride 1 / pad 1 layers that launch() sends to igemm8_kernel or igemm3_kernel
+// does asm_conv2d_dgrad_bnred cover this layer?  1x1 / stride 1 / no padding and 3x3 / stride 1 / pad 1 layers whose plan has
+// the batch-norm backward sums in every launch (all 1x1 kernels have them; of the 3x3 ones igemm8 and igemm3)
 static bool dgrad_bnred_covers(const asm_conv_desc* d) {
   if (!d || d->C % 8 || d->K % 8 || d->stride != 1 || d->x_img_pitch || d->x_row_pitch || d->x_pix_pitch || d->out_f32) return false;
-  if (d->R == 1 && d->S == 1 && d->pad == 0) return true;
-  if (d->R != 3 || d->S != 3 || d->pad != 1 || d->Ho != d->H || d->Wo != d->W) return false;
-  IGemmArgs a;            // the geometry of dgrad_impl's generic form, as far as the selection reads it
-  a.M = d->N * d->H * d->W;
-  a.Hi = d->Ho; a.Wi = d->Wo; a.Ci = d->K;
-  a.Wo = d->W; a.HoWo = d->H * d->W;
-  a.Co = d->C; a.ldy = d->C;
-  a.R = 3; a.S = 3;
-  a.x_bytes = (unsigned)((int64_t)d->N * d->Ho * d->Wo * d->K * 2);
-  a.x_img_pitch = d->Ho * d->Wo * d->K; a.x_row_pitch = d->Wo * d->K; a.x_pix_pitch = d->K;
-  a.wt0 = 0; a.wtr = 3; a.wts = 1; a.y_strided = 0; a.m_tile0 = 0;
-  a.pool_dy = nullptr; a.bn_scale = nullptr;
-  a.so = 1; a.sd = 1; a.tsign = -1; a.pad = -1; a.pad_w = -1;
-  return bnred_3x3_supported(a);
+  if (!(d->R == 1 && d->S == 1 && d->pad == 0) && !(d->R == 3 && d->S == 3 && d->pad == 1 && d->Ho == d->H && d->Wo == d->W))
+    return false;
+  const ConvPlan p = plan_conv(dgrad_args(d), ConvOut::bnred);
+  for (int i = 0; i < p.n; ++i)
+    if (p.l[i].epi != EPI_BNRED) return false;
+  return p.n > 0;
 }
 
 // partial rows of asm_conv2d_dgrad_bnred for this layer; 0: the layer is not one it covers
@@ -1285,23 +1305,11 @@ static int dgrad_impl(const asm_conv_desc* d, const void* dy, const void* wt, co
               "conv dgrad: custom pitches / f32 output not supported");
   const int64_t dyelems = (int64_t)d->N * d->Ho * d->Wo * d->K;
   ASM_REQUIRE(dyelems * 2 < (int64_t)ASM_OOB, "conv dgrad: dy larger than 2 GiB");
-  IGemmArgs a;
+  IGemmArgs a = dgrad_args(d);
   a.x = dy; a.w = wt; a.y = dx; a.addend = addend; a.addend_mask = addend_mask;
-  a.stats = red ? red->partial : nullptr;
-  a.red_y = red ? red->y : nullptr; a.red_mask = red ? red->mask : nullptr;
-  a.x_bytes = (unsigned)(dyelems * 2);
-  a.w_bytes = (unsigned)((int64_t)d->K * d->R * d->S * d->C * 2);
-  a.M = d->N * d->H * d->W;
-  a.Hi = d->Ho; a.Wi = d->Wo; a.Ci = d->K;
-  a.Wo = d->W; a.HoWo = d->H * d->W;
-  a.Co = d->C; a.ldy = d->C;
-  a.R = d->R; a.S = d->S;
-  a.x_img_pitch = d->Ho * d->Wo * d->K; a.x_row_pitch = d->Wo * d->K; a.x_pix_pitch = d->K;
-  a.w_row_pitch = d->R * d->S * d->K;
-  a.wt0 = 0; a.wtr = a.S; a.wts = 1; a.y_strided = 0; a.m_tile0 = 0;
-  a.y_base = a.y_img_pitch = a.y_row_pitch = a.y_pix_pitch = 0;
-  a.bn_scale = a.bn_shift = nullptr; a.bn_relu = 0;
-  a.pool_dy = nullptr; a.pool_k = a.pool_stride = a.pool_pad = a.pool_Hp = a.pool_Wp = a.pool_cv = a.pool_H = 0;
+  if (red) {
+    a.stats = red->partial; a.red_y = red->y; a.red_mask = red->mask;
+  }
   if (pool) {
     a.pool_dy = pool->dy; a.pool_k = pool->k; a.pool_stride = pool->stride; a.pool_pad = pool->pad;
     a.pool_Hp = pool->Hp; a.pool_Wp = pool->Wp; a.pool_cv = pool->cv; a.pool_H = d->H;
@@ -1339,6 +1347,11 @@ static int dgrad_impl(const asm_conv_desc* d, const void* dy, const void* wt, co
       c.y_img_pitch = d->H * d->W * d->C; c.y_row_pitch = 2 * d->W * d->C; c.y_pix_pitch = 2 * d->C;
       if (!launched && k1 && addend_mask)
         ASM_FAIL(ASM_ENOTSUP, "conv dgrad_masked: a masked addend is not supported for the 1x1 stride-2 input gradient");
+      const ConvPlan pl = plan_conv(c, ConvOut::bf16);
+      if (pl.n > 0 && pl.l[0].family == FAM_GENERAL) {   // no gather-free kernel for this class: the generic gather below
+        if (launched) ASM_FAIL(ASM_ENOTSUP, "conv dgrad: parity classes launched inconsistently");
+        break;
+      }
       if (!launched && k1) {   // fill the untouched classes before the one launch that overwrites its own pixels
         const size_t bytes = (size_t)a.M * d->C * 2;
         hipError_t e = (addend && addend != dx) ? asm_fill_async(dx, addend, 0, bytes, (hipStream_t)stream)
@@ -1346,17 +1359,10 @@ static int dgrad_impl(const asm_conv_desc* d, const void* dy, const void* wt, co
                               : asm_fill_async(dx, nullptr, 0, bytes, (hipStream_t)stream);
         if (e != hipSuccess) ASM_FAIL(ASM_EHIP, "conv dgrad: fill: %s", hipGetErrorString(e));
       }
-      const int rc = launch(c, false, false, (hipStream_t)stream, /*igemm2_only=*/true);
-      if (rc == 1) {           // no igemm2 instantiation for this shape: nothing was launched for this class
-        if (launched) ASM_FAIL(ASM_ENOTSUP, "conv dgrad: parity classes launched inconsistently");
-        break;                 // (a stray fill above is overwritten by the generic kernel below)
-      }
-      if (rc != ASM_OK) return rc;
+      if (const int rc = run_plan(pl, c, (hipStream_t)stream)) return rc;
       launched = true;
     }
     if (launched) return ASM_OK;
   }
-  // generic form: p = (h + pad - r) / stride  when divisible
-  a.so = 1; a.sd = d->stride; a.tsign = -1; a.pad = -d->pad; a.pad_w = a.pad;
-  return launch(a, false, red != nullptr, (hipStream_t)stream);
+  return run_plan(plan_conv(a, red ? ConvOut::bnred : ConvOut::bf16), a, (hipStream_t)stream);
 }

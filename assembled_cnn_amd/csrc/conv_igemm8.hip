@@ -56,7 +56,7 @@ struct IC {
 
 template <bool STATS, bool PFA, bool BNRED = false>
 __global__ __launch_bounds__(512) void igemm8_kernel(IGemmArgs p) {
-  using C = Cfg<256, 256, 64, 2, 4, false, STATS, 2>;
+  using C = Cfg<256, 256, 64, 2, 4, false, STATS>;
   constexpr int ROWB = 128, HALF = 128 * ROWB, TILE = 4 * HALF;
   constexpr int OFF_W0 = 0, OFF_X0 = HALF, OFF_W1 = 2 * HALF, OFF_X1 = 3 * HALF;
   constexpr int NTAP = 9, KK = 4;
@@ -256,7 +256,7 @@ __global__ __launch_bounds__(512) void igemm8_kernel(IGemmArgs p) {
 
 template <bool STATS, bool PFA, bool BNRED = false>
 int launch8_one(const IGemmArgs& a, hipStream_t st) {
-  using C = Cfg<256, 256, 64, 2, 4, false, STATS, 2>;
+  using C = Cfg<256, 256, 64, 2, 4, false, STATS>;
   constexpr int LDS = cmax(cmax(2 * 4 * 128 * 128, C::EPI), C::RED);
   static_assert(LDS <= 160 * 1024, "lds");
   auto kern = igemm8_kernel<STATS, PFA, BNRED>;
@@ -264,7 +264,6 @@ int launch8_one(const IGemmArgs& a, hipStream_t st) {
   if (hipError_t e = asm_ensure_dyn_lds(kern, LDS, attr_done); e != hipSuccess)
     ASM_FAIL(ASM_EHIP, "igemm8_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
   ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(512), LDS, st, a);
-  asm_last_conv_kernel = 8;
   ASM_CHECK_LAUNCH("igemm8_kernel");
   return ASM_OK;
 }
@@ -280,17 +279,12 @@ bool asm_igemm8_covers(const IGemmArgs& a, bool out_f32) {
   return span < (long long)ASM_OOB;
 }
 
-// returns 1 when the layer is not one igemm8_kernel covers (the caller goes on to igemm3 / igemm2)
-int asm_igemm8_try(IGemmArgs& a, bool out_f32, bool stats, hipStream_t st) {
-  if (!asm_igemm8_covers(a, out_f32)) return 1;
-  a.n_tiles_n = cdiv(a.Co, 256);
-  a.n_blocks = cdiv(a.M, 256) * a.n_tiles_n;
-  a.kchunks = a.Ci / 64;
-  a.fd_ntn = make_fastdiv((unsigned)a.n_tiles_n);
-  const int pfa_env = asm_tune().igemm_pfa;
-  const bool pfa = a.addend != nullptr && (pfa_env >= 0 ? pfa_env != 0 : true);
-  if (stats && a.red_y) return launch8_one<true, false, true>(a, st);   // the batch-norm backward sums of an input gradient
-  if (stats) return launch8_one<true, false>(a, st);
-  if (pfa) return launch8_one<false, true>(a, st);
-  return launch8_one<false, false>(a, st);
+int asm_igemm8_launch(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
+  switch (L.epi) {
+    case EPI_BNRED: return launch8_one<true, false, true>(a, st);   // the batch-norm backward sums of an input gradient
+    case EPI_STATS: return launch8_one<true, false>(a, st);
+    case EPI_PFA: return launch8_one<false, true>(a, st);
+    case EPI_PLAIN: return launch8_one<false, false>(a, st);
+  }
+  return conv_no_variant("igemm8_kernel", L.epi);
 }

@@ -49,6 +49,34 @@ struct IGemmArgs {
 
 constexpr int STATS_BM = 128;  // rows per statistics partial (asm_conv2d_stats_blocks)
 
+// ---- the kernel a forward / input-gradient launch runs: plan_conv (conv_igemm.hip) decides, run_plan launches ----
+// kernel families, numbered as asm_debug_last_conv_kernel reports them
+enum ConvFamily { FAM_GENERAL = 0, FAM_GEMM1 = 1, FAM_IGEMM2 = 2, FAM_IGEMM3 = 3, FAM_HALO = 4, FAM_IGEMM8 = 8 };
+// epilogue variant (igemm_epilogue's template flags): plain, addend-prefetching (PFA), pooled-gradient gather, statistics,
+// batch-norm backward sums (BNRED), f32 output
+enum ConvEpi { EPI_PLAIN, EPI_PFA, EPI_POOL, EPI_STATS, EPI_BNRED, EPI_F32 };
+constexpr unsigned epi_bit(int e) { return 1u << e; }
+struct ConvTile {
+  int bm, bn, bk, wgm, wgn;   // BM x BN block tile, BK channels per step, WGM x WGN waves (conv_halo: BN = KO, BK = CI)
+};
+struct ConvLaunch {
+  int family;                 // ConvFamily
+  int epi;                    // ConvEpi; -1: the family has no instantiation for what the launch must write
+  ConvTile t;
+  int gemm1;                  // igemm1: the configuration code of conv_gemm1.hip's table
+  int hr, nhb;                // igemm3: halo rows per buffer, halo buffers
+  int M, m_tile0;             // rows of the launch's tiles: row tiles m_tile0 .. cdiv(M, BM) - 1
+  int n_tiles_n, n_blocks, kchunks;
+};
+struct ConvPlan {
+  int n;                      // 1, or 2: the ragged last round of an igemm8 layer (its full rounds, then the rest on 128-row
+                              // tiles); 0: no kernel covers the layer
+  ConvLaunch l[2];
+  const char* why;            // n == 0: the reason ASM_ENOTSUP reports
+};
+// a dispatcher handed a variant its family was not instantiated with (plan and dispatcher disagree)
+static inline int conv_no_variant(const char* kernel, int epi) { ASM_FAIL(ASM_EINVAL, "conv: %s has no epilogue variant %d", kernel, epi); }
+
 template <int BK>
 __device__ __forceinline__ int swz(int row) {
   // BK=64: 8 chunks / 128-B row ; BK=32: 4 chunks / 64-B row.  16 rows that are distinct mod 16
@@ -62,9 +90,7 @@ constexpr int cmax(int a, int b) { return a > b ? a : b; }
 // 32x32 MFMA tiles.  Arithmetic intensity against the L2->LDS path is 2*BM*BN/((BM+BN)*2) FLOP/B:
 // 64 for 128x128, 85 for 256x128, 128 for 256x256 -- the MFMA-bound layers need the big tiles, the
 // HBM-bound ones the small footprints (more workgroups per CU).
-// MODE: 0 = register-staged, 1-deep prefetch; 1 = register-staged, 2-deep prefetch (two register tile sets);
-//       2 = LDS-DMA staging (global_load_lds_dwordx4: no VGPR round trip, no ds_write), 1-deep.
-template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS, int MODE>
+template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS>
 struct Cfg {
   static constexpr int NT = 64 * WGM * WGN;
   static constexpr int CPR = BK / 8;            // 16-byte chunks per tile row
@@ -152,7 +178,7 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& p, f32x16 (&acc)
     // pass's store (they may alias: in-place accumulation is allowed), i.e. one exposed HBM round trip per pass, 8-16 per
     // workgroup: that is what bounds the input gradients of the small maps (7x7 / 14x14: a few hundred workgroups, nothing
     // to overlap with; measured -20..-25 % there).  On the large maps the extra ~40 registers cost occupancy and the
-    // bandwidth-bound 1x1 layers lose 10-30 %, so the launcher picks the variant per layer (launch2_cfg).  A thread only
+    // bandwidth-bound 1x1 layers lose 10-30 %, so the plan picks the variant per layer (plan_conv).  A thread only
     // ever re-reads the addresses it writes itself, so in-place accumulation stays exact.
     constexpr bool PF_ON = PFA && !STATS;
     constexpr int PF = !PF_ON ? 1 : (OP < 8 ? OP : 8);

@@ -677,6 +677,25 @@ def test_igemm8_ragged_last_round_split(hip_lib, monkeypatch):
   g1 = ops.conv_dgrad(d2, dy, wt, addend=add)
   assert hip_lib.asm_launch_count() - n0 == 2
   assert torch.equal(g0, g1)
+  # the same input gradient with the batch-norm backward sums in its epilogue (igemm8 head + igemm3 tail, both BNRED): dx must be
+  # the plain input gradient's bits and the partial rows those of the whole layer on igemm3 (ASM_IGEMM8=0, ASM_IGEMM3=2)
+  Cx, M = K, N * H * W
+  by = (_rand((N, H, W, Cx), 26).float() * 1.5 + 0.7).to(BF).cuda()
+  rmask = torch.randint(0, 256, (M, Cx // 8), generator=torch.Generator().manual_seed(27), dtype=torch.uint8).cuda()
+  util.set_knob(monkeypatch, 'ASM_IGEMM8', '0')
+  ref = ops.conv_dgrad(d2, dy, wt)
+  for mask in (None, rmask):
+    util.set_knob(monkeypatch, 'ASM_IGEMM8', '0')
+    util.set_knob(monkeypatch, 'ASM_IGEMM3', '2')
+    dx0, p0 = ops.conv_dgrad_bnred(d2, dy, wt, None, None, by, mask)
+    assert hip_lib.asm_debug_last_conv_kernel() == 3
+    util.set_knob(monkeypatch, 'ASM_IGEMM3', '3')
+    util.set_knob(monkeypatch, 'ASM_IGEMM8', '1')
+    n0 = hip_lib.asm_launch_count()
+    dx1, p1 = ops.conv_dgrad_bnred(d2, dy, wt, None, None, by, mask)
+    assert hip_lib.asm_launch_count() - n0 == 2 and hip_lib.asm_debug_last_conv_kernel() == 3, 'expected igemm8 + igemm3'
+    assert torch.equal(dx1, ref) and torch.equal(dx0, ref)
+    assert p1.shape[0] == (M + 127) // 128 and torch.equal(p0, p1)
 
 
 BNRED_CASES = [

@@ -12,7 +12,7 @@ print('`tools/gemm1_sweep.py%s` on one MI355X, batch 256, every 1x1 stride-1 sha
 print('warm / cold (HIP events; warm = 20 back-to-back launches, cold = each launch behind a 512 MB fill).  Code 0 = the kernel the library')
 print('chose before this round (igemm2_kernel / the register-staged weight gradient); the other codes are the configurations of')
 print('`%s`.  Outputs are bit-identical to code 0 for every cell shown (fused statistics: same sums in another order).\n'
-      % ('wgrad_kernel<.., LIN, NS>: NS = code' if d.get('field') == 'wgrad_ring' else 'csrc/conv_gemm1.hip (asm_gemm1_try)'))
+      % ('wgrad_kernel<.., LIN, NS>: NS = code' if d.get('field') == 'wgrad_ring' else 'csrc/conv_gemm1.hip (kConfigs)'))
 print('| kind | map | C -> K | launches / step | ' + ' | '.join(str(c) for c in codes) + ' | best | vs 0 |')
 print('|---|---|---|---:|' + '---:|' * len(codes) + '---:|---:|')
 for r in d['rows']:
