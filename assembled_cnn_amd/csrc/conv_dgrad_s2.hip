@@ -206,14 +206,16 @@ __global__ __launch_bounds__(256, 1) void dgrad_s2_kernel(S2Args p) {
 
 }  // namespace
 
-// returns 1 when the layer is not one this kernel covers (the caller falls back to the parity-class launches)
-int asm_dgrad_s2_try(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend, const uint8_t* addend_mask,
-                     void* dx, void* stream) {
-  if (asm_tune().dgrad_parity < 2) return 1;
-  if (d->R != 3 || d->S != 3 || d->stride != 2 || d->pad != 1 || d->C != 64 || d->K != 64) return 1;
-  if (d->H != 2 * d->Ho || d->W != 2 * d->Wo || d->Ho % 8 || d->Wo % 8) return 1;
-  if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(wt) | reinterpret_cast<uintptr_t>(dx) |
-       reinterpret_cast<uintptr_t>(addend)) & 15) return 1;
+// does dgrad_s2_kernel cover this layer (3x3 / stride 2 / pad 1, 64 -> 64 channels, dy in whole 8 x 8 patches; asm_tuning
+// dgrad_parity >= 2 and igemm_mode 0)?  The plan in conv_igemm.hip (plan_dgrad) also needs 16-byte-aligned operands.
+bool asm_dgrad_s2_covers(const asm_conv_desc* d) {
+  if (asm_tune().dgrad_parity < 2 || asm_tune().igemm_mode != 0) return false;
+  if (d->R != 3 || d->S != 3 || d->stride != 2 || d->pad != 1 || d->C != 64 || d->K != 64) return false;
+  return d->H == 2 * d->Ho && d->W == 2 * d->Wo && d->Ho % 8 == 0 && d->Wo % 8 == 0;
+}
+
+int asm_dgrad_s2_launch(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend, const uint8_t* addend_mask,
+                        void* dx, void* stream) {
   S2Args a;
   a.dy = dy; a.wt = wt; a.dx = dx; a.addend = addend; a.mask = addend_mask;
   a.dy_bytes = (unsigned)((size_t)d->N * d->Ho * d->Wo * 64 * 2);
@@ -221,7 +223,6 @@ int asm_dgrad_s2_try(const asm_conv_desc* d, const void* dy, const void* wt, con
   a.ppr = d->Wo / 8; a.ppi = a.ppr * (d->Ho / 8); a.patches = a.ppi * d->N;
   const int grid = a.patches < 256 ? a.patches : 256;      // one persistent workgroup per CU
   ASM_LAUNCH(dgrad_s2_kernel, dim3(grid), dim3(256), S2_LDS, (hipStream_t)stream, a);
-  asm_last_conv_kernel = 5;
   ASM_CHECK_LAUNCH("dgrad_s2_kernel");
   return ASM_OK;
 }

@@ -1233,9 +1233,88 @@ static IGemmArgs dgrad_args(const asm_conv_desc* d) {
   a.wt0 = 0; a.wtr = a.S; a.wts = 1;
   return a;
 }
-// conv_dgrad_s2.hip: the one-launch 3x3 / stride-2 input gradient (returns 1 when the layer is not one it covers)
-int asm_dgrad_s2_try(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend, const uint8_t* addend_mask,
-                     void* dx, void* stream);
+// the descriptor checks of every input-gradient entry point
+static int dgrad_check(const asm_conv_desc* d) {
+  if (int e = check_desc(d)) return e;
+  ASM_REQUIRE(d->K % 8 == 0, "conv dgrad: K=%d must be a multiple of 8 (pad dy)", d->K);
+  ASM_REQUIRE(d->x_img_pitch == 0 && d->x_row_pitch == 0 && d->x_pix_pitch == 0 && !d->out_f32,
+              "conv dgrad: custom pitches / f32 output not supported");
+  const int64_t dyelems = (int64_t)d->N * d->Ho * d->Wo * d->K;
+  ASM_REQUIRE(dyelems * 2 < (int64_t)ASM_OOB, "conv dgrad: dy larger than 2 GiB");
+  return ASM_OK;
+}
+// conv_dgrad_s2.hip: the one-launch 3x3 / stride-2 input gradient
+bool asm_dgrad_s2_covers(const asm_conv_desc* d);
+int asm_dgrad_s2_launch(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend, const uint8_t* addend_mask,
+                        void* dx, void* stream);
+
+// The kernels of an input gradient, all chosen before the first launch: dgrad_s2_kernel, the parity classes of a stride-2 layer,
+// or the plan_conv plan of the generic gather (which also carries an ASM_ENOTSUP).
+enum class DgradForm { conv, parity, s2 };
+struct DgradPlan {
+  DgradForm form;
+  int nc;                     // parity: classes, each a dense stride-1 gather over dy (cls[i]) on its plan (cp[i])
+  IGemmArgs cls[4];
+  ConvPlan cp[4];
+  bool fill;                  // parity of a 1x1 layer: fill dx (zeros or the addend) before its one class writes
+  ConvPlan conv;              // conv
+};
+
+// Pure: reads the descriptor, which operands `a` has, asm_tuning and the CU count.  aligned: dy, wt, dx and the addend are
+// 16-byte aligned (dgrad_s2_kernel's vector accesses).
+static DgradPlan plan_dgrad(const asm_conv_desc* d, const IGemmArgs& a, ConvOut out, bool aligned) {
+  DgradPlan p = {};
+  const asm_tuning& tu = asm_tune();
+  const bool k3 = d->R == 3 && d->S == 3, k1 = d->R == 1 && d->S == 1 && d->pad == 0;
+  if (aligned && !a.pool_dy && asm_dgrad_s2_covers(d)) {   // all four parity classes in one launch
+    p.form = DgradForm::s2;
+    return p;
+  }
+  // Stride-2 3x3: three quarters of the (pixel, tap) pairs of the generic gather are parity misses (multiplied as
+  // zeros).  Split dx into its four (h % 2, w % 2) classes instead: within a class every pixel uses the same
+  // 1 / 2 / 2 / 4 taps, so each class is a dense stride-1 gather over dy with a 1x1 / 1x2 / 2x1 / 2x2 sub-filter
+  //   dx(2hh+ph, 2ww+pw) = sum_{i,j} dy(hh + dh0 - i, ww + dw0 - j) . w(r0 + 2i, s0 + 2j),
+  //   r0 = (ph + pad) & 1, dh0 = (ph + pad - r0) / 2   (same for columns)
+  // written through the strided-output epilogue: 9/4 instead of 9 tap passes.  A 1x1 / 2 projection touches only the
+  // (even, even) class.  Taken only if every class has a gather-free kernel; otherwise the whole layer is the generic gather.
+  if (tu.dgrad_parity && d->stride == 2 && (k3 || k1) && tu.igemm_mode == 0) {
+    if (k1 && a.addend_mask) {
+      p.conv = no_plan("conv dgrad_masked: a masked addend is not supported for the 1x1 stride-2 input gradient");
+      return p;
+    }
+    for (int cls = 0; cls < 4; ++cls) {
+      const int ph = cls >> 1, pw = cls & 1;
+      const int Hc = (d->H - ph + 1) / 2, Wc = (d->W - pw + 1) / 2;
+      const int r0 = (ph + d->pad) & 1, s0 = (pw + d->pad) & 1;
+      const int Rc = (d->R - r0 + 1) / 2, Sc = (d->S - s0 + 1) / 2;   // taps r0, r0 + 2, ... (< R)
+      if (Hc <= 0 || Wc <= 0 || Rc <= 0 || Sc <= 0) continue;
+      IGemmArgs& c = p.cls[p.nc];
+      c = a;
+      c.R = Rc; c.S = Sc;
+      c.M = d->N * Hc * Wc;
+      c.Wo = Wc; c.HoWo = Hc * Wc;
+      c.so = 1; c.sd = 1; c.tsign = -1;
+      c.pad = -((ph + d->pad - r0) / 2); c.pad_w = -((pw + d->pad - s0) / 2);
+      c.wt0 = r0 * d->S + s0; c.wtr = 2 * d->S; c.wts = 2;
+      c.y_strided = 1;
+      c.y_base = (ph * d->W + pw) * d->C;
+      c.y_img_pitch = d->H * d->W * d->C; c.y_row_pitch = 2 * d->W * d->C; c.y_pix_pitch = 2 * d->C;
+      p.cp[p.nc] = plan_conv(c, ConvOut::bf16);
+      if (p.cp[p.nc].n > 0 && p.cp[p.nc].l[0].family == FAM_GENERAL) {   // no gather-free kernel for this class
+        p.nc = 0;
+        break;
+      }
+      ++p.nc;
+    }
+    if (p.nc > 0) {
+      p.form = DgradForm::parity;
+      p.fill = k1;
+      return p;
+    }
+  }
+  p.conv = plan_conv(a, out);
+  return p;
+}
 
 extern "C" int asm_conv2d_dgrad(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend,
                                 void* dx, void* stream) {
@@ -1296,15 +1375,31 @@ extern "C" int asm_conv2d_dgrad_bnred(const asm_conv_desc* d, const void* dy, co
   return dgrad_impl(d, dy, wt, addend, addend_mask, dx, stream, nullptr, &r);
 }
 
+extern "C" int asm_conv2d_dgrad_kernel(const asm_conv_desc* d, int variant) {
+  if (int e = dgrad_check(d)) return e;
+  ASM_REQUIRE(!(variant & ~(ASM_DGRAD_MASKED | ASM_DGRAD_POOLED | ASM_DGRAD_BNRED)), "conv dgrad_kernel: bad variant %d", variant);
+  const bool pooled = variant & ASM_DGRAD_POOLED, bnred = variant & ASM_DGRAD_BNRED;
+  if (pooled && (bnred || d->R != 1 || d->S != 1 || d->stride != 1 || d->pad != 0))
+    ASM_FAIL(ASM_ENOTSUP, "conv dgrad_kernel: the pooled input gradient is a 1x1 stride-1 one without the batch-norm sums");
+  if (bnred && !dgrad_bnred_covers(d)) ASM_FAIL(ASM_ENOTSUP, "conv dgrad_kernel: no batch-norm sums for this layer");
+  alignas(16) static const unsigned char operand[16] = {};   // stands in for the tensors: the plan asks only which are there
+  IGemmArgs a = dgrad_args(d);
+  if (variant & ASM_DGRAD_MASKED) {
+    a.addend = operand;
+    a.addend_mask = operand;
+  }
+  if (pooled) a.pool_dy = operand;
+  const DgradPlan p = plan_dgrad(d, a, bnred ? ConvOut::bnred : ConvOut::bf16, true);
+  if (p.form == DgradForm::s2) return FAM_DGRAD_S2;
+  const ConvPlan& last = p.form == DgradForm::parity ? p.cp[p.nc - 1] : p.conv;   // what asm_last_conv_kernel reports
+  if (last.n == 0) ASM_FAIL(ASM_ENOTSUP, "%s", last.why);
+  return last.l[last.n - 1].family;
+}
+
 static int dgrad_impl(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend,
                       const uint8_t* addend_mask, void* dx, void* stream, const PoolAdd* pool, const BnRed* red) {
-  if (int e = check_desc(d)) return e;
+  if (int e = dgrad_check(d)) return e;
   ASM_REQUIRE(dy && wt && dx, "conv dgrad: null pointer");
-  ASM_REQUIRE(d->K % 8 == 0, "conv dgrad: K=%d must be a multiple of 8 (pad dy)", d->K);
-  ASM_REQUIRE(d->x_img_pitch == 0 && d->x_row_pitch == 0 && d->x_pix_pitch == 0 && !d->out_f32,
-              "conv dgrad: custom pitches / f32 output not supported");
-  const int64_t dyelems = (int64_t)d->N * d->Ho * d->Wo * d->K;
-  ASM_REQUIRE(dyelems * 2 < (int64_t)ASM_OOB, "conv dgrad: dy larger than 2 GiB");
   IGemmArgs a = dgrad_args(d);
   a.x = dy; a.w = wt; a.y = dx; a.addend = addend; a.addend_mask = addend_mask;
   if (red) {
@@ -1314,55 +1409,27 @@ static int dgrad_impl(const asm_conv_desc* d, const void* dy, const void* wt, co
     a.pool_dy = pool->dy; a.pool_k = pool->k; a.pool_stride = pool->stride; a.pool_pad = pool->pad;
     a.pool_Hp = pool->Hp; a.pool_Wp = pool->Wp; a.pool_cv = pool->cv; a.pool_H = d->H;
   }
-  // Stride-2 3x3: three quarters of the (pixel, tap) pairs of the generic gather are parity misses (multiplied as
-  // zeros).  Split dx into its four (h % 2, w % 2) classes instead: within a class every pixel uses the same
-  // 1 / 2 / 2 / 4 taps, so each class is a dense stride-1 gather over dy with a 1x1 / 1x2 / 2x1 / 2x2 sub-filter
-  //   dx(2hh+ph, 2ww+pw) = sum_{i,j} dy(hh + dh0 - i, ww + dw0 - j) . w(r0 + 2i, s0 + 2j),
-  //   r0 = (ph + pad) & 1, dh0 = (ph + pad - r0) / 2   (same for columns)
-  // written through the strided-output epilogue: 9/4 instead of 9 tap passes.
-  const int split_ok = asm_tune().dgrad_parity;
-  const bool k3 = d->R == 3 && d->S == 3, k1 = d->R == 1 && d->S == 1 && d->pad == 0;
-  if (k3 && d->stride == 2 && !pool && asm_tune().igemm_mode == 0) {   // all four parity classes in one launch
-    const int rc = asm_dgrad_s2_try(d, dy, wt, addend, addend_mask, dx, stream);
-    if (rc != 1) return rc;
-  }
-  if (split_ok && d->stride == 2 && (k3 || k1) && asm_tune().igemm_mode == 0) {
-    // a 1x1 / 2 projection touches only the (even, even) class: the other three are zero (or just the addend)
-    bool launched = false;
-    for (int cls = 0; cls < 4; ++cls) {
-      const int ph = cls >> 1, pw = cls & 1;
-      const int Hc = (d->H - ph + 1) / 2, Wc = (d->W - pw + 1) / 2;
-      const int r0 = (ph + d->pad) & 1, s0 = (pw + d->pad) & 1;
-      const int Rc = (d->R - r0 + 1) / 2, Sc = (d->S - s0 + 1) / 2;   // taps r0, r0 + 2, ... (< R)
-      if (Hc <= 0 || Wc <= 0 || Rc <= 0 || Sc <= 0) continue;
-      IGemmArgs c = a;
-      c.R = Rc; c.S = Sc;
-      c.M = d->N * Hc * Wc;
-      c.Wo = Wc; c.HoWo = Hc * Wc;
-      c.so = 1; c.sd = 1; c.tsign = -1;
-      c.pad = -((ph + d->pad - r0) / 2); c.pad_w = -((pw + d->pad - s0) / 2);
-      c.wt0 = r0 * d->S + s0; c.wtr = 2 * d->S; c.wts = 2;
-      c.y_strided = 1;
-      c.y_base = (ph * d->W + pw) * d->C;
-      c.y_img_pitch = d->H * d->W * d->C; c.y_row_pitch = 2 * d->W * d->C; c.y_pix_pitch = 2 * d->C;
-      if (!launched && k1 && addend_mask)
-        ASM_FAIL(ASM_ENOTSUP, "conv dgrad_masked: a masked addend is not supported for the 1x1 stride-2 input gradient");
-      const ConvPlan pl = plan_conv(c, ConvOut::bf16);
-      if (pl.n > 0 && pl.l[0].family == FAM_GENERAL) {   // no gather-free kernel for this class: the generic gather below
-        if (launched) ASM_FAIL(ASM_ENOTSUP, "conv dgrad: parity classes launched inconsistently");
-        break;
-      }
-      if (!launched && k1) {   // fill the untouched classes before the one launch that overwrites its own pixels
+  const bool aligned = ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(wt) | reinterpret_cast<uintptr_t>(dx) |
+                         reinterpret_cast<uintptr_t>(addend)) & 15) == 0;
+  const DgradPlan p = plan_dgrad(d, a, red ? ConvOut::bnred : ConvOut::bf16, aligned);
+  const hipStream_t st = (hipStream_t)stream;
+  switch (p.form) {
+    case DgradForm::s2:
+      if (const int rc = asm_dgrad_s2_launch(d, dy, wt, addend, addend_mask, dx, stream)) return rc;
+      asm_last_conv_kernel = FAM_DGRAD_S2;
+      return ASM_OK;
+    case DgradForm::parity:
+      if (p.fill) {   // the classes the one launch does not write are zero, or just the addend
         const size_t bytes = (size_t)a.M * d->C * 2;
-        hipError_t e = (addend && addend != dx) ? asm_fill_async(dx, addend, 0, bytes, (hipStream_t)stream)
+        hipError_t e = (addend && addend != dx) ? asm_fill_async(dx, addend, 0, bytes, st)
                      : addend ? hipSuccess
-                              : asm_fill_async(dx, nullptr, 0, bytes, (hipStream_t)stream);
+                              : asm_fill_async(dx, nullptr, 0, bytes, st);
         if (e != hipSuccess) ASM_FAIL(ASM_EHIP, "conv dgrad: fill: %s", hipGetErrorString(e));
       }
-      if (const int rc = run_plan(pl, c, (hipStream_t)stream)) return rc;
-      launched = true;
-    }
-    if (launched) return ASM_OK;
+      for (int i = 0; i < p.nc; ++i)
+        if (const int rc = run_plan(p.cp[i], p.cls[i], st)) return rc;
+      return ASM_OK;
+    case DgradForm::conv: break;
   }
-  return run_plan(plan_conv(a, red ? ConvOut::bnred : ConvOut::bf16), a, (hipStream_t)stream);
+  return run_plan(p.conv, a, st);
 }

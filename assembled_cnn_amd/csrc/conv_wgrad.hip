@@ -738,6 +738,41 @@ __global__ __launch_bounds__((WHalo<KF, CI, PH, PW>::NTHR)) void wgrad_halo_kern
   }
 }
 
+// ---- the plan: plan_wgrad decides, asm_conv2d_wgrad launches ----
+// the kernel forms: wgrad_halo_kernel; wgrad_kernel with 128-wide column tiles, register-staged or (1x1, LIN) by LDS-DMA into a
+// two-stage ring; wgrad8_kernel, the 256 x 256 tile
+enum class WgradForm { halo, reg, ring, big };
+
+// asm_conv2d_wgrad_plan reports a plan as {bnw, bcw, tiles_n, tiles_c, splits, m_per_split}, the halo form as {K, -1, 1, 1,
+// workgroups per K / KF slice (= slabs), pixels per workgroup}.
+struct WgradPlan {
+  WgradForm form;
+  int kf, ci, pw;                 // halo: output channels per workgroup (64 for K = 128), input channels, patch width (16 / 56 / 28)
+  int bnw, bcw;                   // dy-tile rows, (tap, channel) column-tile width (wgrad_kernel's BNW / BCW; 256 / 256 for big)
+  bool lin;                       // LIN of wgrad_kernel / wgrad8_kernel: 1x1, stride 1, no padding over a densely packed x
+  int tiles_n, tiles_c, splits, m_per_split;   // WgradArgs (halo: K / KF, 1, slabs, 0)
+  unsigned grid, block, lds;
+  int slabs;                      // fp32 [K][R S C] slabs wgrad_reduce_kernel sums into dW; 0: the kernel writes dW itself
+  size_t workspace;               // slabs * |dW| * 4 bytes
+};
+
+// the halo form's instantiation: f(HaloForm<KF, CI, PH, PW>{}) for the plan's channels and patch geometry
+template <int KF, int CI, int PH, int PW>
+struct HaloForm : WHalo<KF, CI, PH, PW> {
+  static constexpr void (*kernel)(WgradArgs) = wgrad_halo_kernel<KF, CI, PH, PW>;
+};
+template <int KF, int CI, class F>
+int on_halo_patch(int pw, F&& f) {
+  if (pw == 16) return f(HaloForm<KF, CI, 8, 16>{});
+  if (pw == 56) return f(HaloForm<KF, CI, 2, 56>{});
+  return f(HaloForm<KF, CI, 4, 28>{});
+}
+template <class F>
+int on_halo(const WgradPlan& p, F&& f) {
+  if (p.kf == 32) return p.ci == 32 ? on_halo_patch<32, 32>(p.pw, f) : on_halo_patch<32, 64>(p.pw, f);
+  return p.ci == 32 ? on_halo_patch<64, 32>(p.pw, f) : on_halo_patch<64, 64>(p.pw, f);
+}
+
 // patch geometry of the halo form for a map: 8 x 16 patches where the map tiles into them, whole-row bands of 112 pixels on the
 // 56- and 28-wide maps; 0 = none
 inline int halo_patch_w(const asm_conv_desc* d) {
@@ -749,13 +784,11 @@ inline int halo_patch_w(const asm_conv_desc* d) {
 
 // patch runs (= slabs) of the persistent halo form for this layer, or 0 if it does not apply; the launch has K / KF workgroups
 // per run (KF = 64 for K = 128)
-int wgrad_halo_blocks(const asm_conv_desc* d) {
+int wgrad_halo_blocks(const asm_conv_desc* d, int pw) {
   const int mode = asm_tune().wgrad_halo;     // 0 off, 1 on for the large maps, 2 whenever the shape allows (tests)
-  if (!mode) return 0;
+  if (!mode || !pw) return 0;
   if (d->R != 3 || d->S != 3 || d->stride != 1 || d->pad != 1 || d->Ho != d->H || d->Wo != d->W) return 0;
   if (d->x_img_pitch || d->x_row_pitch || d->x_pix_pitch) return 0;
-  const int pw = halo_patch_w(d);
-  if (!pw) return 0;
   if (!((d->C == 32 || d->C == 64) && (d->K == 32 || d->K == 64 || d->K == 128))) return 0;
   const int ppx = pw == 16 ? 128 : 112;
   const int n_m = d->N * d->H * d->W / ppx;
@@ -765,16 +798,48 @@ int wgrad_halo_blocks(const asm_conv_desc* d) {
   return n_m < wgs / kh ? n_m : wgs / kh;
 }
 
-struct Plan {
-  int bnw, bcw, tiles_n, tiles_c, splits, m_per_split;
-};
+// LDS-DMA ring for a linear-address 1x1 layer with 128-column tiles?  (asm_tuning.wgrad_ring: 0 never, n >= 1 always, -1 per
+// layer from the same-box sweep, tools/gemm1_sweep.py --wgrad)
+bool wgrad_ring(const asm_conv_desc* d) {
+  const int mode = asm_tune().wgrad_ring;
+  if (mode == 0) return false;
+  if (mode > 0) return true;
+  // Round-5 sweep (tools/gemm1_sweep.py --wgrad, every 1x1 shape of Assemble-ResNet-50 at batch 256, bit-identical sums): two
+  // stages (64 KB, two workgroups per CU like the register-staged loop) win 3 - 10 % on the 28 x 28 and smaller maps and on
+  // the 56 x 56 layers with >= 128 input channels, and lose 20 - 30 % on the narrow 56 x 56 ones (x rows of 64 / 128 bytes:
+  // a quarter / half of every 256-byte DMA row is padding).  Deeper rings (three / four stages, one workgroup per CU) lost
+  // everywhere and were removed in round 6 (see the note in wgrad_kernel: hipcc drains the ring before every fragment read).
+  return !((long long)d->N * d->H * d->W >= 500000 && d->C <= 64);
+}
 
-Plan make_plan(const asm_conv_desc* d) {
-  Plan pl;
-  const int M = d->N * d->Ho * d->Wo;
+// The weight-gradient launch of a layer: form, template arguments, grid, splits and slabs.  Pure: reads the descriptor and
+// asm_tuning only.
+WgradPlan plan_wgrad(const asm_conv_desc* d) {
+  WgradPlan p = {};
   const int cols = d->R * d->S * d->C;
-  pl.bnw = (d->K <= 32 && WPX == 64) ? 32 : (d->K <= 64 ? 64 : 128);
-  pl.bcw = 128;
+  const int pw = halo_patch_w(d);
+  if (const int hb = wgrad_halo_blocks(d, pw)) {
+    p.form = WgradForm::halo;
+    p.kf = d->K == 128 ? 64 : d->K;
+    p.ci = d->C;
+    p.pw = pw;
+    p.tiles_n = d->K / p.kf; p.tiles_c = 1; p.splits = hb; p.m_per_split = 0;
+    p.grid = hb * p.tiles_n;
+    on_halo(p, [&](auto h) {
+      p.block = h.NTHR;
+      p.lds = h.LDS;
+      return 0;
+    });
+    p.slabs = hb;
+    p.workspace = (size_t)hb * d->K * cols * sizeof(float);
+    return p;
+  }
+  const int M = d->N * d->Ho * d->Wo;
+  p.lin = d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0 && d->Ho == d->H && d->Wo == d->W &&
+          (d->x_pix_pitch == 0 || d->x_pix_pitch == d->C) && (d->x_row_pitch == 0 || d->x_row_pitch == d->W * d->C) &&
+          (d->x_img_pitch == 0 || d->x_img_pitch == (int64_t)d->H * d->W * d->C);
+  p.bnw = d->K <= 32 ? 32 : (d->K <= 64 ? 64 : 128);
+  p.bcw = 128;
   // 256 x 256 / 8 waves (wgrad8_kernel) when dW tiles exactly (no padded MFMAs) and there is enough of it; ASM_WGRAD_BIG=0/1
   // forces.  Round-6 same-box sweep of wgrad8 against the 128-wide kernels at batch 256 (tools/conv_bench.py --kinds wgrad,
   // ASM_WGRAD_BIG=1 against the default): 3x3 layers win from 30 GFLOP up (7x7x256->512 69 -> 61 us, 14x14x128->256 60 -> 56 us;
@@ -788,10 +853,11 @@ Plan make_plan(const asm_conv_desc* d) {
              (taps ? (cols >= 512 && gflop >= 25.0) : (cols >= 256 && gflop >= 40.0));
   if (big_env == 0) big = false;
   if (big_env == 1 && d->K >= 256 && cols >= 256) big = true;
-  if (big) pl.bnw = pl.bcw = 256;
-  pl.tiles_n = cdiv(d->K, pl.bnw);
-  pl.tiles_c = cdiv(cols, pl.bcw);
-  const int tiles = pl.tiles_n * pl.tiles_c;
+  if (big) p.bnw = p.bcw = 256;
+  p.form = big ? WgradForm::big : (p.lin && wgrad_ring(d)) ? WgradForm::ring : WgradForm::reg;
+  p.tiles_n = cdiv(d->K, p.bnw);
+  p.tiles_c = cdiv(cols, p.bcw);
+  const int tiles = p.tiles_n * p.tiles_c;
   const int msteps = cdiv(M, WPX);
   // Split count from a small cost model (microseconds): the MFMA/stream time scales with how evenly
   // tiles*splits blocks fill the resident slots (256 CUs x 1..4 workgroups), the slab path costs
@@ -806,9 +872,8 @@ Plan make_plan(const asm_conv_desc* d) {
   const size_t wbytes = (size_t)d->K * cols * sizeof(float);
   const double flops = 2.0 * (double)M * d->K * cols;
   const double io_bytes = 2.0 * ((double)M * d->C + (double)M * d->K);
-  const bool big8 = pl.bnw == 256;
-  const double work_us = fmax(flops / (big8 ? 9.0e8 : 6.0e8), io_bytes / 4.0e6);      // ~900 / ~600 TFLOP/s or ~4 TB/s
-  const int slots = 256 * (pl.bnw == 256 ? 1 : (pl.bnw == 128 ? 2 : (pl.bnw == 64 ? 3 : 4))) * (64 / WPX);
+  const double work_us = fmax(flops / (big ? 9.0e8 : 6.0e8), io_bytes / 4.0e6);      // ~900 / ~600 TFLOP/s or ~4 TB/s
+  const int slots = 256 * (p.bnw == 256 ? 1 : (p.bnw == 128 ? 2 : (p.bnw == 64 ? 3 : 4))) * (64 / WPX);
   const int max_splits = msteps / 4 > 0 ? msteps / 4 : 1;            // at least 4 steps per block
   int splits = 1;
   double best = 1e30;
@@ -819,10 +884,10 @@ Plan make_plan(const asm_conv_desc* d) {
     const double rounds = ceil(blocks / slots);
     const double fill = rounds / (blocks / slots);                    // >= 1: quantisation of the last round
     const double under = blocks >= slots ? 1.0                        // too few blocks: less overlap
-                         : (big8 ? 1.0 + 0.35 * ((double)slots / blocks - 1.0) : (double)slots / blocks * 0.5 + 0.5);
+                         : (big ? 1.0 + 0.35 * ((double)slots / blocks - 1.0) : (double)slots / blocks * 0.5 + 0.5);
     const double straddle = (tiles > 1 && sp > 8 && sp % 8 != 0) ? 1.08 : 1.0;
     const double slab = sp > 1 ? ((double)(sp + 1) * wbytes / 4.0e6 + 4.0) : 0.0;
-    const double est = work_us * (blocks < slots ? under : fill) * straddle + slab + (big8 ? 12.0 * rounds : 0.0);
+    const double est = work_us * (blocks < slots ? under : fill) * straddle + slab + (big ? 12.0 * rounds : 0.0);
     if (est < best) {
       best = est;
       splits = sp;
@@ -831,48 +896,51 @@ Plan make_plan(const asm_conv_desc* d) {
   // ASM_WGRAD_SPLITS=n forces the pixel split (tests: slab path on small shapes; tuning)
   const int forced = asm_tune().wgrad_splits;
   if (forced > 0) splits = forced < msteps ? forced : msteps;
-  int steps_per = cdiv(msteps, splits);
-  pl.m_per_split = steps_per * WPX;
-  pl.splits = cdiv(M, pl.m_per_split);
-  return pl;
+  const int steps_per = cdiv(msteps, splits);
+  p.m_per_split = steps_per * WPX;
+  p.splits = cdiv(M, p.m_per_split);
+  p.grid = p.tiles_n * p.tiles_c * p.splits;
+  p.block = big ? 512 : 256;
+  p.lds = big ? 2 * 8 * 16 * 512                       // 128 KiB: two rings of eight 16-pixel blocks
+              : 2 * (WPX * p.bnw * 2 + WPX * 256);     // two stages of a dy and an x tile (registers or LDS-DMA)
+  p.slabs = p.splits > 1 ? p.splits : 0;
+  p.workspace = (size_t)p.slabs * d->K * cols * sizeof(float);
+  return p;
 }
 
-// ring depth of the LDS-DMA form for a linear-address 1x1 layer with 128-column tiles (asm_tuning.wgrad_ring: 0 never,
-// n >= 1 the two-stage ring forced, -1 per layer from the same-box sweep, tools/gemm1_sweep.py --wgrad), or 0 for the register-staged loop
-int wgrad_ring_depth(const asm_conv_desc* d, const Plan& pl) {
-  const int mode = asm_tune().wgrad_ring;
-  if (mode == 0 || WPX != 64) return 0;
-  if (mode > 0) return 2;
-  // Round-5 sweep (tools/gemm1_sweep.py --wgrad, every 1x1 shape of Assemble-ResNet-50 at batch 256, bit-identical sums): two
-  // stages (64 KB, two workgroups per CU like the register-staged loop) win 3 - 10 % on the 28 x 28 and smaller maps and on
-  // the 56 x 56 layers with >= 128 input channels, and lose 20 - 30 % on the narrow 56 x 56 ones (x rows of 64 / 128 bytes:
-  // a quarter / half of every 256-byte DMA row is padding).  Deeper rings (three / four stages, one workgroup per CU) lost
-  // everywhere and were removed in round 6 (see the note in wgrad_kernel: hipcc drains the ring before every fragment read).
-  (void)pl;
-  if ((long long)d->N * d->H * d->W >= 500000 && d->C <= 64) return 0;
-  return 2;
+// one launch of the plan on kernel KERN, with the dynamic-LDS opt-in it needs above 64 KiB
+template <auto KERN>
+int launch_wg(const WgradPlan& pl, const WgradArgs& a, hipStream_t st) {
+  static bool done[ASM_MAX_DEVICES] = {};
+  if (hipError_t e = asm_ensure_dyn_lds(KERN, (int)pl.lds, done); e != hipSuccess)
+    ASM_FAIL(ASM_EHIP, "conv wgrad: dynamic LDS opt-in: %s", hipGetErrorString(e));
+  ASM_LAUNCH(KERN, dim3(pl.grid), dim3(pl.block), pl.lds, st, a);
+  return ASM_OK;
+}
+
+// wgrad_kernel with 128-wide column tiles on the plan's dy-tile rows
+template <bool LIN, int NS>
+int launch_128(const WgradPlan& pl, const WgradArgs& a, hipStream_t st) {
+  if (pl.bnw == 128) return launch_wg<wgrad_kernel<128, 128, LIN, NS>>(pl, a, st);
+  if (pl.bnw == 64) return launch_wg<wgrad_kernel<64, 128, LIN, NS>>(pl, a, st);
+  return launch_wg<wgrad_kernel<32, 128, LIN, NS>>(pl, a, st);
 }
 
 }  // namespace
 
 extern "C" size_t asm_conv2d_wgrad_workspace_bytes(const asm_conv_desc* d) {
-  if (!d) return 0;
-  if (const int hb = wgrad_halo_blocks(d)) return (size_t)hb * d->K * 9 * d->C * sizeof(float);
-  Plan pl = make_plan(d);
-  if (pl.splits <= 1) return 0;
-  return (size_t)pl.splits * d->K * d->R * d->S * d->C * sizeof(float);
+  return d ? plan_wgrad(d).workspace : 0;
 }
 
 extern "C" int asm_conv2d_wgrad_plan(const asm_conv_desc* d, int32_t plan[6]) {
   ASM_REQUIRE(d && plan, "conv wgrad plan: null pointer");
-  if (const int hb = wgrad_halo_blocks(d)) {      // persistent halo form: {K, -1, 1, 1, workgroups, pixels per workgroup}
-    plan[0] = d->K; plan[1] = -1; plan[2] = 1; plan[3] = 1; plan[4] = hb;
-    plan[5] = (d->N * d->H * d->W + hb - 1) / hb;
+  const WgradPlan p = plan_wgrad(d);
+  if (p.form == WgradForm::halo) {
+    plan[0] = d->K; plan[1] = -1; plan[2] = 1; plan[3] = 1; plan[4] = p.splits;
+    plan[5] = (d->N * d->H * d->W + p.splits - 1) / p.splits;
     return ASM_OK;
   }
-  const Plan pl = make_plan(d);
-  plan[0] = pl.bnw; plan[1] = pl.bcw; plan[2] = pl.tiles_n; plan[3] = pl.tiles_c; plan[4] = pl.splits;
-  plan[5] = pl.m_per_split;
+  plan[0] = p.bnw; plan[1] = p.bcw; plan[2] = p.tiles_n; plan[3] = p.tiles_c; plan[4] = p.splits; plan[5] = p.m_per_split;
   return ASM_OK;
 }
 
@@ -887,52 +955,12 @@ extern "C" int asm_conv2d_wgrad(const asm_conv_desc* d, const void* x, const voi
   const int64_t xelems = (int64_t)d->N * img_p;
   const int64_t dyelems = (int64_t)d->N * d->Ho * d->Wo * ldy;
   ASM_REQUIRE(xelems * 2 < (int64_t)ASM_OOB && dyelems * 2 < (int64_t)ASM_OOB, "conv wgrad: tensor larger than 2 GiB");
-  Plan pl = make_plan(d);
-  const size_t need = asm_conv2d_wgrad_workspace_bytes(d);
-  ASM_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "conv wgrad: workspace too small (%zu < %zu)",
-              workspace_bytes, need);
-  if (const int hb = wgrad_halo_blocks(d)) {
-    WgradArgs h;
-    const int kf = d->K == 128 ? 64 : d->K, kh = d->K / kf, pw = halo_patch_w(d);
-    h.dy = dy; h.x = x; h.out = reinterpret_cast<float*>(workspace);
-    h.dy_bytes = (unsigned)(dyelems * 2); h.x_bytes = (unsigned)(xelems * 2);
-    h.M = d->N * d->H * d->W; h.Hi = d->H; h.Wi = d->W; h.Ci = d->C; h.Co = d->K; h.ldy = ldy;
-    h.R = 3; h.S = 3; h.so = 1; h.pad = 1;
-    h.x_img_pitch = d->H * d->W * d->C; h.x_row_pitch = d->W * d->C; h.x_pix_pitch = d->C;
-    h.cols = 9 * d->C; h.tiles_n = kh; h.tiles_c = 1; h.splits = hb; h.m_per_split = 0;
-    h.HoWo = d->H * d->W; h.Wo = d->W;
-    h.fd_howo = make_fastdiv((unsigned)h.HoWo); h.fd_wo = make_fastdiv((unsigned)h.Wo);
-    hipStream_t hs = (hipStream_t)stream;
-#define LAUNCH_WH(KF, CI, PH, PW)                                                                                      \
-    do {                                                                                                               \
-      constexpr int LDS_ = WHalo<KF, CI, PH, PW>::LDS;                                                                 \
-      static bool done_[ASM_MAX_DEVICES] = {};                                                                         \
-      if (hipError_t e = asm_ensure_dyn_lds(wgrad_halo_kernel<KF, CI, PH, PW>, LDS_, done_); e != hipSuccess)          \
-        ASM_FAIL(ASM_EHIP, "wgrad_halo_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));                         \
-      ASM_LAUNCH((wgrad_halo_kernel<KF, CI, PH, PW>), dim3(hb * kh), dim3(WHalo<KF, CI, PH, PW>::NTHR), LDS_, hs, h);                          \
-    } while (0)
-#define LAUNCH_WH_GEO(KF, CI)                                  \
-    do {                                                       \
-      if (pw == 16) LAUNCH_WH(KF, CI, 8, 16);                  \
-      else if (pw == 56) LAUNCH_WH(KF, CI, 2, 56);             \
-      else LAUNCH_WH(KF, CI, 4, 28);                           \
-    } while (0)
-    if (kf == 32 && d->C == 64) LAUNCH_WH_GEO(32, 64);
-    else if (kf == 64 && d->C == 32) LAUNCH_WH_GEO(64, 32);
-    else if (kf == 32 && d->C == 32) LAUNCH_WH_GEO(32, 32);
-    else LAUNCH_WH_GEO(64, 64);
-#undef LAUNCH_WH_GEO
-#undef LAUNCH_WH
-    ASM_CHECK_LAUNCH("wgrad_halo_kernel");
-    const size_t n = (size_t)d->K * 9 * d->C;
-    ASM_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)cdivz(n, 128)), dim3(256), 0, hs,
-                       reinterpret_cast<const float*>(workspace), dw, n, hb);
-    ASM_CHECK_LAUNCH("wgrad_reduce_kernel");
-    return ASM_OK;
-  }
+  const WgradPlan pl = plan_wgrad(d);
+  ASM_REQUIRE(pl.workspace == 0 || (workspace && workspace_bytes >= pl.workspace), "conv wgrad: workspace too small (%zu < %zu)",
+              workspace_bytes, pl.workspace);
   WgradArgs a;
   a.dy = dy; a.x = x;
-  a.out = pl.splits > 1 ? reinterpret_cast<float*>(workspace) : dw;
+  a.out = pl.slabs ? reinterpret_cast<float*>(workspace) : dw;
   a.dy_bytes = (unsigned)(dyelems * 2);
   a.x_bytes = (unsigned)(xelems * 2);
   a.M = d->N * d->Ho * d->Wo;
@@ -948,57 +976,19 @@ extern "C" int asm_conv2d_wgrad(const asm_conv_desc* d, const void* x, const voi
   a.fd_howo = make_fastdiv((unsigned)a.HoWo);
   a.fd_wo = make_fastdiv((unsigned)a.Wo);
   hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(pl.tiles_n * pl.tiles_c * pl.splits);
-  const bool lin = d->R == 1 && d->S == 1 && d->stride == 1 && d->pad == 0 && d->Ho == d->H && d->Wo == d->W &&
-                   a.x_pix_pitch == d->C && a.x_row_pitch == d->W * d->C && a.x_img_pitch == d->H * d->W * d->C;
-  const int ring = lin && pl.bcw != 256 ? wgrad_ring_depth(d, pl) : 0;
-  if (ring >= 2) {
-#define LAUNCH_RING(BNW_, NS_)                                                                                         \
-    do {                                                                                                               \
-      constexpr int LDS_ = NS_ * (WPX * BNW_ * 2 + WPX * 256);                                                         \
-      static bool done_[ASM_MAX_DEVICES] = {};                                                                         \
-      if (hipError_t e = asm_ensure_dyn_lds(wgrad_kernel<BNW_, 128, true, NS_>, LDS_, done_); e != hipSuccess)         \
-        ASM_FAIL(ASM_EHIP, "wgrad_kernel (ring): dynamic LDS opt-in: %s", hipGetErrorString(e));                       \
-      ASM_LAUNCH((wgrad_kernel<BNW_, 128, true, NS_>), grid, dim3(256), LDS_, st, a);                                  \
-    } while (0)
-#define LAUNCH_RING_NS(NS_)                                      \
-    do {                                                         \
-      if (pl.bnw == 128) LAUNCH_RING(128, NS_);                  \
-      else if (pl.bnw == 64) LAUNCH_RING(64, NS_);               \
-      else LAUNCH_RING(32, NS_);                                 \
-    } while (0)
-    LAUNCH_RING_NS(2);
-#undef LAUNCH_RING_NS
-#undef LAUNCH_RING
-  } else if (lin && pl.bcw != 256) {
-    if (pl.bnw == 128) ASM_LAUNCH((wgrad_kernel<128, 128, true>), grid, dim3(256), 2 * (WPX * 256 + WPX * 256), st, a);
-    else if (pl.bnw == 64) ASM_LAUNCH((wgrad_kernel<64, 128, true>), grid, dim3(256), 2 * (WPX * 128 + WPX * 256), st, a);
-    else ASM_LAUNCH((wgrad_kernel<32, 128, true>), grid, dim3(256), 2 * (WPX * 64 + WPX * 256), st, a);
-  } else if (pl.bcw == 256) {
-    constexpr int LDS = 2 * 8 * 16 * 512;              // 128 KiB: two rings of eight 16-pixel blocks
-    if (lin) {
-      static bool attr_done_l[ASM_MAX_DEVICES] = {};
-      if (hipError_t e = asm_ensure_dyn_lds(wgrad8_kernel<true>, LDS, attr_done_l); e != hipSuccess)
-        ASM_FAIL(ASM_EHIP, "wgrad8_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-      ASM_LAUNCH((wgrad8_kernel<true>), grid, dim3(512), LDS, st, a);
-    } else {
-      static bool attr_done[ASM_MAX_DEVICES] = {};
-      if (hipError_t e = asm_ensure_dyn_lds(wgrad8_kernel<false>, LDS, attr_done); e != hipSuccess)
-        ASM_FAIL(ASM_EHIP, "wgrad8_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-      ASM_LAUNCH((wgrad8_kernel<false>), grid, dim3(512), LDS, st, a);
-    }
-  } else if (pl.bnw == 128) {
-    ASM_LAUNCH((wgrad_kernel<128, 128>), grid, dim3(256), 2 * (WPX * 256 + WPX * 256), st, a);
-  } else if (pl.bnw == 64) {
-    ASM_LAUNCH((wgrad_kernel<64, 128>), grid, dim3(256), 2 * (WPX * 128 + WPX * 256), st, a);
-  } else {
-    ASM_LAUNCH((wgrad_kernel<32, 128>), grid, dim3(256), 2 * (WPX * 64 + WPX * 256), st, a);
+  int rc = ASM_OK;
+  switch (pl.form) {
+    case WgradForm::halo: rc = on_halo(pl, [&](auto h) { return launch_wg<decltype(h)::kernel>(pl, a, st); }); break;
+    case WgradForm::reg: rc = pl.lin ? launch_128<true, 0>(pl, a, st) : launch_128<false, 0>(pl, a, st); break;
+    case WgradForm::ring: rc = launch_128<true, 2>(pl, a, st); break;
+    case WgradForm::big: rc = pl.lin ? launch_wg<wgrad8_kernel<true>>(pl, a, st) : launch_wg<wgrad8_kernel<false>>(pl, a, st); break;
   }
-  ASM_CHECK_LAUNCH("wgrad_kernel");
-  if (pl.splits > 1) {
+  if (rc != ASM_OK) return rc;
+  ASM_CHECK_LAUNCH(pl.form == WgradForm::halo ? "wgrad_halo_kernel" : pl.form == WgradForm::big ? "wgrad8_kernel" : "wgrad_kernel");
+  if (pl.slabs) {
     const size_t n = (size_t)d->K * a.cols;
     ASM_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)cdivz(n, 128)), dim3(256), 0, st,
-                       reinterpret_cast<const float*>(workspace), dw, n, pl.splits);
+               reinterpret_cast<const float*>(workspace), dw, n, pl.slabs);
     ASM_CHECK_LAUNCH("wgrad_reduce_kernel");
   }
   return ASM_OK;

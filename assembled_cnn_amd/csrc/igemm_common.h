@@ -51,7 +51,7 @@ constexpr int STATS_BM = 128;  // rows per statistics partial (asm_conv2d_stats_
 
 // ---- the kernel a forward / input-gradient launch runs: plan_conv (conv_igemm.hip) decides, run_plan launches ----
 // kernel families, numbered as asm_debug_last_conv_kernel reports them
-enum ConvFamily { FAM_GENERAL = 0, FAM_GEMM1 = 1, FAM_IGEMM2 = 2, FAM_IGEMM3 = 3, FAM_HALO = 4, FAM_IGEMM8 = 8 };
+enum ConvFamily { FAM_GENERAL = 0, FAM_GEMM1 = 1, FAM_IGEMM2 = 2, FAM_IGEMM3 = 3, FAM_HALO = 4, FAM_DGRAD_S2 = 5, FAM_IGEMM8 = 8 };
 // epilogue variant (igemm_epilogue's template flags): plain, addend-prefetching (PFA), pooled-gradient gather, statistics,
 // batch-norm backward sums (BNRED), f32 output
 enum ConvEpi { EPI_PLAIN, EPI_PFA, EPI_POOL, EPI_STATS, EPI_BNRED, EPI_F32 };

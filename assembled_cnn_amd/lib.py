@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ASM_HIP_LIB') or os.path.join(HERE, 'libasm_hip.so')
 
 ASM_OK, ASM_EINVAL, ASM_ENOTSUP, ASM_EHIP = 0, -1, -2, -3
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class AsmError(RuntimeError):
@@ -88,6 +88,8 @@ def apply_env_tuning(lib) -> 'Tuning':
 
 
 ASM_F32, ASM_BF16, ASM_F16 = 0, 1, 2
+ASM_DGRAD_MASKED, ASM_DGRAD_POOLED, ASM_DGRAD_BNRED = 1, 2, 4     # asm_conv2d_dgrad_kernel variants
+CONV_DGRAD_S2 = 5       # asm_conv2d_dgrad_kernel's number of the one-launch 3x3 / stride-2 input gradient
 ASM_AA_SCONV, ASM_AA_PROJ = 1, 2
 POOL_TYPES = {'gap': 0, 'gem': 1, 'flatten': 2}
 (PLAN_CONV, PLAN_BN, PLAN_DENSE, PLAN_MAXPOOL, PLAN_AVGPOOL, PLAN_BLURPOOL, PLAN_GAP, PLAN_GEM, PLAN_FLATTEN, PLAN_SK_GAP,
@@ -120,6 +122,7 @@ SIGNATURES = {
     'asm_conv2d_dgrad_pooled': (_I, [_D, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     'asm_conv2d_dgrad_bnred_blocks': (_I, [_D]),
     'asm_conv2d_dgrad_bnred': (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'asm_conv2d_dgrad_kernel': (_I, [_D, _I]),
     'asm_conv2d_wgrad_workspace_bytes': (_Z, [_D]),
     'asm_conv2d_wgrad': (_I, [_D, _P, _P, _P, _P, _Z, _P]),
     'asm_filter_transpose': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),

@@ -285,35 +285,39 @@ def conv_fprop_bn(d: ConvDesc, x: torch.Tensor, w: torch.Tensor, scale, shift, r
   return y
 
 
+def dgrad_kernel(d: ConvDesc, variant: int = 0) -> int:
+  """the kernel family an input gradient of ``d`` would run (asm_conv2d_dgrad_kernel; variant: lib.ASM_DGRAD_* flags), or
+  ASM_ENOTSUP (negative) where that entry point does not cover the layer.  A C-ABI provider without the query (a CPU test double
+  written against ABI 5; the library itself refuses to load at another version) covers no fused route as far as the host knows:
+  the plain input gradient is always right."""
+  query = getattr(L(), 'asm_conv2d_dgrad_kernel', None)
+  if query is None:
+    return _lib.ASM_ENOTSUP
+  return query(C.byref(d), variant)
+
+
 def dgrad_pool_ok(d: ConvDesc) -> bool:
-  """can asm_conv2d_dgrad_pooled take this layer (1x1, stride 1, on the igemm2 path)?  ASM_POOL_FUSE=0: never"""
-  return (knob('ASM_POOL_FUSE', '1') != '0' and d.R == 1 and d.S == 1 and d.stride == 1 and d.pad == 0
-          and d.C % 8 == 0 and d.K % 32 == 0 and not _is_dense(d) and knob('ASM_IGEMM_MODE', '0') in ('', '0'))
+  """can asm_conv2d_dgrad_pooled take this layer?  ASM_POOL_FUSE=0: never"""
+  # K % 32: the library also covers narrower reductions (K <= the tile's 32 / 64 channels), which have never been fused --
+  # the host keeps the rule that held when the pooled epilogue was introduced
+  return (knob('ASM_POOL_FUSE', '1') != '0' and not _is_dense(d) and d.K % 32 == 0
+          and dgrad_kernel(d, _lib.ASM_DGRAD_POOLED) >= 0)
 
 
 def dgrad_s2_ok(d: ConvDesc) -> bool:
   """does the one-launch 3x3 / stride-2 input gradient (csrc/conv_dgrad_s2.hip) take this layer?  It adds a MASKED fan-in
-  addend in its copy-out, so the caller need not materialise the masked gradient first.  ASM_DGRAD_PARITY < 2: never"""
-  if not _IS_DOUBLE:        # the library decides from asm_tuning (asm_dgrad_s2_try): ask it, not only the environment
-    t = _lib.Tuning()
-    L().asm_get_tuning(C.byref(t))
-    if t.dgrad_parity < 2 or t.igemm_mode:
-      return False
-  return (knob('ASM_DGRAD_PARITY', '2') == '2' and knob('ASM_IGEMM_MODE', '0') in ('', '0') and d.R == 3 and d.S == 3
-          and d.stride == 2 and d.pad == 1 and d.C == 64 and d.K == 64 and d.H == 2 * d.Ho and d.W == 2 * d.Wo
-          and d.Ho % 8 == 0 and d.Wo % 8 == 0)
+  addend in its copy-out, so the caller need not materialise the masked gradient first."""
+  return dgrad_kernel(d) == _lib.CONV_DGRAD_S2
 
 
 def dgrad_bnred_ok(d: ConvDesc) -> bool:
   """should this layer's input gradient reduce the batch-norm backward sums of its input (asm_conv2d_dgrad_bnred)?  Whatever the
-  library covers (asm_conv2d_dgrad_bnred_blocks > 0): the 1x1 stride-1 layers and the 3x3 stride-1 layers of its igemm8 / igemm3
-  kernels.  ASM_BN_RED=0: never; ASM_BN_RED=1x1: the 1x1 layers only (round 6 A/B)"""
+  library covers: the 1x1 stride-1 layers and the 3x3 stride-1 layers of its igemm8 / igemm3 kernels.  ASM_BN_RED=0: never;
+  ASM_BN_RED=1x1: the 1x1 layers only (round 6 A/B)"""
   mode = knob('ASM_BN_RED', '1')
-  if mode == '0' or _is_dense(d) or d.stride != 1 or d.C % 8:
+  if mode == '0' or _is_dense(d) or (mode == '1x1' and d.R != 1):
     return False
-  if mode == '1x1' and d.R != 1:
-    return False
-  return L().asm_conv2d_dgrad_bnred_blocks(C.byref(d)) > 0
+  return dgrad_kernel(d, _lib.ASM_DGRAD_BNRED) >= 0
 
 
 def conv_dgrad_bnred(d: ConvDesc, dy: torch.Tensor, wt: torch.Tensor, addend, addend_mask, bn_y: torch.Tensor, bn_mask):

@@ -35,7 +35,7 @@ extern "C" {
 #define ASM_ENOTSUP (-2)
 #define ASM_EHIP (-3)
 
-#define ASM_ABI_VERSION 5
+#define ASM_ABI_VERSION 6
 
 const char* asm_last_error(void);
 int asm_abi_version(void);
@@ -199,6 +199,16 @@ int asm_conv2d_dgrad_bnred_blocks(const asm_conv_desc* d);
 int asm_conv2d_dgrad_bnred(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend,
                            const uint8_t* addend_mask, const void* bn_y, const uint8_t* bn_relu_mask, float* partial,
                            void* dx, void* stream);
+
+/* Which kernel family an input gradient of d would run, from the plan and without launching: 0 the general igemm_kernel,
+ * 1 igemm1, 2 igemm2, 3 igemm3, 4 conv_halo, 5 dgrad_s2_kernel (the one-launch 3x3 / stride-2 form), 8 igemm8 -- for the parity
+ * classes of a stride-2 layer the family of the last class, i.e. what asm_debug_last_conv_kernel reports after the call.  variant: ASM_DGRAD_MASKED (asm_conv2d_dgrad_masked),
+ * ASM_DGRAD_POOLED (asm_conv2d_dgrad_pooled), ASM_DGRAD_BNRED (asm_conv2d_dgrad_bnred, optionally with MASKED), 0
+ * (asm_conv2d_dgrad).  Operands are taken to be 16-byte aligned.  ASM_ENOTSUP: that entry point does not cover the layer. */
+#define ASM_DGRAD_MASKED 1
+#define ASM_DGRAD_POOLED 2
+#define ASM_DGRAD_BNRED 4
+int asm_conv2d_dgrad_kernel(const asm_conv_desc* d, int variant);
 
 /* dw[k][r][s][c] (float32) = sum_{n,ho,wo} dy(n,ho,wo,k) * x(n, ho*stride+r-pad, wo*stride+s-pad, c).
  * Split-K over output pixels; `workspace` holds the per-split slabs. */

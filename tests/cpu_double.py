@@ -12,6 +12,7 @@ and rounding to bf16 exactly where the kernels store bf16.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -237,6 +238,25 @@ class CpuDouble(object):
     if d.C in (32, 64) and d.K in (32, 64) and d.H % 8 == 0 and d.W % 16 == 0:      # conv_halo_kernel: not there
       return False
     return d.K % 64 == 0 and d.C > 64
+
+  def asm_conv2d_dgrad_kernel(self, d, variant):
+    """the family the GPU plan would give, as far as a host test needs it (the double reads the two tuning variables itself):
+    -2 (ASM_ENOTSUP) where the entry point refuses, 5 for the one-launch 3x3 / stride-2 form, else igemm2 (2) or, with
+    ASM_IGEMM_MODE=1, the general kernel (0)"""
+    d = _desc(d)
+    mode = os.environ.get('ASM_IGEMM_MODE') or '0'
+    parity = os.environ.get('ASM_DGRAD_PARITY') or '2'
+    k1 = d.R == 1 and d.S == 1 and d.pad == 0
+    if variant & 2:       # pooled: the 1x1 stride-1 igemm2 path
+      return 2 if k1 and d.stride == 1 and d.C % 8 == 0 and mode == '0' and not variant & 4 else -2
+    if variant & 4:       # batch-norm sums
+      return 2 if self._bnred_covers(d) else -2
+    if variant & 1 and k1 and d.stride == 2 and parity != '0' and mode == '0':
+      return -2
+    if (parity == '2' and mode == '0' and d.R == 3 and d.S == 3 and d.stride == 2 and d.pad == 1 and d.C == 64 and d.K == 64
+        and d.H == 2 * d.Ho and d.W == 2 * d.Wo and d.Ho % 8 == 0 and d.Wo % 8 == 0):
+      return 5
+    return 2 if mode == '0' else 0
 
   def asm_conv2d_dgrad_bnred_blocks(self, d):
     d = _desc(d)

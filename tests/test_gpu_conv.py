@@ -772,3 +772,72 @@ def test_dgrad_bnred_refuses_what_it_does_not_cover(hip_lib):
     assert hip_lib.asm_conv2d_dgrad_bnred(C.byref(d), 1, 1, None, None, 1, None, 1, 1, None) == -2    # ASM_ENOTSUP before any pointer is touched
     assert not ops.dgrad_bnred_ok(d)
   assert ops.dgrad_bnred_ok(ops.make_conv_desc(2, 14, 14, 128, 256, 3, 3, 1))
+
+
+@pytest.mark.parametrize('workload', ['assemble-r50', 'r50'])
+def test_dgrad_kernel_query_is_what_the_input_gradient_runs(hip_lib, workload):
+  """asm_conv2d_dgrad_kernel answers from the plan, without launching: for every convolution of the workload (batch 2) and
+  every input-gradient entry point, the family it reports is the one asm_debug_last_conv_kernel reports after the call, and
+  ASM_ENOTSUP means that entry point refuses the layer."""
+  import os
+  import sys
+  from assembled_cnn_amd import lib, ops
+  sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tools'))
+  import list_convs
+  st = torch.cuda.current_stream().cuda_stream
+  seen = set()
+  for key in list_convs.conv_shapes(workload, 2).keys():
+    N, H, W, Cn, K, R, S, stride, stem = key
+    if stem or K % 8:
+      continue
+    d = ops.make_conv_desc(N, H, W, Cn, K, R, S, stride)
+    dy = torch.zeros((N, d.Ho, d.Wo, K), dtype=BF, device='cuda')
+    wt = torch.zeros((Cn, R, S, K), dtype=BF, device='cuda')
+    addend = torch.zeros((N, H, W, Cn), dtype=BF, device='cuda')
+    mask = torch.zeros((N * H * W * Cn // 8,), dtype=torch.uint8, device='cuda')
+    bn_y = torch.zeros((N, H, W, Cn), dtype=BF, device='cuda')
+    part = torch.zeros((max(hip_lib.asm_conv2d_dgrad_bnred_blocks(C.byref(d)), 1), 2, Cn), device='cuda')
+    dx = torch.empty((N, H, W, Cn), dtype=BF, device='cuda')
+    p = lambda t: t.data_ptr()   # noqa: E731
+    calls = {
+        0: lambda: hip_lib.asm_conv2d_dgrad(C.byref(d), p(dy), p(wt), None, p(dx), st),
+        lib.ASM_DGRAD_MASKED: lambda: hip_lib.asm_conv2d_dgrad_masked(C.byref(d), p(dy), p(wt), p(addend), p(mask), p(dx), st),
+        lib.ASM_DGRAD_POOLED: lambda: hip_lib.asm_conv2d_dgrad_pooled(C.byref(d), p(dy), p(wt), None, None, p(addend), 1, 1, 0, H,
+                                                                      W, 1, p(dx), st),
+        lib.ASM_DGRAD_BNRED: lambda: hip_lib.asm_conv2d_dgrad_bnred(C.byref(d), p(dy), p(wt), None, None, p(bn_y), None, p(part),
+                                                                    p(dx), st),
+    }
+    for variant, call in calls.items():
+      tag = '%s %s variant %d' % (workload, key[:8], variant)
+      fam = hip_lib.asm_conv2d_dgrad_kernel(C.byref(d), variant)
+      rc = call()
+      if fam == lib.ASM_ENOTSUP:
+        assert rc != lib.ASM_OK, tag + ': the query says ENOTSUP, the entry point ran'
+      else:
+        assert fam >= 0 and rc == lib.ASM_OK, '%s: query %d, entry point %d' % (tag, fam, rc)
+        assert hip_lib.asm_debug_last_conv_kernel() == fam, '%s: query %d, ran %d' % (tag, fam, hip_lib.asm_debug_last_conv_kernel())
+        seen.add(fam)
+    torch.cuda.synchronize()
+  assert lib.CONV_DGRAD_S2 in seen or workload == 'r50'
+
+
+def test_stride2_parity_classes_without_a_gather_free_kernel_take_the_generic_gather(hip_lib):
+  """The parity classes of a stride-2 input gradient are planned together: if any class lacks a gather-free kernel, the
+  whole layer runs the generic gather.  Under the current instantiations every class of a layer gets the same answer (the
+  classes differ only in their tap shape, and igemm2 has the plain epilogue for all of them), so no shape could stop
+  half-launched; this pins the whole-layer fallback on a layer no class covers (K = 40 input channels of the gradient: no
+  igemm2 tile steps through them) against the direct kernel."""
+  from assembled_cnn_amd import ops
+  N, H, W, Cn, K = 2, 16, 12, 64, 40
+  d = ops.make_conv_desc(N, H, W, Cn, K, 3, 3, 2)
+  w = _rand((K, 3, 3, Cn), 41, scale=(1.0 / (9 * Cn)) ** 0.5).cuda()
+  dy = _rand((N, d.Ho, d.Wo, K), 42).cuda()
+  wt = torch.zeros((Cn, 3, 3, K), dtype=BF, device='cuda')
+  ops.filter_transpose(w, wt, K, 3, 3, Cn)
+  assert ops.dgrad_kernel(d) == 0
+  dx = ops.conv_dgrad(d, dy, wt)
+  assert hip_lib.asm_debug_last_conv_kernel() == 0
+  dxn = torch.empty_like(dx)
+  st = torch.cuda.current_stream().cuda_stream
+  assert hip_lib.asm_conv2d_dgrad_naive(C.byref(d), dy.data_ptr(), w.data_ptr(), dxn.data_ptr(), st) == 0
+  assert util.rel_l2(dx.float(), dxn.float()) <= 4e-3

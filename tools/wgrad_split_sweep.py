@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Same-box sweep of the weight gradient's pixel-split count (asm_tuning.wgrad_splits) against the cost model's own choice
-(csrc/conv_wgrad.hip make_plan), every convolution shape of a workload at the benchmark batch, reduce pass included.
+(csrc/conv_wgrad.hip plan_wgrad), every convolution shape of a workload at the benchmark batch, reduce pass included.
 usage: wgrad_split_sweep.py [--workload W] [--batch B] [--splits 2,4,...] [--only SUBSTR] [--out file.json]"""
 import argparse
 import ctypes as C
