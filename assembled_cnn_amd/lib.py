@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ASM_HIP_LIB') or os.path.join(HERE, 'libasm_hip.so')
 
 ASM_OK, ASM_EINVAL, ASM_ENOTSUP, ASM_EHIP = 0, -1, -2, -3
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class AsmError(RuntimeError):
@@ -189,6 +189,11 @@ SIGNATURES = {
     'asm_dropblock_apply': (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _P]),
     'asm_eval_rows': (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     'asm_eval_accumulate': (_I, [_P, _P, _P, _I, _P, _P]),
+    'asm_embed_sqnorm': (_I, [_P, _I, _I, _I, _P, _P]),
+    'asm_retrieval_topk_workspace_bytes': (_Z, [_I, _I, _I]),
+    'asm_retrieval_topk': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    'asm_topk_merge': (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    'asm_recall_accumulate': (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _I, _P, _P]),
     'asm_sgd_momentum': (_I, [_P, _P, _P, _P, _Z, _F, _F, _F, _F, _P]),
     'asm_conv2d_fprop_bn': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'asm_bn_apply2': (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P]),

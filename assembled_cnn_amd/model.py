@@ -484,7 +484,10 @@ class Model(object):
       else:
         x = conv_bn(ctx, x, ce, be, 1, relu=True)   # relu after squeeze (:591-592)
     if return_embedding:
-      return None if ctx.dry else x.data.view(x.shape[0], x.shape[3]).float()
+      if ctx.dry:
+        return None
+      self.embedding_bf16 = x.data.view(x.shape[0], x.shape[3])   # what the head stored; the returned fp32 is its conversion
+      return self.embedding_bf16.float()
     return self._dense(ctx, x)
 
   def _dense(self, ctx: Ctx, x: Var):

@@ -972,3 +972,68 @@ def resize_crop_flip(src_u8, descs_dev, n, out_h, out_w, subtract_mean):
     check(L().asm_resize_crop_flip(_ptr(src_u8), src_u8.numel(), _ptr(descs_dev), n, out_h, out_w,
                                    1 if subtract_mean else 0, _ptr(out), _stream()), 'resize_crop_flip')
   return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# retrieval evaluation (metric/recall_metric.py)
+# ---------------------------------------------------------------------------------------------------
+SIMILARITIES = {'cosine': 0, 'euclidean': 1}    # eval_similarity (nets/hparams_config.py:273)
+
+
+def _emb(x, D):
+  """[rows, ld] bf16, rows contiguous -> (rows, D, ld)"""
+  if x.dim() != 2 or x.dtype != BF16 or x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) != x.shape[1]):
+    raise ValueError('embeddings must be a contiguous 2-D bfloat16 tensor')
+  ld = x.shape[1]
+  return x.shape[0], (ld if D is None else D), ld
+
+
+def embed_sqnorm(x, D=None):
+  """float32 [rows]: sum of squares of the first D channels of every row of x (bf16 [rows, ld])."""
+  n, D, ld = _emb(x, D)
+  sq = empty((n,), F32, x)
+  check(L().asm_embed_sqnorm(_ptr(x), n, D, ld, _ptr(sq), _stream()), 'embed_sqnorm')
+  return sq
+
+
+def retrieval_topk_workspace_bytes(Q, N, K) -> int:
+  return int(L().asm_retrieval_topk_workspace_bytes(Q, N, K))
+
+
+def retrieval_topk(queries, index, sq_queries, sq_index, K, similarity='cosine', index_base=0, D=None):
+  """(top_val float32 [Q, K], top_idx int32 [Q, K]): the K index rows most similar to every query, best first, of equal
+  values the lower index first; top_idx counts from index_base (the first global row of this shard of the index)."""
+  if similarity not in SIMILARITIES:
+    raise NotImplementedError('eval_similarity %r (cosine | euclidean)' % (similarity,))   # recall_metric.py:107-108
+  Q, Dq, ldq = _emb(queries, D)
+  N, Di, ldi = _emb(index, D)
+  if Dq != Di:
+    raise ValueError('queries have %d channels, the index %d' % (Dq, Di))
+  need = retrieval_topk_workspace_bytes(Q, N, K)
+  ws = _workspace(need, queries)
+  val = empty((Q, K), F32, queries)
+  idx = empty((Q, K), torch.int32, queries)
+  check(L().asm_retrieval_topk(_ptr(queries), ldq, _ptr(index), ldi, _ptr(sq_queries), _ptr(sq_index), Q, N, Dq,
+                               SIMILARITIES[similarity], K, index_base, _ptr(val), _ptr(idx), _ptr(ws), need, _stream()),
+        'retrieval_topk')
+  return val, idx
+
+
+def topk_merge(vals, idxs):
+  """[rows, P, K] sorted lists (float32 values, int32 indices, -1 = unused) -> the K best per row, same order."""
+  rows, P, K = vals.shape
+  if tuple(idxs.shape) != (rows, P, K):
+    raise ValueError('values and indices differ in shape')
+  val = empty((rows, K), F32, vals)
+  idx = empty((rows, K), torch.int32, vals)
+  check(L().asm_topk_merge(_ptr(vals), _ptr(idxs), rows, P, K, _ptr(val), _ptr(idx), _stream()), 'topk_merge')
+  return val, idx
+
+
+def recall_accumulate(top_idx, query_labels, index_labels, query_base, k_list_dev, hits):
+  """hits[i] (int32, device) += number of rows of top_idx whose label is among the first k_list[i] entries after the
+  entry equal to the row's own query number (query_base + row) is dropped (recall_metric.get_recall)."""
+  Q, K = top_idx.shape
+  check(L().asm_recall_accumulate(_ptr(top_idx), Q, K, _ptr(query_labels), _ptr(index_labels), index_labels.numel(),
+                                  query_base, _ptr(k_list_dev), k_list_dev.numel(), _ptr(hits), _stream()),
+        'recall_accumulate')

@@ -682,6 +682,12 @@ class Trainer(object):
     """Inference forward (BN moving statistics), logits float32 [B, C]."""
     return self.model(images_meansub_nhwc, False, use_resnet_d=self.p.use_resnet_d)
 
+  def embed(self, images_meansub_nhwc: torch.Tensor) -> torch.Tensor:
+    """Inference forward with return_embedding=True (metric/recall_metric.py:51-55): the embedding as the head stored it,
+    bfloat16 [B, D] on the device -- what retrieval.RecallEvaluator.add takes."""
+    self.model(images_meansub_nhwc, False, use_resnet_d=self.p.use_resnet_d, return_embedding=True)
+    return self.model.embedding_bf16
+
   # ---- evaluation metrics on device (nets/run_loop_classification.py:208-219) ----------------------
   def eval_reset(self):
     self.eval_state = torch.zeros((33,), dtype=torch.float32, device=self.model.device)

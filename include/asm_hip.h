@@ -35,7 +35,7 @@ extern "C" {
 #define ASM_ENOTSUP (-2)
 #define ASM_EHIP (-3)
 
-#define ASM_ABI_VERSION 6
+#define ASM_ABI_VERSION 7
 
 const char* asm_last_error(void);
 int asm_abi_version(void);
@@ -493,6 +493,42 @@ int asm_eval_rows(const float* logits, int ld, const int32_t* labels, int B, int
                   float* top1, float* top5, void* stream);
 int asm_eval_accumulate(const float* conf, const float* top1, const float* top5, int B, float* state33,
                         void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Retrieval evaluation: Recall@K (metric/recall_metric.py; --zeroshot_eval, nets/run_loop_classification.py:439-445).
+ * Embeddings are bf16 rows of D channels with a row stride ld (elements; ld >= D, ld % 8 == 0: 16-byte rows; channels
+ * D .. ld-1 are never used and may hold anything).  Label -1 marks a distractor: it is indexed but never a query.
+ * ---------------------------------------------------------------------------------------------- */
+/* sq[n] = sum_d x[n][d]^2 in float32 (the |.|^2 of tf_simple_pairwise_distance :207-215 and of tf.nn.l2_normalize) */
+int asm_embed_sqnorm(const void* x, int N, int D, int ld, float* sq, void* stream);
+/* Similarity of Q queries with N index rows and, per query, the K best index rows -- tf.matmul + tf.nn.top_k(k, sorted=True) of
+ * :98-110 in one kernel that never stores the [Q, N] matrix.  similarity 0: cosine, (q.x) * rsqrt(max(|q|^2, 1e-12)) *
+ * rsqrt(max(|x|^2, 1e-12)); 1: euclidean, -(|q|^2 + |x|^2 - 2 q.x); q.x accumulates the raw bf16 products in float32, sq_queries /
+ * sq_index are asm_embed_sqnorm of the two operands.  top_val float32 [Q][K] descending, top_idx int32 [Q][K] = row in `index` +
+ * index_base (the first global row of this shard of the index); of equal values the lower index first (TensorFlow's rule);
+ * with N < K the unused slots hold -inf / -1.  K is max(k_list) + 1 (:110).  workspace: asm_retrieval_topk_workspace_bytes(Q, N, K)
+ * bytes (positive, non-decreasing in each argument; 0 for a non-positive one) for the lists of the index splits the kernel cuts the
+ * walk into; the split count depends on (Q, N) alone, so the result is the same on every run.
+ * Errors, all raised before anything is launched: a null pointer, a non-positive size, ld < D or ld % 8 != 0, index_base < 0 or
+ * index_base + N beyond int32, a short workspace -> ASM_EINVAL; similarity other than 0 / 1 (the reference's
+ * NotImplementedError, :107-108) and K > 64 (asm_last_error names the cap) -> ASM_ENOTSUP. */
+size_t asm_retrieval_topk_workspace_bytes(int Q, int N, int K);
+int asm_retrieval_topk(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
+                       const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base,
+                       float* top_val, int32_t* top_idx, void* workspace, size_t workspace_bytes, void* stream);
+/* P sorted lists of K (value, index) per row, in_val / in_idx [rows][P][K] (index -1: unused slot, at the end of its list) -> the K
+ * best of them, out_val / out_idx [rows][K], same order: value descending, of equal values the lower index first.  Combines the
+ * index shards of several devices (:115-123 is this merge for num_gpus shards).  The output must not alias the input; K > 64 ->
+ * ASM_ENOTSUP. */
+int asm_topk_merge(const float* in_val, const int32_t* in_idx, int rows, int P, int K, float* out_val, int32_t* out_idx,
+                   void* stream);
+/* get_recall (:217-228) for Q rows of top_idx [Q][K]: query number qi = query_base + row (its position in the QUERY list) is
+ * dropped from its row wherever it appears, the remaining entries are mapped through index_labels [N], and hits[i] += 1 if
+ * query_labels[row] is among the first k_list[i] of them (k_list: int32 [nk] on the device; entries outside [0, N) match nothing).
+ * hits: int32 [nk], integer atomics -- exact, the same on every run.  As in the reference, qi is compared with positions in the
+ * INDEX: the two agree only while no distractor precedes the query. */
+int asm_recall_accumulate(const int32_t* top_idx, int Q, int K, const int32_t* query_labels, const int32_t* index_labels,
+                          int N, int query_base, const int32_t* k_list, int nk, int32_t* hits, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Input-pipeline tail: the tensor work of imagenet_preprocessing.preprocess_image after
