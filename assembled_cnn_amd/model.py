@@ -214,7 +214,7 @@ class Model(object):
       # The big branch's output gradient (whatever lazy form it is in) was allocated on the compute stream and is read on
       # the branch stream; its consumer drops it while the little branch keeps allocating on the compute stream, and the
       # caching allocator would hand the block out again while the branch stream still reads it.  Kept alive until the join.
-      keep = (big_out._grad, big_out.grad_mask, big_out.pre_dy, big_out.pool_grad)
+      keep = big_out.held()
       ops.stream_join(side, main)       # the merge's backward produced both branches' output gradients on the compute stream
       bi = li = 0
       try:

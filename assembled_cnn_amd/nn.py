@@ -316,13 +316,21 @@ def const_init(shape, value):
 # activations + tape
 # ---------------------------------------------------------------------------------------------------
 class Var(object):
-  """An activation: NHWC bf16 tensor (``data`` is None during the shape-only build walk).
-
-  The gradient may be held LAZILY MASKED: (``_grad``, ``grad_mask``) stands for _grad * [mask bit set] -- the masked
-  gradient dz = dy * [y > 0] that the ReLU behind a residual add sends down the shortcut branch.  The two consumers
-  that dominate (the input gradient of the next 1x1 convolution, which adds it in its epilogue, and the batch-norm
-  backward of a projection shortcut) read (dy, mask) directly, so dz is never written; anything else just reads
-  ``.grad``, which materialises it."""
+  """An activation: NHWC bf16 tensor (``data`` is None during the shape-only build walk) and the gradient accumulated for
+  it so far, which only the methods below write.  The gradient is the sum of up to two terms:
+    * (``_grad``, ``grad_mask``): a tensor, possibly LAZILY MASKED -- it stands for _grad * [mask bit set], the masked gradient
+      dz = dy * [y > 0] that the ReLU behind a residual add sends down the shortcut branch.  The consumers that dominate
+      (the input gradient of the next 1x1 convolution, which adds it in its epilogue, and the batch-norm backward of a
+      projection shortcut) read (dy, mask) directly, so dz is never written;
+    * ``pool_grad``: (dpool [N,Hp,Wp,C], k, stride, pad, count_valid) stands for avgpool_bwd(dpool); a 1x1 stride-1
+      convolution reading this activation gathers it in its input-gradient epilogue (asm_conv2d_dgrad_pooled).
+  Anything else just reads ``.grad``, which materialises the sum through the ordinary kernels.  What always holds:
+    * only a tensor nobody else reads (``grad_owned``) is updated in place;
+    * a reader that bypasses ``.grad`` (take_masked_grad) cannot drop a pending pooled term;
+    * ``red`` = (partials, the gradient tensor they were reduced from), the batch-norm backward sums of the layer that
+      produced this activation, reduced by the convolution whose input gradient wrote ``_grad`` (asm_conv2d_dgrad_bnred),
+      is dropped by ANY change of the gradient's value (another term, a mask, a replacement).
+  ``pre_dy``: this layer's batch-norm backward has been run by the block-final layer (ops.bn_bwd_dual); its dy waits here."""
   __slots__ = ('_data', 'shape', '_grad', 'grad_mask', 'grad_owned', 'needs_grad', 'bn_ctx', 'red_ctx', 'red',
                'pre_dy', 'deferred', 'pool_grad')
 
@@ -333,27 +341,14 @@ class Var(object):
     # reader just touches .data, which runs the ordinary apply pass once.
     self.deferred = None
     self.shape = tuple(data.shape) if data is not None else tuple(shape)
-    self._grad = None
-    self.grad_mask = None
-    self.grad_owned = False
     self.needs_grad = needs_grad
-    # projection-shortcut fusion: the output of a ReLU-less conv + batch norm carries what its BN backward needs (bn_ctx);
-    # the block-final layer that adds it behind one ReLU then runs BOTH batch-norm backwards in one reduce + one apply
-    # (ops.bn_bwd_dual) and leaves this layer's dy here (pre_dy)
-    self.bn_ctx = None
-    self.pre_dy = None
-    # a gradient contribution still in pooled form: (dpool [N,Hp,Wp,C], k, stride, pad, count_valid) stands for
-    # avgpool_bwd(dpool); a 1x1 stride-1 convolution reading this activation gathers it in its input-gradient epilogue
-    # (asm_conv2d_dgrad_pooled), anything else reads .grad, which scatters it through asm_avgpool_bwd
-    self.pool_grad = None
-    # batch-norm backward sums in the producing input gradient's epilogue (asm_conv2d_dgrad_bnred).  red_ctx, set in the forward
-    # pass on the output of a conv -> BN [-> + shortcut] [-> ReLU] layer: (its pre-BN convolution output y, its packed ReLU mask
-    # or None) -- what a convolution that reads this activation needs to reduce (sum dz, sum dz * y) while it writes the
-    # activation's gradient.  red, set by that convolution's backward: (partials, the gradient tensor they were reduced from).
-    # Anything that changes the gradient afterwards (another fan-in term, a lazy mask) drops it; the layer's own backward uses it
-    # only if the gradient it finds IS that tensor, unmasked -- otherwise it runs its reduce pass as before.
-    self.red_ctx = None
-    self.red = None
+    self._grad = self.grad_mask = self.pool_grad = self.red = self.pre_dy = None
+    self.grad_owned = False
+    # Set in the forward pass for the backward closures.  bn_ctx, on the output of a ReLU-less conv + batch norm: what its BN
+    # backward needs, so that the block-final layer adding it behind one ReLU can run BOTH batch-norm backwards at once.
+    # red_ctx, on the output of a conv -> BN [-> + shortcut] [-> ReLU] layer: (its pre-BN convolution output y, its packed ReLU
+    # mask or None), what a convolution reading this activation needs to reduce ``red`` while it writes the gradient.
+    self.bn_ctx = self.red_ctx = None
 
   @property
   def data(self):
@@ -368,33 +363,64 @@ class Var(object):
 
   @property
   def grad(self):
+    """the gradient as one tensor (materialises a lazy mask and a pending pooled term)"""
     if self.grad_mask is not None:
-      self._grad = ops.mask_apply(self._grad, self.grad_mask)
-      self.grad_mask = None
-      self.grad_owned = True
-      self.red = None
+      self.set_grad(ops.mask_apply(self._grad, self.grad_mask), True)
     if self.pool_grad is not None:
-      dp, k, stride, pad, cv = self.pool_grad
-      self.pool_grad = None
-      self.red = None
-      if self._grad is None:
-        self._grad = ops.avgpool_bwd(dp, self.shape, k, stride, pad, cv)
-      elif self.grad_owned:
-        ops.avgpool_bwd(dp, self.shape, k, stride, pad, cv, addend=self._grad)      # in place
-      else:
-        self._grad = ops.add_bf16(self._grad, ops.avgpool_bwd(dp, self.shape, k, stride, pad, cv))
-      self.grad_owned = True
+      pg, self.pool_grad = self.pool_grad, None
+      self._add_scattered(*pg)
     return self._grad
 
   @grad.setter
   def grad(self, g):
-    self._grad = g
-    self.grad_mask = None
+    """None: clear.  A tensor: one that someone else may read too."""
+    self.set_grad(g, False)
+
+  def set_grad(self, g, owned: bool, red_part=None):
+    """The (tensor, mask) term becomes ``g``; ``owned``: nobody else reads g, we may update it in place later; ``red_part``:
+    the batch-norm backward sums that were reduced while g was written."""
+    self._grad, self.grad_mask, self.grad_owned = g, None, owned
+    self.red = (red_part, g) if red_part is not None else None
+
+  def add_grad(self, g, owned: bool, mask=None):
+    """+= g [* mask].  ``owned`` says whether g may later be updated in place by us."""
     self.red = None
+    if mask is not None:
+      if self._grad is None:
+        self._grad, self.grad_mask, self.grad_owned = g, mask, False
+        return
+      g, owned = ops.mask_apply(g, mask), True
+    cur = self.grad
+    if cur is None:
+      self.set_grad(g, owned)
+    elif self.grad_owned:
+      ops.add_bf16(cur, g, out=cur)
+    else:
+      self.set_grad(ops.add_bf16(cur, g), True)
+
+  def add_pooled_grad(self, dp, k, stride, pad, count_valid, keep_pooled: bool):
+    """+= avgpool_bwd(dp).  ``keep_pooled``: a convolution that runs its backward later may be able to gather the term
+    (take_pool_grad), so leave it in pooled form -- one such term at a time."""
+    self.red = None
+    if keep_pooled and self.pool_grad is None:
+      self.pool_grad = (dp, k, stride, pad, count_valid)
+    else:
+      self.grad                       # one tensor, no mask
+      self._add_scattered(dp, k, stride, pad, count_valid)
+
+  def _add_scattered(self, dp, k, stride, pad, count_valid):
+    self.red = None
+    if self._grad is None:
+      self._grad = ops.avgpool_bwd(dp, self.shape, k, stride, pad, count_valid)
+    elif self.grad_owned:
+      ops.avgpool_bwd(dp, self.shape, k, stride, pad, count_valid, addend=self._grad)      # in place
+    else:
+      self._grad = ops.add_bf16(self._grad, ops.avgpool_bwd(dp, self.shape, k, stride, pad, count_valid))
+    self.grad_owned = True
 
   def take_masked_grad(self):
     """-> (gradient tensor, packed mask or None) without materialising the product.  A pooled contribution nobody
-    gathered (take_pool_grad) is scattered first, so a caller that bypasses ``.grad`` can never drop it."""
+    gathered (take_pool_grad) is scattered first."""
     if self.pool_grad is not None:
       self.grad      # the getter scatters it (and materialises a lazy mask)
     return self._grad, self.grad_mask
@@ -407,25 +433,33 @@ class Var(object):
     pg, self.pool_grad = self.pool_grad, None
     return pg
 
+  def take_red(self, g, relu_mask):
+    """-> the pre-reduced batch-norm backward sums if they were reduced from ``g`` (while set, ``red`` is of the whole gradient,
+    unmasked) under the ReLU mask ``relu_mask``; else None.  Dropped either way."""
+    red, self.red = self.red, None
+    ok = red is not None and red[1] is g and self.red_ctx is not None and self.red_ctx[1] is relu_mask
+    return red[0] if ok else None
+
+  def park_dy(self, dy):
+    self.pre_dy = dy
+
+  def take_dy(self):
+    dy, self.pre_dy = self.pre_dy, None
+    return dy
+
+  def no_grad_yet(self) -> bool:
+    return self._grad is None and self.pre_dy is None
+
+  def held(self):
+    """-> (gradient tensor, its lazy mask, parked dy, pooled term) as they are: whoever reads them on another stream keeps
+    them alive with this; tests look at the lazy state without touching it"""
+    return self._grad, self.grad_mask, self.pre_dy, self.pool_grad
+
 
 def accum_grad(v: Var, g: torch.Tensor, owned: bool, mask: Optional[torch.Tensor] = None):
-  """v.grad += g [* mask].  ``owned`` says whether g may later be updated in place by us."""
-  if not v.needs_grad:
-    return
-  v.red = None           # the gradient changes: sums reduced from an earlier form of it are void
-  if mask is not None:
-    if v._grad is None:
-      v._grad, v.grad_mask, v.grad_owned = g, mask, False
-      return
-    g, owned = ops.mask_apply(g, mask), True
-  if v.grad is None:
-    v.grad = g
-    v.grad_owned = owned
-  elif v.grad_owned:
-    ops.add_bf16(v.grad, g, out=v.grad)
-  else:
-    v.grad = ops.add_bf16(v.grad, g)
-    v.grad_owned = True
+  """v.grad += g [* mask] (Var.add_grad) for an activation that wants a gradient"""
+  if v.needs_grad:
+    v.add_grad(g, owned, mask)
 
 
 class Ctx(object):
@@ -614,9 +648,7 @@ class ConvKernel(object):
     None).  Falls back to the plain input gradient (partials None) wherever the fused form does not apply."""
     a = self.arena
     self.wgrad_streamed(d, x, dy)
-    if self.stem:
-      return None, None
-    if not need_dx:
+    if self.stem or not need_dx:
       return None, None
     if addend_mask is not None and (d.stride != 1 or d.C % 8) and not ops.dgrad_s2_ok(d):
       addend, addend_mask = ops.mask_apply(addend, addend_mask), None     # the strided forms take a plain addend
@@ -720,19 +752,12 @@ def conv_bn(ctx: Ctx, x: Var, conv: ConvKernel, bn: BatchNorm, stride: int, relu
     x_t = x.data
 
     def bwd():
-      if out.pre_dy is not None:      # projection shortcut: the block-final layer already ran this batch norm's backward
-        dy, out.pre_dy = out.pre_dy, None
+      dy = out.take_dy()
+      if dy is not None:               # projection shortcut: the block-final layer already ran this batch norm's backward
         a.notify_grad(bn.gamma)
-        pool = x.take_pool_grad(d) if (conv.kpad == conv.cout and x.needs_grad) else None
-        if x.pool_grad is not None:
-          x.grad                                        # (not gatherable here) scatter it now
-        xg, xmask = x.take_masked_grad()
-        dx = conv.backward(d, x_t, dy, x.needs_grad, addend=xg, addend_mask=xmask, pool=pool)
-        if dx is not None:
-          x.grad, x.grad_owned = dx, True
+        # no sums for x's producer: the main branch's first convolution still adds to this dx
+        conv_input_grad(conv, d, x, x_t, dy, want_red=False)
         return
-      if out.pool_grad is not None:
-        out.grad                                        # a pooled contribution nobody gathered: scatter it now
       # the incoming gradient may be lazily masked by the ReLU of the block this layer's output was the shortcut of:
       # a BN without its own ReLU takes that mask as if it were its own (dz = dout * mask is exactly what it needs)
       dout, in_mask = out.take_masked_grad()
@@ -744,57 +769,52 @@ def conv_bn(ctx: Ctx, x: Var, conv: ConvKernel, bn: BatchNorm, stride: int, relu
           dout, in_mask = out.grad, None                 # (never on this path's networks) materialise
         else:
           bmask, brelu = in_mask, True
-      lazy = LAZY_DZ and residual is not None and relu and res_mode == 1 and mask_t is not None and residual.needs_grad
-      # BigLittle merge (res_mode 2): the 2x2 block sum reads (dout, mask) as well, so dz is not written there either
-      lazy_up = LAZY_DZ and residual is not None and relu and res_mode == 2 and mask_t is not None
-      want_dz = residual is not None and relu and not lazy and not lazy_up
-      rc = residual.bn_ctx if residual is not None else None
-      dual = (lazy and rc is not None and residual._grad is None and residual.pre_dy is None and rc[5] == M and rc[6] == Cn
-              and in_mask is None and dual_bn_on())
+      # Behind a ReLU the shortcut's share is dz = dout * [out > 0].  ``lazy``: dz is not written, the shortcut receives the
+      # pair (dout, mask) (res_mode 2, the BigLittle merge: its 2x2 block sum reads the pair).  ``dual``: lazy, and the shortcut
+      # is a projection's batch norm no other gradient has reached: both batch norms see the same masked gradient, so one
+      # reduce + one apply serve both and its dy is parked on it.  Otherwise the batch-norm backward apply writes dz.
+      masked = residual is not None and relu
+      lazy = masked and LAZY_DZ and mask_t is not None and (residual.needs_grad if res_mode == 1 else res_mode == 2)
+      rc = residual.bn_ctx if (lazy and res_mode == 1) else None
+      dual = (rc is not None and residual.no_grad_yet() and rc[5] == M and rc[6] == Cn and in_mask is None and dual_bn_on())
+      dz = None
       if small:
-        dy, dz = ops.bn_small_bwd(dout, y, bmask, M, Cn, gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta)), None
+        dy = ops.bn_small_bwd(dout, y, bmask, M, Cn, gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta))
       elif dual:
-        # out = relu(bn(y) + bn_sc(y_sc)): both batch norms see the same masked gradient -> one reduce, one apply
-        sc_bn = rc[4]
-        dy, residual.pre_dy = ops.bn_bwd_dual(dout, y, rc[0], mask_t, M, Cn,
-                                              (gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta)),
-                                              (rc[1], rc[2], rc[3], a.g(sc_bn.gamma), a.g(sc_bn.beta)))
-        dz = None
+        dy, dy_sc = ops.bn_bwd_dual(dout, y, rc[0], mask_t, M, Cn,
+                                    (gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta)),
+                                    (rc[1], rc[2], rc[3], a.g(rc[4].gamma), a.g(rc[4].beta)))
+        residual.park_dy(dy_sc)
       else:
         # the input gradient that wrote dout may have reduced (sum dz, sum dz * y) already (Var.red)
-        raw = None
-        if (out.red is not None and out.red[1] is dout and in_mask is None and out.red_ctx is not None
-            and out.red_ctx[1] is bmask):
-          raw = out.red[0]
-        out.red = None
-        dy, dz = ops.bn_bwd(dout, y, bmask, brelu, M, Cn, gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta), want_dz,
-                            raw_part=raw)
+        dy, dz = ops.bn_bwd(dout, y, bmask, brelu, M, Cn, gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta),
+                            masked and not lazy, raw_part=out.take_red(dout, bmask))
       a.notify_grad(bn.gamma)
-      if residual is not None:
-        if dual:
-          pass             # the shortcut layer's gradient is complete: its dy waits in residual.pre_dy
-        elif lazy:           # dz = dout * mask is NOT written: the shortcut branch receives (dout, mask)
+      if residual is not None and not dual:
+        if res_mode == 2:
+          accum_grad(residual, ops.upsample2x_bwd(dout, mask_t) if lazy else ops.upsample2x_bwd(dz if relu else dout), True)
+        elif lazy:
           accum_grad(residual, dout, False, mask=mask_t)
         else:
-          dres = dz if relu else dout
-          if res_mode == 2:
-            accum_grad(residual, ops.upsample2x_bwd(dout, mask_t) if lazy_up else ops.upsample2x_bwd(dres), True)
-          else:
-            accum_grad(residual, dres, relu)
-      pool = x.take_pool_grad(d) if (conv.kpad == conv.cout and x.needs_grad and not conv.stem) else None
-      if x.pool_grad is not None:
-        x.grad                                          # (not gatherable here) scatter it now
-      xg, xmask = x.take_masked_grad()
-      # fan-in add (and a pending average-pool backward) fused into the dgrad epilogue; and, when x is itself the output of
-      # a conv -> BN layer, the reduce pass of THAT batch norm's backward (x.red_ctx)
-      dx, part = conv.backward_red(d, x_t, dy, x.needs_grad, addend=xg, addend_mask=xmask, pool=pool, red_ctx=x.red_ctx)
-      if dx is not None:
-        x.grad, x.grad_owned = dx, True
-        if part is not None:
-          x.red = (part, dx)
+          accum_grad(residual, dz if relu else dout, relu)
+      conv_input_grad(conv, d, x, x_t, dy)
       out.grad = None
+    bwd.relu_mask = mask_t          # by name for the test harness, which teacher-forces the saved ReLU decisions
     ctx.record(bwd)
   return out
+
+
+def conv_input_grad(conv: ConvKernel, d, x: Var, x_t: torch.Tensor, dy: torch.Tensor, want_red: bool = True):
+  """The tail of every convolution's backward: dW into the gradient arena, and x's gradient becomes dx + what x has
+  accumulated so far -- the fan-in add (with its lazy mask) and a pending average-pool backward ride in the dgrad epilogue
+  where the kernel can take them, and are materialised first where it cannot.  ``want_red``: when x is itself the output of
+  a conv -> BN layer, reduce THAT batch norm's backward sums while writing dx (x.red_ctx); only right when this dx is x's
+  final gradient."""
+  pool = x.take_pool_grad(d) if (conv.kpad == conv.cout and x.needs_grad) else None
+  xg, xmask = x.take_masked_grad()
+  dx, part = conv.backward_red(d, x_t, dy, x.needs_grad, xg, xmask, pool, x.red_ctx if want_red else None)
+  if dx is not None:
+    x.set_grad(dx, True, part)
 
 
 def conv_plain(ctx: Ctx, x: Var, conv: ConvKernel, out_f32: bool, ldy: int = 0):
@@ -811,9 +831,7 @@ def conv_plain(ctx: Ctx, x: Var, conv: ConvKernel, out_f32: bool, ldy: int = 0):
     # the backward descriptor is always a bf16 one; dy's row stride is ldy when the logits were padded
     dd = ops.make_conv_desc(d.N, d.H, d.W, d.C, d.K, d.R, d.S, d.stride, pad=d.pad, Ho=d.Ho, Wo=d.Wo,
                             ldy=ldy if (ldy and ldy != conv.cout) else 0)
-    dx = conv.backward(dd, x_t, dy, x.needs_grad, addend=x.grad)
-    if dx is not None:
-      x.grad, x.grad_owned = dx, True
+    conv_input_grad(conv, dd, x, x_t, dy, want_red=False)
   return y, bwd, tuple(y.shape)
 
 
@@ -912,12 +930,7 @@ class SKUnit(object):
                            grad_stats, mask_stats if factor else None)
         s.grad = None
         a.notify_grad(bn.gamma)
-        # fan-in add fused into the dgrad epilogue, and the reduce pass of conv1's batch-norm backward (x.red_ctx)
-        dx, part = conv.backward_red(d, x_t, dy, x.needs_grad, addend=x.grad, red_ctx=x.red_ctx)
-        if dx is not None:
-          x.grad, x.grad_owned = dx, True
-          if part is not None:
-            x.red = (part, dx)
+        conv_input_grad(conv, d, x, x_t, dy)
         v.grad = None
       ctx.record(bwd)
     return v
@@ -985,16 +998,11 @@ def avg_pool(ctx: Ctx, x: Var, k: int, stride: int, pad: int, count_valid: bool)
     def bwd():
       if y.grad is None:
         raise RuntimeError('avg_pool backward: no gradient reached this layer')
-      if (x.needs_grad and x.pool_grad is None and stride in (1, 2) and stride <= k <= 2 * stride and
-          ops.knob('ASM_POOL_FUSE', '1') != '0'):
-        # leave the contribution in pooled form: the block's first 1x1 convolution gathers it in its input-gradient
-        # epilogue (its backward runs after this one: model._bottleneck orders the tape that way)
-        x.pool_grad = (y.grad, k, stride, pad, count_valid)
-      elif x.needs_grad and x.grad is not None and x.grad_owned:
-        # gradient fan-in of the block input (main path arrived first): add inside the pool backward, in place
-        ops.avgpool_bwd(y.grad, x.shape, k, stride, pad, count_valid, addend=x.grad)
-      else:
-        accum_grad(x, ops.avgpool_bwd(y.grad, x.shape, k, stride, pad, count_valid), True)
+      if x.needs_grad:
+        # left in pooled form where the block's first 1x1 convolution can gather it in its input-gradient epilogue (its
+        # backward runs after this one: model._bottleneck orders the tape that way), else scattered into x's gradient
+        x.add_pooled_grad(y.grad, k, stride, pad, count_valid,
+                          stride in (1, 2) and stride <= k <= 2 * stride and ops.knob('ASM_POOL_FUSE', '1') != '0')
       y.grad = None
     ctx.record(bwd)
   return y

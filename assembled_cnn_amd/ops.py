@@ -491,6 +491,15 @@ def bn_apply(x, M, Cn, scale, shift, residual=None, res_mode=0, relu=False, H=0,
   return (y, mask) if want_mask else y
 
 
+def _bn_bwd_coeffs(part, M, Cn, gamma, mean, invstd, dgamma, dbeta, co, raw=False):
+  """(sum dz, sum dz * xhat) partials [``raw``: (sum dz, sum dz * y), from a convolution epilogue] -> dgamma, dbeta and the
+  three coefficient rows ``co`` of the batch-norm backward apply pass"""
+  part = _compact(part, Cn)
+  fin, what = (L().asm_bn_bwd_finalize_raw, 'bn_bwd_finalize_raw') if raw else (L().asm_bn_bwd_finalize, 'bn_bwd_finalize')
+  check(fin(_ptr(part), part.shape[0], M, Cn, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dgamma), _ptr(dbeta),
+            _ptr(co[0]), _ptr(co[1]), _ptr(co[2]), _stream()), what)
+
+
 def bn_bwd(dy, x, yout, relu, M, Cn, gamma, mean, invstd, dgamma, dbeta, want_dz, raw_part=None):
   """-> dx, dz (dz None unless want_dz).  dgamma/dbeta: f32 [C] views, overwritten.
   ``yout`` is the bf16 forward output or (uint8) the packed ReLU mask from bn_apply(want_mask=True).
@@ -500,19 +509,12 @@ def bn_bwd(dy, x, yout, relu, M, Cn, gamma, mean, invstd, dgamma, dbeta, want_dz
   red_bytes = 0.0 if raw_part is not None else (4.0 + (0.125 if rk == 2 else 2.0 if rk == 1 else 0.0))
   ev = _bn_ev(M * Cn * (red_bytes + 4.0 + 2.0 + (2.0 if want_dz else 0.0) + (0.125 if rk == 2 else 2.0 if rk == 1 else 0.0)))
   co = empty((3, Cn), F32, dy)
-  if raw_part is not None:
-    part = _compact(raw_part, Cn)
-    check(L().asm_bn_bwd_finalize_raw(_ptr(part), part.shape[0], M, Cn, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dgamma),
-                                      _ptr(dbeta), _ptr(co[0]), _ptr(co[1]), _ptr(co[2]), _stream()), 'bn_bwd_finalize_raw')
-  else:
-    blocks = L().asm_bn_stats_blocks(M, Cn)
-    part = empty((blocks, 2, Cn), F32, dy)
+  part = raw_part
+  if part is None:
+    part = empty((L().asm_bn_stats_blocks(M, Cn), 2, Cn), F32, dy)
     check(L().asm_bn_bwd_reduce(_ptr(dy), _ptr(x), _ptr(yout if relu else None), rk, M, Cn,
                                 _ptr(mean), _ptr(invstd), _ptr(part), _stream()), 'bn_bwd_reduce')
-    part = _compact(part, Cn)
-    blocks = part.shape[0]
-    check(L().asm_bn_bwd_finalize(_ptr(part), blocks, M, Cn, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dgamma),
-                                  _ptr(dbeta), _ptr(co[0]), _ptr(co[1]), _ptr(co[2]), _stream()), 'bn_bwd_finalize')
+  _bn_bwd_coeffs(part, M, Cn, gamma, mean, invstd, dgamma, dbeta, co, raw=raw_part is not None)
   dx = torch.empty_like(x)
   dz = torch.empty_like(x) if want_dz else None
   check(L().asm_bn_bwd_apply(_ptr(dy), _ptr(x), _ptr(yout if relu else None), rk, M, Cn,
@@ -544,10 +546,7 @@ def bn_bwd_dual(dy, xa, xb, mask, M, Cn, bn_a, bn_b):
                                _ptr(bn_b[1]), _ptr(bn_b[2]), _ptr(pa), _ptr(pb), _stream()), 'bn_bwd_reduce2')
   co = empty((6, Cn), F32, dy)
   for i, (part, (gamma, mean, invstd, dgamma, dbeta)) in enumerate(((pa, bn_a), (pb, bn_b))):
-    part = _compact(part, Cn)
-    check(L().asm_bn_bwd_finalize(_ptr(part), part.shape[0], M, Cn, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dgamma),
-                                  _ptr(dbeta), _ptr(co[3 * i]), _ptr(co[3 * i + 1]), _ptr(co[3 * i + 2]), _stream()),
-          'bn_bwd_finalize')
+    _bn_bwd_coeffs(part, M, Cn, gamma, mean, invstd, dgamma, dbeta, co[3 * i:3 * i + 3])
   dxa, dxb = torch.empty_like(xa), torch.empty_like(xb)
   check(L().asm_bn_bwd_apply2(_ptr(dy), _ptr(xa), _ptr(xb), _ptr(mask), M, Cn, _ptr(co), _ptr(dxa), _ptr(dxb), _stream()),
         'bn_bwd_apply2')
@@ -736,29 +735,21 @@ def sk_bn_bwd(dv, att, ds, y, scale, shift, gamma, mean, invstd, dgamma, dbeta, 
   With the per-image statistics of sk_select_bn_bwd_att / sk_gap_bn the reduce pass is replaced by a tiny finalize."""
   N, H, W, C2 = y.shape
   HW, M = H * W, N * H * W
+  co = empty((3, C2), F32, y)
   if grad_stats is not None and mask_stats is not None:
     ev = _bn_ev(M * (2.0 * C2 + 2.0 * F_ + 2.0 * C2))         # one pass over (y, dV), one write of dy
-    co = empty((3, C2), F32, y)
     check(L().asm_sk_bn_bwd_finalize(_ptr(grad_stats), _ptr(mask_stats), _ptr(att), _ptr(ds), N, HW, F_, _ptr(gamma),
                                      _ptr(mean), _ptr(invstd), _ptr(dgamma), _ptr(dbeta), _ptr(co[0]), _ptr(co[1]),
                                      _ptr(co[2]), _stream()), 'sk_bn_bwd_finalize')
-    dy = torch.empty_like(y)
-    check(L().asm_sk_bn_bwd_apply(_ptr(dv), _ptr(att), _ptr(ds), _ptr(y), _ptr(scale), _ptr(shift), _ptr(co[0]),
-                                  _ptr(co[1]), _ptr(co[2]), _ptr(dy), N, HW, F_, _stream()), 'sk_bn_bwd_apply')
-    if ev is not None:
-      ev.record()
-    return dy
-  blocks = L().asm_sk_bn_bwd_blocks(N, HW, F_)
-  if blocks <= 0:
-    raise ValueError('sk_bn_bwd: bad shape')
-  ev = _bn_ev(M * (2 * (2.0 * C2 + 2.0 * F_) + 2.0 * C2))     # two passes over (y, dV), one write of dy
-  part = empty((blocks, 2, C2), F32, y)
-  check(L().asm_sk_bn_bwd_reduce(_ptr(dv), _ptr(att), _ptr(ds), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean),
-                                 _ptr(invstd), N, HW, F_, _ptr(part), _stream()), 'sk_bn_bwd_reduce')
-  part = _compact(part, C2)
-  co = empty((3, C2), F32, y)
-  check(L().asm_bn_bwd_finalize(_ptr(part), part.shape[0], M, C2, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(dgamma),
-                                _ptr(dbeta), _ptr(co[0]), _ptr(co[1]), _ptr(co[2]), _stream()), 'bn_bwd_finalize')
+  else:
+    blocks = L().asm_sk_bn_bwd_blocks(N, HW, F_)
+    if blocks <= 0:
+      raise ValueError('sk_bn_bwd: bad shape')
+    ev = _bn_ev(M * (2 * (2.0 * C2 + 2.0 * F_) + 2.0 * C2))     # two passes over (y, dV), one write of dy
+    part = empty((blocks, 2, C2), F32, y)
+    check(L().asm_sk_bn_bwd_reduce(_ptr(dv), _ptr(att), _ptr(ds), _ptr(y), _ptr(scale), _ptr(shift), _ptr(mean),
+                                   _ptr(invstd), N, HW, F_, _ptr(part), _stream()), 'sk_bn_bwd_reduce')
+    _bn_bwd_coeffs(part, M, C2, gamma, mean, invstd, dgamma, dbeta, co)
   dy = torch.empty_like(y)
   check(L().asm_sk_bn_bwd_apply(_ptr(dv), _ptr(att), _ptr(ds), _ptr(y), _ptr(scale), _ptr(shift), _ptr(co[0]),
                                 _ptr(co[1]), _ptr(co[2]), _ptr(dy), N, HW, F_, _stream()), 'sk_bn_bwd_apply')

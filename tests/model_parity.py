@@ -518,11 +518,12 @@ def check_teacher_forced_backward(name, device, batch, size, label_smoothing=0.1
 
     def peek_grad(v):
       """the gradient a Var holds, materialised WITHOUT touching its lazy state; (tensor or None, was_lazy)"""
-      g, lazy = v._grad, False
-      if g is not None and v.grad_mask is not None:
-        g, lazy = ops.mask_apply(g, v.grad_mask), True
-      if v.pool_grad is not None:
-        dp, k, stride, pad, cv = v.pool_grad
+      g, mask, _, pool = v.held()
+      lazy = False
+      if g is not None and mask is not None:
+        g, lazy = ops.mask_apply(g, mask), True
+      if pool is not None:
+        dp, k, stride, pad, cv = pool
         s = ops.avgpool_bwd(dp, v.shape, k, stride, pad, cv)
         g, lazy = (s if g is None else ops.add_bf16(g, s)), True
       return g, lazy
@@ -543,12 +544,12 @@ def check_teacher_forced_backward(name, device, batch, size, label_smoothing=0.1
         ent[3] += 1
 
       def bwd():
-        if out.pre_dy is None and ref_out.grad is not None:
+        if out.held()[2] is None and ref_out.grad is not None:      # (no batch-norm backward parked here already)
           g, lazy = peek_grad(out)
           assert g is not None, '%s: no gradient reached this group' % label
           cmp(g, ref_out.grad, label, 'dout-squeeze' if squeeze else ('dout-lazy' if lazy else 'dout'))
           if not lazy:
-            out._grad, out.grad_mask, out.grad_owned = to_dev(ref_out.grad), None, True
+            out.set_grad(to_dev(ref_out.grad), True)
             n_forced[0] += 1
         inner()
         ent = pending_dx.get(id(x_var)) if x_var is not None else None
@@ -614,8 +615,7 @@ def check_teacher_forced_backward(name, device, batch, size, label_smoothing=0.1
         # them regularly EQUALS the channel mean: its normalised value is 0 up to float32 rounding (|out| <= 1e-7 on both
         # sides, measured), and whether ReLU'(0) counts as 0 or 1 is decided by the last bit.  One such tie is 3-7 % of a
         # squeeze layer's dbeta (16 terms per channel).  The oracle's decisions are written into the product's packed mask.
-        fn = ctx.tape[-1]
-        cell = fn.__closure__[fn.__code__.co_freevars.index('mask_t')].cell_contents
+        cell = ctx.tape[-1].relu_mask
         if cell is not None:
           bits = (ref_out.detach().reshape(ref_out.shape[0], -1) > 0).to(torch.uint8).view(ref_out.shape[0], -1, 8)
           packed = (bits * (2 ** torch.arange(8, dtype=torch.uint8))).sum(-1).to(torch.uint8)
