@@ -5,6 +5,8 @@
 //                          top_k(sim, k = max(k_list) + 1, sorted=True)                                     reads it again
 //   here                   retrieval_topk_kernel: one MFMA GEMM whose epilogue keeps a sorted list of K (value, index) pairs per
 //                          query row; it moves O((Q + N) D) bytes where the reference moves O(Q N)
+//                          retrieval_topk_wide_kernel (64 < K <= 1024): the same GEMM and epilogue (retrieval_walk), whose
+//                          survivors go unsorted into a per-query candidate buffer that a radix select cuts back to K
 //
 // Tiling.  A workgroup of four waves owns 128 query rows (wave w: rows 32 w .. 32 w + 31) and walks a contiguous range of
 // 128-row index tiles in ascending order.  Per 64-channel step both tiles go global -> registers -> LDS (the next step's loads
@@ -31,7 +33,7 @@ namespace {
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int PITCH = BK * 2 + 16;          // bytes per LDS tile row: the 16-byte pad spreads the ds_read_b128 row reads over the banks
-constexpr int TOPK_MAX = 64;                // lists are insertion-sorted: past this a selection scheme of another kind is due
+constexpr int TOPK_MAX = 64;                // lists are insertion-sorted: past this the wide selection below
 constexpr int SPLIT_MAX = 64, SPLIT_TARGET = 512;   // workgroups wanted (two per CU) / most splits of one query tile
 constexpr int EMPTY = 0x7fffffff;           // index of an unused list slot while lists are being built (-1 once stored)
 
@@ -45,6 +47,9 @@ struct TopkArgs {
   float* out_val;       // [Q][S][K]
   int* out_idx;
   int Q, N, D, ldq, ldi, K, sim, index_base, S, tiles_per_split, n_tiles;
+  int B;                // wide selection only: capacity of a (query, run) candidate buffer
+  unsigned long long* counters;   // wide selection, test builds of the call only (else null): {survivors appended,
+                                  // compactions during the walk, compactions at the end of a run}
 };
 
 // 8 channels [e, e + 8) of one row; zero beyond the row count or D.  e % 8 == 0 and ld % 8 == 0 keep the 16 bytes inside the row
@@ -64,27 +69,23 @@ __device__ __forceinline__ u32x4 load_chunk(const bf16_t* base, int row, int nro
   return v;
 }
 
-__global__ __launch_bounds__(256, 2) void retrieval_topk_kernel(TopkArgs p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// The walk both selection kernels share: the 128 x 128 x 64 GEMM over this workgroup's run of index tiles and the scale
+// epilogue.  At the end of every index tile a lane holds the 64 similarities of its query in acc (acc[a][i]: index row
+// nb + a*32 + (i&3) + 8*(i>>2) + 4*lhi) and the bit mask `cand` of those that reach sel.threshold(row); sel.insert takes them.
+// One instantiation per selection scheme, so every similarity is the same bits whichever scheme looks at it.
+template <class Sel>
+__device__ __forceinline__ void retrieval_walk(const TopkArgs& p, unsigned char* smem, Sel& sel) {
   unsigned char* qs = smem;
   unsigned char* xs = smem + BM * PITCH;
   float* xn = reinterpret_cast<float*>(smem + (BM + BN) * PITCH);     // per index row of the tile: |x|^2 or rsqrt(max(|x|^2, eps))
-  float* lv = xn + BN;                                                 // [K][BM] list values
-  int* li = reinterpret_cast<int*>(lv + p.K * BM);                     // [K][BM] list indices (local to this index)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, lhi = lane >> 5;
-  const int K = p.K;
   const int q0 = blockIdx.x * BM;
   const int split = blockIdx.y;
   const int t0 = split * p.tiles_per_split;
   const int t1 = min(p.n_tiles, t0 + p.tiles_per_split);
   const int ksteps = (p.D + BK - 1) / BK;
-
-  for (int i = tid; i < K * BM; i += 256) {
-    lv[i] = -INFINITY;
-    li[i] = EMPTY;
-  }
 
   const int row = wave * 32 + l31;            // the query row of this lane inside the tile
   float qn = 0.f;
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void retrieval_topk_kernel(TopkArgs p) {
   const int total = (t1 - t0) * ksteps;
 #pragma unroll 1
   for (int s = 0; s < total; ++s) {
-    __syncthreads();                          // the previous step's fragment reads (and the list initialisation) are done
+    __syncthreads();                          // the previous step's fragment reads (and the selection's initialisation) are done
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       *reinterpret_cast<u32x4*>(qs + (r0 + 32 * j) * PITCH + chunk * 16) = gq[j];
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256, 2) void retrieval_topk_kernel(TopkArgs p) {
     }
     // ---- epilogue of one index tile: acc[a][i] is (query l31, index row a*32 + (i&3) + 8*(i>>2) + 4*lhi) ----
     const int nb = tile * BN;
-    float thr = lv[(K - 1) * BM + row];        // written by this wave before the barriers above
+    const float thr = sel.threshold(row);
     unsigned long long cand = 0ull;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
@@ -166,21 +167,44 @@ __global__ __launch_bounds__(256, 2) void retrieval_topk_kernel(TopkArgs p) {
         acc[a][i] = sv;
         if (nb + nl < p.N && sv >= thr) cand |= 1ull << (a * 16 + i);
       }
-    // the two lanes of a query insert in turn; a lane re-reads the threshold its partner may have raised
+    sel.insert(acc, cand, nb, row, lhi);
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[a][i] = 0.f;
+    kc = 0;
+    ++tile;
+  }
+}
+
+// acc[b >> 4][b & 15]: registers cannot be indexed, a select chain can
+__device__ __forceinline__ float pick(const f32x16 (&acc)[4], int b) {
+  float sv = 0.f;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) sv = b == a * 16 + i ? acc[a][i] : sv;
+  return sv;
+}
+
+// K <= 64: a sorted list per query, [K][BM] in LDS, whose K-th entry is the threshold
+struct ListSel {
+  float* lv;
+  int* li;
+  int K;
+  __device__ __forceinline__ float threshold(int row) const { return lv[(K - 1) * BM + row]; }   // written by this wave before the barriers of the step
+  // the two lanes of a query insert in turn; a lane re-reads the threshold its partner may have raised
+  __device__ __forceinline__ void insert(const f32x16 (&acc)[4], unsigned long long cand, int nb, int row, int lhi) {
 #pragma unroll 1
     for (int half = 0; half < 2; ++half) {
       if (lhi == half && cand != 0ull) {
-        thr = lv[(K - 1) * BM + row];
+        float thr = lv[(K - 1) * BM + row];
         int thi = li[(K - 1) * BM + row];
         unsigned long long left = cand;
         while (left != 0ull) {                 // ascending index order; rare once the list is warm
           const int b = __builtin_ctzll(left);
           left &= left - 1ull;
-          float sv = 0.f;                      // acc[b >> 4][b & 15]: registers cannot be indexed, a select chain can
-#pragma unroll
-          for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) sv = b == a * 16 + i ? acc[a][i] : sv;
+          const float sv = pick(acc, b);
           const int n = nb + (b >> 4) * 32 + (b & 3) + 8 * ((b & 15) >> 2) + 4 * lhi;
           if (better(sv, n, thr, thi)) {
             int j = K - 1;
@@ -201,14 +225,22 @@ __global__ __launch_bounds__(256, 2) void retrieval_topk_kernel(TopkArgs p) {
       }
       __syncthreads();
     }
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[a][i] = 0.f;
-    kc = 0;
-    ++tile;
   }
+};
+
+__global__ __launch_bounds__(256, 2) void retrieval_topk_kernel(TopkArgs p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  float* lv = reinterpret_cast<float*>(smem + (BM + BN) * PITCH) + BN;      // [K][BM] list values, behind the tiles and the |x|^2 row
+  int* li = reinterpret_cast<int*>(lv + p.K * BM);                          // [K][BM] list indices (local to this index)
+  const int tid = threadIdx.x, K = p.K;
+  for (int i = tid; i < K * BM; i += 256) {
+    lv[i] = -INFINITY;
+    li[i] = EMPTY;
+  }
+  ListSel sel{lv, li, K};
+  retrieval_walk(p, smem, sel);
   __syncthreads();
+  const int q0 = blockIdx.x * BM, split = blockIdx.y;
   if (tid < BM && q0 + tid < p.Q) {
     const size_t o = ((size_t)(q0 + tid) * p.S + split) * K;
     for (int j = 0; j < K; ++j) {
@@ -216,6 +248,285 @@ __global__ __launch_bounds__(256, 2) void retrieval_topk_kernel(TopkArgs p) {
       p.out_val[o + j] = lv[j * BM + tid];
       p.out_idx[o + j] = n == EMPTY ? -1 : n + p.index_base;
     }
+  }
+}
+
+// ---- wide selection (64 < K <= 1024; legal from K = 1) -------------------------------------------------------------------------
+// A (value, index) pair is ranked by one 64-bit key, larger = better: the value's bits mapped so that unsigned order is float
+// order (-0 counts as +0, as the float compare of the list path has it) above the complement of the index, so of equal values
+// the lower index wins.  Keys of distinct index rows are distinct: the K best are one set, whatever order they arrived in.
+// Key 0 is an unused slot (index -1).
+typedef unsigned long long u64;
+constexpr int WIDE_MAX = 1024;
+constexpr int WIDE_ROOM_MIN = 256, WIDE_ROOM_MAX = 448;   // room above K in a candidate buffer: K itself, within these bounds (the
+                                                          // trigger sits BN below the capacity, so BN of it is never filled)
+constexpr int WIDE_NCH = 23;                  // 64-key register chunks that hold the largest buffer: wide_capacity(WIDE_MAX) / 64
+constexpr int WIDE_TARGET = 256;              // workgroups wanted: one per CU, the buffers of two would not meet the workspace bound
+
+inline int wide_capacity(int K) {             // B: K + its room, whole 64-key chunks; non-decreasing in K
+  int room = K < WIDE_ROOM_MIN ? WIDE_ROOM_MIN : K;
+  if (room > WIDE_ROOM_MAX) room = WIDE_ROOM_MAX;
+  return (K + room + 63) / 64 * 64;
+}
+static_assert(WIDE_NCH * 64 == (WIDE_MAX + WIDE_ROOM_MAX + 63) / 64 * 64, "the register copy of a buffer holds the largest one");
+
+__device__ __forceinline__ u64 make_key(float v, int idx) {
+  if (idx < 0) return 0ull;
+  unsigned u = __float_as_uint(v);
+  if (u == 0x80000000u) u = 0u;
+  u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
+  return ((u64)u << 32) | (unsigned)~idx;
+}
+__device__ __forceinline__ float key_value(u64 k) {
+  const unsigned u = (unsigned)(k >> 32);
+  return __uint_as_float((u >> 31) ? u ^ 0x80000000u : ~u);
+}
+__device__ __forceinline__ int key_index(u64 k) { return (int)~(unsigned)k; }
+
+__device__ __forceinline__ void wave_sync() {             // LDS traffic between the lanes of one wave
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// One step of a radix select, by one whole wave: hist holds the counts of 256 digit values; the digit d in which the need-th
+// largest element lies (1 <= need <= sum of hist), how many elements have a larger digit, and how many have d itself.
+__device__ __forceinline__ void select_digit(const unsigned* hist, int need, int lane, int& d, int& above, int& binc) {
+  unsigned c[4], s = 0u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    c[j] = hist[255 - (4 * lane + j)];        // lanes walk the digits downwards
+    s += c[j];
+  }
+  unsigned incl = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(incl, o);
+    if (lane >= o) incl += t;
+  }
+  unsigned run = incl - s;
+  int fd = -1, fa = 0, fb = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (fd < 0 && run < (unsigned)need && (unsigned)need <= run + c[j]) {
+      fd = 255 - (4 * lane + j);
+      fa = (int)run;
+      fb = (int)c[j];
+    }
+    run += c[j];
+  }
+  const u64 found = __ballot(fd >= 0);
+  const int src = found ? __builtin_ctzll(found) : 0;
+  d = max(__shfl(fd, src), 0);
+  above = __shfl(fa, src);
+  binc = __shfl(fb, src);
+}
+
+// K <= 1024: per (query, run) an unsorted buffer of B candidates in the workspace, the count and the threshold in registers
+struct WideSel {
+  float* wv;            // this wave's first query, this run: row r of the wave is at r * rstride
+  int* wi;
+  unsigned* hist;       // this wave's 256 digit counts in LDS
+  size_t rstride;       // S * B
+  int K, B, index_base, l31;
+  unsigned long long* counters;
+  bool valid;           // this lane's query exists
+  float thr;            // a lower bound of the K-th best value of this lane's query so far
+  int cnt;              // entries in its buffer (the two lanes of a query agree)
+
+  __device__ __forceinline__ float threshold(int) const { return thr; }
+
+  // The wave keeps the K best of the n > K entries of row r's buffer, in place, and returns the new threshold.  The buffer is
+  // read once into registers; every digit pass counts from there.
+  __device__ float compact(int r, int n) {
+    float* v = wv + (size_t)r * rstride;
+    int* ix = wi + (size_t)r * rstride;
+    const int lane = threadIdx.x & 63;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the appends of this wave's other lanes: one CU, one vector cache --
+                                                             // a wider scope would write the L2 back at every compaction
+    u64 key[WIDE_NCH];
+#pragma unroll
+    for (int c = 0; c < WIDE_NCH; ++c) {
+      const int e = c * 64 + lane;
+      key[c] = 0ull;
+      if (c * 64 < n && e < n) key[c] = make_key(v[e], ix[e]);
+    }
+    u64 prefix = 0ull;
+    int need = K;
+#pragma unroll 1
+    for (int shift = 56;; shift -= 8) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) hist[lane + 64 * j] = 0u;
+      wave_sync();
+      const u64 mask = shift == 56 ? 0ull : ~0ull << (shift + 8);
+#pragma unroll
+      for (int c = 0; c < WIDE_NCH; ++c)
+        if (c * 64 < n && key[c] != 0ull && (key[c] & mask) == prefix) atomicAdd(&hist[(unsigned)(key[c] >> shift) & 255u], 1u);
+      wave_sync();
+      int d, above, binc;
+      select_digit(hist, need, lane, d, above, binc);
+      wave_sync();
+      prefix |= (u64)d << shift;
+      need -= above;
+      if (need == binc || shift == 0) break;  // the whole bin is taken: every key >= prefix is one of the K best
+    }
+    int out = 0;
+#pragma unroll
+    for (int c = 0; c < WIDE_NCH; ++c)
+      if (c * 64 < n) {
+        const bool keep = key[c] != 0ull && key[c] >= prefix;
+        const u64 b = __ballot(keep);
+        const int pos = out + __popcll(b & ((1ull << lane) - 1ull));
+        if (keep && pos < B) {
+          v[pos] = key_value(key[c]);
+          ix[pos] = key_index(key[c]);
+        }
+        out += __popcll(b);
+      }
+    const float t = key_value(prefix);        // the low bits of an early exit are zero: at or below every kept value
+    return t != t ? -INFINITY : t;
+  }
+
+  __device__ __forceinline__ void insert(const f32x16 (&acc)[4], unsigned long long cand, int nb, int row, int lhi) {
+    if (!valid) cand = 0ull;
+    const int c = __popcll(cand), cp = __shfl_xor(c, 32);
+    if (counters && c) atomicAdd(counters, (unsigned long long)c);
+    int pos = cnt + (lhi ? cp : 0);           // the low lane's survivors first: no turn-taking, the order never shows
+    float* v = wv + (size_t)l31 * rstride;
+    int* ix = wi + (size_t)l31 * rstride;
+    while (cand != 0ull) {
+      const int b = __builtin_ctzll(cand);
+      cand &= cand - 1ull;
+      const float sv = pick(acc, b);
+      const int n = nb + (b >> 4) * 32 + (b & 3) + 8 * ((b & 15) >> 2) + 4 * lhi;
+      if (pos < B) {                          // always: a tile adds at most BN to a count of at most B - BN
+        v[pos] = sv;
+        ix[pos] = n + index_base;
+      }
+      ++pos;
+    }
+    cnt += c + cp;
+    // a query whose buffer could overflow on the next tile is compacted now, by the whole wave; the other waves wait at the step barrier
+    u64 full = __ballot(cnt > B - BN) & 0xffffffffull;
+    while (full != 0ull) {
+      const int r = __builtin_ctzll(full);
+      full &= full - 1ull;
+      const float t = compact(r, __shfl(cnt, r));
+      if (counters && (threadIdx.x & 63) == 0) atomicAdd(counters + 1, 1ull);
+      if (l31 == r) {
+        cnt = K;
+        thr = t;
+      }
+    }
+  }
+};
+
+// one workgroup per CU (WIDE_TARGET): no second one to leave registers for
+__global__ __launch_bounds__(256) void retrieval_topk_wide_kernel(TopkArgs p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qw = blockIdx.x * BM + wave * 32;                // the wave's first query
+  const size_t o = ((size_t)qw * p.S + blockIdx.y) * p.B;
+  WideSel sel;
+  sel.wv = p.out_val + o;
+  sel.wi = p.out_idx + o;
+  sel.hist = reinterpret_cast<unsigned*>(smem + (BM + BN) * PITCH + BN * 4) + wave * 256;
+  sel.rstride = (size_t)p.S * p.B;
+  sel.K = p.K; sel.B = p.B; sel.index_base = p.index_base; sel.l31 = lane & 31;
+  sel.counters = p.counters;
+  sel.valid = qw + sel.l31 < p.Q;
+  sel.thr = -INFINITY;
+  sel.cnt = 0;
+  retrieval_walk(p, smem, sel);
+  // what the run leaves: at most K entries per query, the rest of the first K slots unused
+  const int nvalid = min(32, p.Q - qw);
+#pragma unroll 1
+  for (int r = 0; r < 32; ++r) {
+    int n = __shfl(sel.cnt, r);
+    if (r >= nvalid) break;
+    if (n > p.K) {
+      sel.compact(r, n);
+      if (p.counters && lane == 0) atomicAdd(p.counters + 2, 1ull);
+      n = p.K;
+    }
+    for (int e = n + lane; e < p.K; e += 64) {
+      sel.wv[(size_t)r * sel.rstride + e] = -INFINITY;
+      sel.wi[(size_t)r * sel.rstride + e] = -1;
+    }
+  }
+}
+
+// The K best of P lists per row, sorted: one workgroup per row.  List l of row r holds K entries from (r * P + l) * stride on, in
+// any order, index -1 = unused.  A radix select over the keys finds the K-th best, the keys at or above it are gathered into LDS
+// (slots by atomic counter: the bitonic sort that follows removes the order they landed in) and sorted.
+__global__ __launch_bounds__(256) void topk_merge_wide_kernel(const float* __restrict__ in_val, const int* __restrict__ in_idx, int P,
+                                                              int K, size_t stride, float* __restrict__ out_val,
+                                                              int* __restrict__ out_idx) {
+  __shared__ unsigned hist[256];
+  __shared__ u64 keys[WIDE_MAX];
+  __shared__ int pick_d, pick_above, pick_binc, nsel;
+  const int tid = threadIdx.x;
+  const size_t r = blockIdx.x;
+  const float* iv = in_val + r * P * stride;
+  const int* ii = in_idx + r * P * stride;
+  u64 prefix = 0ull;
+  int need = K;                               // P * K >= K slots, unused ones (key 0) counted: the K-th may be an unused one
+#pragma unroll 1
+  for (int shift = 56;; shift -= 8) {
+    hist[tid] = 0u;
+    __syncthreads();
+    const u64 mask = shift == 56 ? 0ull : ~0ull << (shift + 8);
+    for (int l = 0; l < P; ++l)
+      for (int j = tid; j < K; j += 256) {
+        const u64 k = make_key(iv[l * stride + j], ii[l * stride + j]);
+        if ((k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
+      }
+    __syncthreads();
+    if (tid < 64) {
+      int d, above, binc;
+      select_digit(hist, need, tid, d, above, binc);
+      if (tid == 0) {
+        pick_d = d;
+        pick_above = above;
+        pick_binc = binc;
+      }
+    }
+    __syncthreads();
+    prefix |= (u64)pick_d << shift;
+    need -= pick_above;
+    if (need == pick_binc || shift == 0) break;
+  }
+  int n2 = 2;
+  while (n2 < K) n2 <<= 1;
+  for (int j = tid; j < n2; j += 256) keys[j] = 0ull;
+  if (tid == 0) nsel = 0;
+  __syncthreads();
+  for (int l = 0; l < P; ++l)
+    for (int j = tid; j < K; j += 256) {
+      const u64 k = make_key(iv[l * stride + j], ii[l * stride + j]);
+      if (k != 0ull && k >= prefix) {
+        const int s = atomicAdd(&nsel, 1);
+        if (s < n2) keys[s] = k;              // always, for lists of distinct index rows
+      }
+    }
+  __syncthreads();
+  for (int k2 = 2; k2 <= n2; k2 <<= 1)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < n2; i += 256) {
+        const int x = i ^ j;
+        if (x > i) {
+          const u64 a = keys[i], b = keys[x];
+          if ((i & k2) == 0 ? a < b : a > b) {
+            keys[i] = b;
+            keys[x] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  for (int j = tid; j < K; j += 256) {
+    const u64 k = keys[j];
+    out_val[r * K + j] = k ? key_value(k) : -INFINITY;
+    out_idx[r * K + j] = k ? key_index(k) : -1;
   }
 }
 
@@ -298,9 +609,9 @@ __global__ __launch_bounds__(256) void recall_accumulate_kernel(const int* __res
   }
 }
 
-inline int retrieval_splits(int Q, int N, int* tiles_per_split) {
+inline int retrieval_splits(int Q, int N, int* tiles_per_split, int target = SPLIT_TARGET) {
   const int qt = cdiv(Q, BM), nt = cdiv(N, BN);
-  int S = cdiv(SPLIT_TARGET, qt);
+  int S = cdiv(target, qt);
   if (S > SPLIT_MAX) S = SPLIT_MAX;
   if (S > nt) S = nt;
   const int tps = cdiv(nt, S);
@@ -362,6 +673,8 @@ extern "C" int asm_retrieval_topk(const void* queries, int ldq, const void* inde
   a.Q = Q; a.N = N; a.D = D; a.ldq = ldq; a.ldi = ldi; a.K = K; a.sim = similarity; a.index_base = index_base;
   a.n_tiles = cdiv(N, BN);
   a.S = retrieval_splits(Q, N, &a.tiles_per_split);
+  a.B = 0;
+  a.counters = nullptr;
   float* ws_val = (float*)workspace;
   int* ws_idx = (int*)workspace + (size_t)Q * a.S * K;
   a.out_val = a.S == 1 ? top_val : ws_val;     // one split: its list IS the result
@@ -375,6 +688,84 @@ extern "C" int asm_retrieval_topk(const void* queries, int ldq, const void* inde
     ASM_LAUNCH(topk_merge_kernel, dim3(cdiv(Q, 256)), dim3(256), 0, st, ws_val, ws_idx, Q, a.S, K, top_val, top_idx);
   ASM_CHECK_LAUNCH("retrieval_topk");
   return ASM_OK;
+}
+
+// An upper bound of Q * S * B * 8 (S from WIDE_TARGET, B = wide_capacity(K)) that grows with each of Q, N, K
+extern "C" size_t asm_retrieval_topk_wide_workspace_bytes(int Q, int N, int K) {
+  if (Q <= 0 || N <= 0 || K <= 0) return 0;
+  const size_t qt = cdivz((size_t)Q, BM), nt = cdivz((size_t)N, BN);
+  size_t lists = qt * nt;
+  if (lists > WIDE_TARGET + qt) lists = WIDE_TARGET + qt;
+  if (lists > SPLIT_MAX * qt) lists = SPLIT_MAX * qt;
+  const size_t room = K < WIDE_ROOM_MIN ? WIDE_ROOM_MIN : (K > WIDE_ROOM_MAX ? WIDE_ROOM_MAX : K);
+  return lists * BM * (((size_t)K + room + 63) / 64 * 64) * 8;
+}
+
+extern "C" int asm_topk_merge_wide(const float* in_val, const int32_t* in_idx, int rows, int P, int K, float* out_val,
+                                   int32_t* out_idx, void* stream) {
+  ASM_REQUIRE(in_val && in_idx && out_val && out_idx && rows > 0 && P > 0 && K > 0,
+              "topk_merge_wide: bad arguments (rows=%d P=%d K=%d)", rows, P, K);
+  ASM_REQUIRE((const void*)in_val != (const void*)out_val && (const void*)in_idx != (const void*)out_idx,
+              "topk_merge_wide: the output must not alias the input");
+  if (K > WIDE_MAX) ASM_FAIL(ASM_ENOTSUP, "topk_merge_wide: K = %d is above the cap of %d", K, WIDE_MAX);
+  ASM_LAUNCH(topk_merge_wide_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, in_val, in_idx, P, K, (size_t)K, out_val,
+             out_idx);
+  ASM_CHECK_LAUNCH("topk_merge_wide");
+  return ASM_OK;
+}
+
+static int retrieval_topk_wide(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
+                               const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base, float* top_val,
+                               int32_t* top_idx, void* workspace, size_t workspace_bytes, void* stream,
+                               unsigned long long* counters) {
+  ASM_REQUIRE(queries && index && sq_queries && sq_index && top_val && top_idx, "retrieval_topk_wide: null operand");
+  ASM_REQUIRE(Q > 0 && N > 0 && D > 0 && K > 0, "retrieval_topk_wide: sizes must be positive (Q=%d N=%d D=%d K=%d)", Q, N, D, K);
+  ASM_REQUIRE(ldq >= D && ldi >= D && ldq % 8 == 0 && ldi % 8 == 0,
+              "retrieval_topk_wide: rows must be 16-byte multiples of at least D channels (ldq=%d ldi=%d D=%d)", ldq, ldi, D);
+  ASM_REQUIRE(index_base >= 0 && (long long)index_base + N <= 0x7fffffffLL, "retrieval_topk_wide: index_base + N exceeds int32");
+  if (similarity != 0 && similarity != 1)
+    ASM_FAIL(ASM_ENOTSUP, "retrieval_topk_wide: similarity %d (0 cosine, 1 euclidean)", similarity);
+  if (K > WIDE_MAX) ASM_FAIL(ASM_ENOTSUP, "retrieval_topk_wide: K = %d is above the cap of %d", K, WIDE_MAX);
+  ASM_REQUIRE(workspace && workspace_bytes >= asm_retrieval_topk_wide_workspace_bytes(Q, N, K),
+              "retrieval_topk_wide: workspace of %zu bytes, %zu needed", workspace_bytes,
+              asm_retrieval_topk_wide_workspace_bytes(Q, N, K));
+  hipStream_t st = (hipStream_t)stream;
+  TopkArgs a;
+  a.q = (const bf16_t*)queries;
+  a.x = (const bf16_t*)index;
+  a.sqq = sq_queries;
+  a.sqx = sq_index;
+  a.Q = Q; a.N = N; a.D = D; a.ldq = ldq; a.ldi = ldi; a.K = K; a.sim = similarity; a.index_base = index_base;
+  a.n_tiles = cdiv(N, BN);
+  a.S = retrieval_splits(Q, N, &a.tiles_per_split, WIDE_TARGET);
+  a.B = wide_capacity(K);
+  a.counters = counters;
+  a.out_val = (float*)workspace;               // [Q][S][B] candidate values, then as many indices
+  a.out_idx = (int*)workspace + (size_t)Q * a.S * a.B;
+  const int lds = (BM + BN) * PITCH + BN * 4 + 4 * 256 * 4;
+  ASM_LAUNCH(retrieval_topk_wide_kernel, dim3(cdiv(Q, BM), a.S), dim3(256), lds, st, a);
+  ASM_LAUNCH(topk_merge_wide_kernel, dim3(Q), dim3(256), 0, st, (const float*)a.out_val, (const int*)a.out_idx, a.S, K,
+             (size_t)a.B, top_val, top_idx);
+  ASM_CHECK_LAUNCH("retrieval_topk_wide");
+  return ASM_OK;
+}
+
+extern "C" int asm_retrieval_topk_wide(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
+                                       const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base,
+                                       float* top_val, int32_t* top_idx, void* workspace, size_t workspace_bytes, void* stream) {
+  return retrieval_topk_wide(queries, ldq, index, ldi, sq_queries, sq_index, Q, N, D, similarity, K, index_base, top_val, top_idx,
+                             workspace, workspace_bytes, stream, nullptr);
+}
+
+// test-only (asm_hip_debug.h): the same call, adding to three device counters
+extern "C" int asm_debug_retrieval_topk_wide_counted(const void* queries, int ldq, const void* index, int ldi,
+                                                     const float* sq_queries, const float* sq_index, int Q, int N, int D,
+                                                     int similarity, int K, int index_base, float* top_val, int32_t* top_idx,
+                                                     void* workspace, size_t workspace_bytes, void* stream,
+                                                     unsigned long long* counters3) {
+  ASM_REQUIRE(counters3, "retrieval_topk_wide_counted: null counters");
+  return retrieval_topk_wide(queries, ldq, index, ldi, sq_queries, sq_index, Q, N, D, similarity, K, index_base, top_val, top_idx,
+                             workspace, workspace_bytes, stream, counters3);
 }
 
 extern "C" int asm_recall_accumulate(const int32_t* top_idx, int Q, int K, const int32_t* query_labels,

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ASM_HIP_LIB') or os.path.join(HERE, 'libasm_hip.so')
 
 ASM_OK, ASM_EINVAL, ASM_ENOTSUP, ASM_EHIP = 0, -1, -2, -3
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class AsmError(RuntimeError):
@@ -193,6 +193,9 @@ SIGNATURES = {
     'asm_retrieval_topk_workspace_bytes': (_Z, [_I, _I, _I]),
     'asm_retrieval_topk': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
     'asm_topk_merge': (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    'asm_retrieval_topk_wide_workspace_bytes': (_Z, [_I, _I, _I]),
+    'asm_retrieval_topk_wide': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    'asm_topk_merge_wide': (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     'asm_recall_accumulate': (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _I, _P, _P]),
     'asm_sgd_momentum': (_I, [_P, _P, _P, _P, _Z, _F, _F, _F, _F, _P]),
     'asm_conv2d_fprop_bn': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
@@ -217,6 +220,7 @@ DEBUG_SIGNATURES = {
     'asm_debug_tr_probe': (_I, [_P, _P]),
     'asm_conv2d_wgrad_plan': (_I, [_D, C.POINTER(C.c_int32 * 6)]),
     'asm_debug_last_conv_kernel': (_I, []),
+    'asm_debug_retrieval_topk_wide_counted': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P, _P]),
 }
 
 _lib = None

@@ -969,6 +969,8 @@ def resize_crop_flip(src_u8, descs_dev, n, out_h, out_w, subtract_mean):
 # retrieval evaluation (metric/recall_metric.py)
 # ---------------------------------------------------------------------------------------------------
 SIMILARITIES = {'cosine': 0, 'euclidean': 1}    # eval_similarity (nets/hparams_config.py:273)
+TOPK_LIST_MAX = 64       # retrieval_topk / topk_merge: sorted lists in LDS
+TOPK_WIDE_MAX = 1024     # retrieval_topk_wide / topk_merge_wide: candidate buffers + radix select
 
 
 def _emb(x, D):
@@ -1018,6 +1020,39 @@ def topk_merge(vals, idxs):
   val = empty((rows, K), F32, vals)
   idx = empty((rows, K), torch.int32, vals)
   check(L().asm_topk_merge(_ptr(vals), _ptr(idxs), rows, P, K, _ptr(val), _ptr(idx), _stream()), 'topk_merge')
+  return val, idx
+
+
+def retrieval_topk_wide_workspace_bytes(Q, N, K) -> int:
+  return int(L().asm_retrieval_topk_wide_workspace_bytes(Q, N, K))
+
+
+def retrieval_topk_wide(queries, index, sq_queries, sq_index, K, similarity='cosine', index_base=0, D=None):
+  """retrieval_topk for K up to TOPK_WIDE_MAX: the same values and order, by a radix select over candidate buffers."""
+  if similarity not in SIMILARITIES:
+    raise NotImplementedError('eval_similarity %r (cosine | euclidean)' % (similarity,))   # recall_metric.py:107-108
+  Q, Dq, ldq = _emb(queries, D)
+  N, Di, ldi = _emb(index, D)
+  if Dq != Di:
+    raise ValueError('queries have %d channels, the index %d' % (Dq, Di))
+  need = retrieval_topk_wide_workspace_bytes(Q, N, K)
+  ws = _workspace(need, queries)
+  val = empty((Q, K), F32, queries)
+  idx = empty((Q, K), torch.int32, queries)
+  check(L().asm_retrieval_topk_wide(_ptr(queries), ldq, _ptr(index), ldi, _ptr(sq_queries), _ptr(sq_index), Q, N, Dq,
+                                    SIMILARITIES[similarity], K, index_base, _ptr(val), _ptr(idx), _ptr(ws), need, _stream()),
+        'retrieval_topk_wide')
+  return val, idx
+
+
+def topk_merge_wide(vals, idxs):
+  """[rows, P, K] lists in any internal order (float32 values, int32 indices, -1 = unused) -> the K best per row, sorted."""
+  rows, P, K = vals.shape
+  if tuple(idxs.shape) != (rows, P, K):
+    raise ValueError('values and indices differ in shape')
+  val = empty((rows, K), F32, vals)
+  idx = empty((rows, K), torch.int32, vals)
+  check(L().asm_topk_merge_wide(_ptr(vals), _ptr(idxs), rows, P, K, _ptr(val), _ptr(idx), _stream()), 'topk_merge_wide')
   return val, idx
 
 

@@ -3,7 +3,7 @@
 
   embeddings of the validation set (Trainer.embed, bf16) + labels        recall_metric.py:132-148
   -> queries = rows with label != -1, in their original order; index = all rows        :151-159
-  -> similarity + top_k(max(k_list) + 1), fused (ops.retrieval_topk)                    :98-110
+  -> similarity + top_k(max(k_list) + 1), fused (ops.retrieval_topk / _wide)            :98-110
   -> get_recall (ops.recall_accumulate)                                                 :217-228
 """
 from __future__ import annotations
@@ -21,9 +21,13 @@ class RecallEvaluator(object):
   ``k_list`` / ``similarity`` are the flags ``recall_at_k`` / ``eval_similarity`` (nets/hparams_config.py:39,273).  As in the
   reference, a query's own entry is removed from its result row by comparing the row's INDEX positions with the query's
   position in the QUERY list (:221-222), so a self-match stays in the row of every query that a distractor precedes.
+
+  ``selection`` names the top-K kernel for K = max(k_list) + 1: 'list' (ops.retrieval_topk, K <= 64), 'wide'
+  (ops.retrieval_topk_wide, K <= 1024) or 'auto', the list kernel where it applies and the wide one above it.
   """
 
-  def __init__(self, k_list: Sequence[int] = (1, 5), similarity: str = 'cosine', query_chunk: int = 8192):
+  def __init__(self, k_list: Sequence[int] = (1, 5), similarity: str = 'cosine', query_chunk: int = 8192,
+               selection: str = 'auto'):
     if similarity not in ops.SIMILARITIES:
       raise NotImplementedError('eval_similarity %r (cosine | euclidean)' % (similarity,))     # :107-108
     self.k_list = [int(k) for k in k_list]
@@ -31,6 +35,15 @@ class RecallEvaluator(object):
       raise ValueError('k_list must hold positive integers')
     if query_chunk < 1:
       raise ValueError('query_chunk must be positive')
+    if selection not in ('auto', 'list', 'wide'):
+      raise ValueError("selection %r (auto | list | wide)" % (selection,))
+    K = max(self.k_list) + 1                        # :110
+    if selection == 'auto':
+      selection = 'list' if K <= ops.TOPK_LIST_MAX else 'wide'
+    cap = ops.TOPK_LIST_MAX if selection == 'list' else ops.TOPK_WIDE_MAX
+    if K > cap:                                     # before an evaluation set has been embedded
+      raise NotImplementedError('max(k_list) + 1 = %d is above the cap of %d of the %s selection' % (K, cap, selection))
+    self.selection = selection
     self.similarity = similarity
     self.query_chunk = int(query_chunk)
     self.reset()
@@ -120,9 +133,10 @@ class RecallEvaluator(object):
     sq = ops.embed_sqnorm(emb)
     sqq = sq if Q == N else ops.embed_sqnorm(qemb)
     lo, hi = Q * rank // world, Q * (rank + 1) // world             # this rank's queries
+    topk = ops.retrieval_topk if self.selection == 'list' else ops.retrieval_topk_wide
     for s in range(lo, hi, self.query_chunk):
       e = min(hi, s + self.query_chunk)
-      _, idx = ops.retrieval_topk(qemb[s:e], emb, sqq[s:e], sq, K, self.similarity)
+      _, idx = topk(qemb[s:e], emb, sqq[s:e], sq, K, self.similarity)
       ops.recall_accumulate(idx, qlab[s:e], lab, s, k_dev, hits)
     if world > 1:
       import torch.distributed as dist

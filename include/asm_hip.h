@@ -35,7 +35,7 @@ extern "C" {
 #define ASM_ENOTSUP (-2)
 #define ASM_EHIP (-3)
 
-#define ASM_ABI_VERSION 7
+#define ASM_ABI_VERSION 8
 
 const char* asm_last_error(void);
 int asm_abi_version(void);
@@ -522,6 +522,23 @@ int asm_retrieval_topk(const void* queries, int ldq, const void* index, int ldi,
  * ASM_ENOTSUP. */
 int asm_topk_merge(const float* in_val, const int32_t* in_idx, int rows, int P, int K, float* out_val, int32_t* out_idx,
                    void* stream);
+/* The same for 1 <= K <= ASM_TOPK_WIDE_MAX (a k_list up to 1023: R@1000), by a selection scheme of another kind: same arguments,
+ * same similarity values bit for bit (one GEMM and epilogue serve both kernels), same result -- top_val descending, of equal
+ * values the lower index first, -inf / -1 in the unused slots when N < K, index_base honoured -- except that a zero value is
+ * always written as +0.  The K best under (value descending, index ascending) are one set in one order: the result is a pure
+ * function of the inputs, the same bits on every run.  workspace: asm_retrieval_topk_wide_workspace_bytes(Q, N, K) bytes
+ * (positive, non-decreasing in each argument; 0 for a non-positive one) of unsorted candidates, O(Q S K) and never the [Q, N]
+ * matrix.  Errors as above, all before anything is launched; K > 1024 -> ASM_ENOTSUP (asm_last_error names the cap). */
+#define ASM_TOPK_WIDE_MAX 1024
+size_t asm_retrieval_topk_wide_workspace_bytes(int Q, int N, int K);
+int asm_retrieval_topk_wide(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
+                            const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base,
+                            float* top_val, int32_t* top_idx, void* workspace, size_t workspace_bytes, void* stream);
+/* asm_topk_merge for K <= ASM_TOPK_WIDE_MAX: the P lists of a row, in_val / in_idx [rows][P][K], may be in any internal order
+ * (index -1: unused slot, anywhere) and hold distinct index rows; out_val / out_idx [rows][K] sorted as above.  The output must
+ * not alias the input; K > 1024 -> ASM_ENOTSUP. */
+int asm_topk_merge_wide(const float* in_val, const int32_t* in_idx, int rows, int P, int K, float* out_val, int32_t* out_idx,
+                        void* stream);
 /* get_recall (:217-228) for Q rows of top_idx [Q][K]: query number qi = query_base + row (its position in the QUERY list) is
  * dropped from its row wherever it appears, the remaining entries are mapped through index_labels [N], and hits[i] += 1 if
  * query_labels[row] is among the first k_list[i] of them (k_list: int32 [nk] on the device; entries outside [0, N) match nothing).

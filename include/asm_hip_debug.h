@@ -31,6 +31,14 @@ int asm_conv2d_wgrad_plan(const asm_conv_desc* d, int32_t plan[6]);
  * 5 dgrad_s2_kernel, 8 igemm8_kernel (wave-staggered multi-phase loop); -1 before the first call. */
 int asm_debug_last_conv_kernel(void);
 
+/* asm_retrieval_topk_wide with the same arguments and result, which also ADDS to three device counters (uint64, zeroed by the
+ * caller): {candidates appended to the (query, run) buffers, compactions during the index walk, compactions at the end of a
+ * run}.  tools/retrieval_bench.py --counters reports them per query. */
+int asm_debug_retrieval_topk_wide_counted(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
+                                          const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base,
+                                          float* top_val, int32_t* top_idx, void* workspace, size_t workspace_bytes,
+                                          void* stream, unsigned long long* counters3);
+
 
 #ifdef __cplusplus
 }
