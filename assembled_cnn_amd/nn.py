@@ -13,9 +13,8 @@ momentum / bf16 arenas) so the optimiser and the gradient all-reduce are single 
 from __future__ import annotations
 
 import math
-import os
 from collections import OrderedDict
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -23,15 +22,23 @@ import torch
 from . import ops
 
 BN_EPS = 1e-5  # nets/model_helper.py:26
-# ASM_LAZY_DZ=0: materialise the masked shortcut gradient dz in the BN backward apply (the pre-round-2 path; A/B runs)
-LAZY_DZ = os.environ.get('ASM_LAZY_DZ', '1') != '0'
-# ASM_BN_DEFER=0: a projection shortcut's batch norm is applied by its own pass (materialised) instead of inside the add
-DEFER_BN = os.environ.get('ASM_BN_DEFER', '1') != '0'
 
 
 def dual_bn_on() -> bool:
   """ASM_BN_DUAL=0: two separate batch-norm backwards for a projection block (A/B runs, tests); cached until ops.refresh_tuning()"""
   return ops.knob('ASM_BN_DUAL', '1') != '0'
+
+
+def lazy_dz_on() -> bool:
+  """ASM_LAZY_DZ=0: materialise the masked shortcut gradient dz in the BN backward apply (the pre-round-2 path; A/B runs);
+  cached until ops.refresh_tuning()"""
+  return ops.knob('ASM_LAZY_DZ', '1') != '0'
+
+
+def defer_bn_on() -> bool:
+  """ASM_BN_DEFER=0: a projection shortcut's batch norm is applied by its own pass (materialised) instead of inside the add;
+  cached until ops.refresh_tuning()"""
+  return ops.knob('ASM_BN_DEFER', '1') != '0'
 
 
 def _round_up(n: int, m: int) -> int:
@@ -315,6 +322,31 @@ def const_init(shape, value):
 # ---------------------------------------------------------------------------------------------------
 # activations + tape
 # ---------------------------------------------------------------------------------------------------
+class SavedBN(NamedTuple):
+  """What a ReLU-less conv + batch-norm layer without a shortcut leaves on its output Var: its pre-BN convolution output and
+  batch norm.  As Var.deferred: nobody has applied (scale, shift) yet (Var.bn_pending); the block-final layer that adds the
+  output as its shortcut applies both batch norms in one pass (ops.bn_apply_dual), any other reader just touches .data, which
+  runs the ordinary apply pass once.  As Var.bn_ctx, on a taped pass: what that block-final layer, behind one ReLU, needs to
+  run BOTH batch-norm backwards at once (ops.bn_bwd_dual)."""
+  y: torch.Tensor
+  M: int
+  C: int
+  gamma: torch.Tensor
+  mean: torch.Tensor
+  invstd: torch.Tensor
+  bn: "BatchNorm"
+  scale: torch.Tensor
+  shift: torch.Tensor
+
+
+class RedCtx(NamedTuple):
+  """What a convolution reading the output of a conv -> BN [-> + shortcut] [-> ReLU] layer needs to reduce that layer's
+  batch-norm backward sums (Var.red) while it writes the gradient: the layer's pre-BN convolution output and its packed
+  ReLU mask (None without a ReLU)."""
+  y: torch.Tensor
+  mask: Optional[torch.Tensor]
+
+
 class Var(object):
   """An activation: NHWC bf16 tensor (``data`` is None during the shape-only build walk) and the gradient accumulated for
   it so far, which only the methods below write.  The gradient is the sum of up to two terms:
@@ -331,31 +363,28 @@ class Var(object):
       produced this activation, reduced by the convolution whose input gradient wrote ``_grad`` (asm_conv2d_dgrad_bnred),
       is dropped by ANY change of the gradient's value (another term, a mask, a replacement).
   ``pre_dy``: this layer's batch-norm backward has been run by the block-final layer (ops.bn_bwd_dual); its dy waits here."""
-  __slots__ = ('_data', 'shape', '_grad', 'grad_mask', 'grad_owned', 'needs_grad', 'bn_ctx', 'red_ctx', 'red',
-               'pre_dy', 'deferred', 'pool_grad')
+  __slots__ = ('_data', 'shape', '_grad', 'grad_mask', 'grad_owned', 'needs_grad', 'deferred', 'bn_ctx', 'red_ctx', 'red',
+               'pre_dy', 'pool_grad')
 
   def __init__(self, data, shape=None, needs_grad=True):
     self._data = data
-    # A ReLU-less conv + batch-norm output whose normalisation has NOT been applied yet: (y, M, C, scale, shift).  The
-    # block-final layer that adds it as the shortcut applies both batch norms in one pass (ops.bn_apply_dual); any other
-    # reader just touches .data, which runs the ordinary apply pass once.
-    self.deferred = None
     self.shape = tuple(data.shape) if data is not None else tuple(shape)
     self.needs_grad = needs_grad
     self._grad = self.grad_mask = self.pool_grad = self.red = self.pre_dy = None
     self.grad_owned = False
-    # Set in the forward pass for the backward closures.  bn_ctx, on the output of a ReLU-less conv + batch norm: what its BN
-    # backward needs, so that the block-final layer adding it behind one ReLU can run BOTH batch-norm backwards at once.
-    # red_ctx, on the output of a conv -> BN [-> + shortcut] [-> ReLU] layer: (its pre-BN convolution output y, its packed ReLU
-    # mask or None), what a convolution reading this activation needs to reduce ``red`` while it writes the gradient.
-    self.bn_ctx = self.red_ctx = None
+    # set by conv_bn in the forward pass: SavedBN (deferred: its batch norm is left to the first reader), SavedBN, RedCtx
+    self.deferred = self.bn_ctx = self.red_ctx = None
 
   @property
   def data(self):
-    if self._data is None and self.deferred is not None:
-      y, M, Cn, scale, shift = self.deferred
-      self._data = ops.bn_apply(y, M, Cn, scale, shift, None, 0, False)
+    if self.bn_pending():
+      s = self.deferred
+      self._data = ops.bn_apply(s.y, s.M, s.C, s.scale, s.shift, None, 0, False)
     return self._data
+
+  def bn_pending(self) -> bool:
+    """a deferred batch norm that nobody has applied: no tensor yet"""
+    return self._data is None and self.deferred is not None
 
   @data.setter
   def data(self, t):
@@ -437,7 +466,7 @@ class Var(object):
     """-> the pre-reduced batch-norm backward sums if they were reduced from ``g`` (while set, ``red`` is of the whole gradient,
     unmasked) under the ReLU mask ``relu_mask``; else None.  Dropped either way."""
     red, self.red = self.red, None
-    ok = red is not None and red[1] is g and self.red_ctx is not None and self.red_ctx[1] is relu_mask
+    ok = red is not None and red[1] is g and self.red_ctx is not None and self.red_ctx.mask is relu_mask
     return red[0] if ok else None
 
   def park_dy(self, dy):
@@ -644,7 +673,7 @@ class ConvKernel(object):
   def backward_red(self, d, x: torch.Tensor, dy: torch.Tensor, need_dx: bool, addend=None, addend_mask=None, pool=None,
                    red_ctx=None):
     """backward() that also reduces the batch-norm backward sums of the layer that produced this convolution's input, in the
-    epilogue that writes dx (``red_ctx`` = that layer's (pre-BN output, ReLU mask or None), nn.Var.red_ctx) -> (dx, partials or
+    epilogue that writes dx (``red_ctx`` = that layer's RedCtx, nn.Var.red_ctx) -> (dx, partials or
     None).  Falls back to the plain input gradient (partials None) wherever the fused form does not apply."""
     a = self.arena
     self.wgrad_streamed(d, x, dy)
@@ -656,7 +685,7 @@ class ConvKernel(object):
     if self.kpad != self.cout:  # dy carries kpad channels (zero padded)
       dd = ops.make_conv_desc(d.N, d.H, d.W, d.C, self.kpad, d.R, d.S, d.stride, pad=d.pad, Ho=d.Ho, Wo=d.Wo)
     if red_ctx is not None and pool is None and ops.dgrad_bnred_ok(dd):
-      return ops.conv_dgrad_bnred(dd, dy, a.wt_view(self._wts), addend, addend_mask, red_ctx[0], red_ctx[1])
+      return ops.conv_dgrad_bnred(dd, dy, a.wt_view(self._wts), addend, addend_mask, red_ctx.y, red_ctx.mask)
     return ops.conv_dgrad(dd, dy, a.wt_view(self._wts), addend, addend_mask, pool), None
 
 
@@ -675,6 +704,46 @@ class BatchNorm(object):
     ctx.arena.register(self.beta, (c,), False, const_init((c,), 0.0))
     ctx.arena.register_state(self.mm, (c,), 0.0)
     ctx.arena.register_state(self.mv, (c,), 1.0)
+
+
+class ConvBnForm(NamedTuple):
+  """How one conv_bn layer runs, decided (conv_bn_form) before its first launch."""
+  stats: str        # 'small': the whole BN in one launch per direction | 'batch' statistics | 'moving' statistics
+  fold: bool        # inference: BN, the shortcut add and the ReLU ride in the conv epilogue (no BN pass at all)
+  apply: str        # 'none' (small) | 'dual': with the shortcut's pending BN in one pass | 'defer': left to the reader | 'own'
+  want_mask: bool   # keep the 1-bit ReLU mask for the backward kernels (16x less traffic than re-reading the output)
+  save_bn: bool     # the output carries its SavedBN as bn_ctx, for a dual backward
+  offer_red: bool   # the output offers RedCtx to the convolution reading it
+
+
+def conv_bn_form(ctx: Ctx, conv: ConvKernel, d, M: int, relu: bool, residual: Optional[Var], rm: int,
+                 tap_pre: Optional[str]) -> ConvBnForm:
+  taped, Cn = ctx.tape is not None, conv.cout
+  # [N, 1, 1, d] squeeze layers (SK / SE fc): the whole BN is one launch per direction instead of 3-4 latency-bound ones
+  small = ctx.training and residual is None and d.Ho * d.Wo == 1 and not conv.stem and ops.bn_small_ok(M)
+  stats = 'small' if small else 'batch' if ctx.training else 'moving'
+  fold = not ctx.training and tap_pre is None and not taped and rm in (0, 1) and Cn % 8 == 0
+  # a projection shortcut (or a BigLittle branch end): conv + batch norm, nothing else
+  linear = ctx.training and not small and not relu and residual is None
+  if small:
+    apply = 'none'
+  elif (residual is not None and rm == 1 and ctx.training and residual.bn_pending()
+        and residual.deferred.M == M and residual.deferred.C == Cn):
+    apply = 'dual'     # the shortcut's batch norm rides in this layer's apply pass: nobody else has asked for its output
+  elif linear and tap_pre is None and Cn % 8 == 0 and defer_bn_on():
+    apply = 'defer'
+  else:
+    apply = 'own'
+  # (not for a block-final layer whose projection shortcut's batch norm shares its backward -- bn_bwd_dual reduces both.  A
+  # taped ReLU layer that applies its batch norm here always keeps its mask, want_mask below, so the mask needs no test.)
+  offer_red = (taped and ctx.training and apply in ('dual', 'own') and Cn % 8 == 0
+               and not (residual is not None and residual.bn_ctx is not None and dual_bn_on()))
+  return ConvBnForm(stats, fold, apply, taped and relu, taped and linear, offer_red)
+
+
+def _with_mask(applied, want_mask: bool):
+  """ops.bn_apply / bn_apply_dual return (y, mask) with want_mask, else y -> (y, mask or None)"""
+  return applied if want_mask else (applied, None)
 
 
 def conv_bn(ctx: Ctx, x: Var, conv: ConvKernel, bn: BatchNorm, stride: int, relu: bool,
@@ -696,57 +765,43 @@ def conv_bn(ctx: Ctx, x: Var, conv: ConvKernel, bn: BatchNorm, stride: int, relu
   M = N * d.Ho * d.Wo
   Cn = conv.cout
   gamma, beta = a.w(bn.gamma), a.w(bn.beta)
-  taped = ctx.tape is not None
   rm = res_mode if residual is not None else 0
-  # the shortcut's batch norm rides in this layer's apply pass when nobody else has asked for its output
-  res_def = residual.deferred if (residual is not None and rm == 1 and residual._data is None and ctx.training) else None
-  res_t = residual.data if (residual is not None and res_def is None) else None
-  # [N, 1, 1, d] squeeze layers (SK / SE fc): the whole BN is one launch per direction instead of 3-4 latency-bound ones
-  small = ctx.training and residual is None and d.Ho * d.Wo == 1 and not conv.stem and ops.bn_small_ok(M)
-  mask_t = None
+  form = conv_bn_form(ctx, conv, d, M, relu, residual, rm, tap_pre)
+  small = form.stats == 'small'
+  res_t = residual.data if (residual is not None and form.apply != 'dual') else None
+  out_t = mask_t = mean = invstd = None
   if small:
     y, _ = conv.fprop(d, x.data, False)
     out_t, mask_t, mean, invstd = ops.bn_small_fwd(y, M, Cn, gamma, beta, BN_EPS, ctx.bn_momentum, a.st(bn.mm),
-                                                   a.st(bn.mv), relu, want_mask=taped)
-  elif ctx.training:
+                                                   a.st(bn.mv), relu, want_mask=form.want_mask)
+  elif form.stats == 'batch':
     y, part = conv.fprop(d, x.data, True)
     mean, invstd, scale, shift = ops.bn_finalize(part, M, Cn, gamma, beta, BN_EPS, ctx.bn_momentum,
                                                  a.st(bn.mm), a.st(bn.mv))
-  elif tap_pre is None and not taped and rm in (0, 1) and Cn % 8 == 0:
-    # inference: moving-statistics BN, the shortcut add and the ReLU ride in the conv epilogue (no BN pass at all)
+  elif form.fold:
     scale, shift = ops.bn_infer_coeffs(Cn, gamma, beta, a.st(bn.mm), a.st(bn.mv), BN_EPS)
     return Var(conv.fprop_bn(d, x.data, scale, shift, res_t if rm == 1 else None, relu))
   else:
     y, _ = conv.fprop(d, x.data, False)
     scale, shift = ops.bn_infer_coeffs(Cn, gamma, beta, a.st(bn.mm), a.st(bn.mv), BN_EPS)
-    mean = invstd = None
   if tap_pre is not None:
     ctx.taps[tap_pre] = y
-  defer = (DEFER_BN and ctx.training and not small and not relu and residual is None and tap_pre is None and Cn % 8 == 0)
-  if small:
-    pass
-  elif res_def is not None and res_def[1] == M and res_def[2] == Cn:
-    if taped and relu:
-      out_t, mask_t = ops.bn_apply_dual(y, res_def[0], M, Cn, scale, shift, res_def[3], res_def[4], True, want_mask=True)
-    else:
-      out_t, mask_t = ops.bn_apply_dual(y, res_def[0], M, Cn, scale, shift, res_def[3], res_def[4], relu), None
-  elif defer:
-    out_t = None
-  elif taped and relu:   # keep the 1-bit ReLU mask for the backward kernels (16x less traffic than re-reading out)
-    out_t, mask_t = ops.bn_apply(y, M, Cn, scale, shift, residual.data if residual is not None else None, rm, True,
-                                 d.Ho, d.Wo, want_mask=True)
-  else:
-    out_t, mask_t = ops.bn_apply(y, M, Cn, scale, shift, residual.data if residual is not None else None, rm, relu,
-                                 d.Ho, d.Wo), None
+  if form.apply == 'dual':
+    sc = residual.deferred
+    out_t, mask_t = _with_mask(ops.bn_apply_dual(y, sc.y, M, Cn, scale, shift, sc.scale, sc.shift, relu,
+                                                 want_mask=form.want_mask), form.want_mask)
+  elif form.apply == 'own':
+    out_t, mask_t = _with_mask(ops.bn_apply(y, M, Cn, scale, shift, res_t, rm, relu, d.Ho, d.Wo, want_mask=form.want_mask),
+                               form.want_mask)
   out = Var(out_t, out_shape)
-  if out_t is None:
-    out.deferred = (y, M, Cn, scale, shift)
-  if taped and ctx.training and not small and not relu and residual is None:
-    out.bn_ctx = (y, gamma, mean, invstd, bn, M, Cn)
-  # (not for a block-final layer whose projection shortcut's batch norm shares its backward -- bn_bwd_dual reduces both)
-  if (taped and ctx.training and not small and out_t is not None and Cn % 8 == 0 and (mask_t is not None or not relu)
-      and not (residual is not None and residual.bn_ctx is not None and dual_bn_on())):
-    out.red_ctx = (y, mask_t if relu else None)
+  if form.apply == 'defer' or form.save_bn:
+    saved = SavedBN(y, M, Cn, gamma, mean, invstd, bn, scale, shift)
+    if form.apply == 'defer':
+      out.deferred = saved
+    if form.save_bn:
+      out.bn_ctx = saved
+  if form.offer_red:
+    out.red_ctx = RedCtx(y, mask_t)
 
   if ctx.tape is not None:
     x_t = x.data
@@ -763,40 +818,46 @@ def conv_bn(ctx: Ctx, x: Var, conv: ConvKernel, bn: BatchNorm, stride: int, relu
       dout, in_mask = out.take_masked_grad()
       if dout is None:
         raise RuntimeError('conv_bn backward: no gradient reached this layer')
-      bmask, brelu = (mask_t if relu else None), relu
+      bmask, brelu = mask_t, relu
       if in_mask is not None:
         if relu or small or residual is not None:
-          dout, in_mask = out.grad, None                 # (never on this path's networks) materialise
+          dout = out.grad                                # (never on this path's networks) materialise
         else:
           bmask, brelu = in_mask, True
-      # Behind a ReLU the shortcut's share is dz = dout * [out > 0].  ``lazy``: dz is not written, the shortcut receives the
-      # pair (dout, mask) (res_mode 2, the BigLittle merge: its 2x2 block sum reads the pair).  ``dual``: lazy, and the shortcut
-      # is a projection's batch norm no other gradient has reached: both batch norms see the same masked gradient, so one
-      # reduce + one apply serve both and its dy is parked on it.  Otherwise the batch-norm backward apply writes dz.
-      masked = residual is not None and relu
-      lazy = masked and LAZY_DZ and mask_t is not None and (residual.needs_grad if res_mode == 1 else res_mode == 2)
-      rc = residual.bn_ctx if (lazy and res_mode == 1) else None
-      dual = (rc is not None and residual.no_grad_yet() and rc[5] == M and rc[6] == Cn and in_mask is None and dual_bn_on())
+      # The shortcut's route.  Behind a ReLU its share is dz = dout * [out > 0].  'lazy': dz is not written, the shortcut
+      # receives the pair (dout, mask) (res_mode 2, the BigLittle merge: its 2x2 block sum reads the pair).  'dual': lazy, and
+      # the shortcut is a projection's batch norm no other gradient has reached: both batch norms see the same masked
+      # gradient, so one reduce + one apply serve both and its dy is parked on it.  'dz': the batch-norm backward apply writes
+      # dz.  'dout': no ReLU, the shortcut receives the incoming gradient as it is.
+      sc = residual.bn_ctx if (residual is not None and rm == 1) else None
+      if residual is None:
+        route = 'none'
+      elif not relu:
+        route = 'dout'
+      elif not (lazy_dz_on() and (residual.needs_grad if rm == 1 else rm == 2)):
+        route = 'dz'
+      elif sc is not None and residual.no_grad_yet() and sc.M == M and sc.C == Cn and dual_bn_on():
+        route = 'dual'
+      else:
+        route = 'lazy'
       dz = None
       if small:
         dy = ops.bn_small_bwd(dout, y, bmask, M, Cn, gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta))
-      elif dual:
-        dy, dy_sc = ops.bn_bwd_dual(dout, y, rc[0], mask_t, M, Cn,
+      elif route == 'dual':
+        dy, dy_sc = ops.bn_bwd_dual(dout, y, sc.y, mask_t, M, Cn,
                                     (gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta)),
-                                    (rc[1], rc[2], rc[3], a.g(rc[4].gamma), a.g(rc[4].beta)))
+                                    (sc.gamma, sc.mean, sc.invstd, a.g(sc.bn.gamma), a.g(sc.bn.beta)))
         residual.park_dy(dy_sc)
       else:
         # the input gradient that wrote dout may have reduced (sum dz, sum dz * y) already (Var.red)
         dy, dz = ops.bn_bwd(dout, y, bmask, brelu, M, Cn, gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta),
-                            masked and not lazy, raw_part=out.take_red(dout, bmask))
+                            route == 'dz', raw_part=out.take_red(dout, bmask))
       a.notify_grad(bn.gamma)
-      if residual is not None and not dual:
-        if res_mode == 2:
-          accum_grad(residual, ops.upsample2x_bwd(dout, mask_t) if lazy else ops.upsample2x_bwd(dz if relu else dout), True)
-        elif lazy:
-          accum_grad(residual, dout, False, mask=mask_t)
-        else:
-          accum_grad(residual, dz if relu else dout, relu)
+      if route in ('lazy', 'dz', 'dout'):
+        g, g_mask, owned = (dout, mask_t, False) if route == 'lazy' else (dz, None, True) if route == 'dz' else (dout, None, False)
+        if rm == 2:                    # the BigLittle merge: the 2x2 block sum reads the pair itself
+          g, g_mask, owned = ops.upsample2x_bwd(g, g_mask), None, True
+        accum_grad(residual, g, owned, mask=g_mask)
       conv_input_grad(conv, d, x, x_t, dy)
       out.grad = None
     bwd.relu_mask = mask_t          # by name for the test harness, which teacher-forces the saved ReLU decisions

@@ -593,7 +593,7 @@ def check_teacher_forced_backward(name, device, batch, size, label_smoothing=0.1
       if not conv.stem:
         xv._data = to_dev(ref_in)
       ref_out, ref_res = rec_bn[bn.gamma]
-      if residual is not None and not (residual._data is None and residual.deferred is not None):
+      if residual is not None and not residual.bn_pending():
         residual._data = to_dev(ref_res)
       ref_y = rec_extra.get('conv_out:' + conv.name) if ref_out.shape[2] * ref_out.shape[3] == 1 else None
       if ref_y is not None:

@@ -11,13 +11,11 @@ from tests import util
 
 
 def _run(monkeypatch, fused: bool, name='a-r50-d', batch=2, size=64, gatherable=True):
-  from assembled_cnn_amd import nn, ops
+  from assembled_cnn_amd import ops
   if not gatherable:      # the pooled gradient stays pending until somebody reads .grad, which scatters it
     monkeypatch.setattr(ops, 'dgrad_pool_ok', lambda d: False)
-  for k in ('ASM_POOL_FUSE', 'ASM_BN_DUAL', 'ASM_DENSE_SMALL', 'ASM_SK_FUSED', 'ASM_BN_RED'):
+  for k in ('ASM_POOL_FUSE', 'ASM_BN_DUAL', 'ASM_DENSE_SMALL', 'ASM_SK_FUSED', 'ASM_BN_RED', 'ASM_LAZY_DZ', 'ASM_BN_DEFER'):
     util.set_knob(monkeypatch, k, '1' if fused else '0')
-  monkeypatch.setattr(nn, 'DEFER_BN', fused)
-  monkeypatch.setattr(nn, 'LAZY_DZ', fused)
   _, pm = MP.make_pair(name, 'cpu', batch, size)
   _, x, _ = MP.inputs(batch, size)
   lp = pm(x, True, use_resnet_d=MP.uses_d(name))

@@ -89,11 +89,13 @@ def test_teacher_forced_backward_per_layer_parity(hip_lib, name, batch, size):
 
 
 @pytest.mark.parametrize('env', [{'ASM_BN_DUAL': '0'}, {'ASM_POOL_FUSE': '0'}, {'ASM_SK_FUSED': '0'},
-                                 {'ASM_WGRAD_STREAM': '0', 'ASM_BL_STREAMS': '0'}])
+                                 {'ASM_WGRAD_STREAM': '0', 'ASM_BL_STREAMS': '0'}, {'ASM_BN_DEFER': '0'}, {'ASM_LAZY_DZ': '0'}])
 def test_teacher_forced_backward_with_a_fusion_switched_off(hip_lib, env):
   """the same per-layer backward check with one fusion replaced by its plain path: ASM_BN_DUAL=0 leaves the projection
   shortcut's gradient lazily masked (compared in that form), ASM_POOL_FUSE=0 scatters the pooled gradient in its own
-  pass, ASM_SK_FUSED=0 runs the materialising SK unit, and one run keeps everything on ONE stream"""
+  pass, ASM_SK_FUSED=0 runs the materialising SK unit, one run keeps everything on ONE stream, ASM_BN_DEFER=0 applies a
+  projection shortcut's batch norm in a pass of its own, and ASM_LAZY_DZ=0 has the batch-norm backward write the masked
+  shortcut gradient dz"""
   errs, st = mp.check_teacher_forced_backward('a-r50-d', 'cuda', 8, 64, env=env)
   if 'ASM_BN_DUAL' in env:
     assert st['kinds']['dout-lazy'] >= 4, st
