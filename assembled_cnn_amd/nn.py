@@ -1197,6 +1197,10 @@ class DropBlockState(object):
       else:
         u.uniform_(0.0, 1.0, generator=self._rng)
 
+  def rewind(self):
+    """before a walk over buffers that begin() has already prepared (a step being recorded)"""
+    self._i = 0
+
   def slot(self, shape, gamma_scale: float, H: int, W: int):
     """the walk reaches its next DropBlock call: (uniform buffer, gamma slot [1])"""
     i = self._i

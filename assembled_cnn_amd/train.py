@@ -11,7 +11,9 @@
 """
 from __future__ import annotations
 
+import ctypes
 import math
+import os
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional
 
@@ -162,12 +164,96 @@ def lr_fn_from_hparams(p: HParams) -> Callable[[int], float]:
                                   warmup_epochs=p.lr_warmup_epochs, train_epochs=p.train_epochs)
 
 
+def _compare_tape_with_graph(g, tape):
+  """A tape replay issues what the LIBRARY launched while the step was captured.  A framework kernel inside the
+  recorded region (a .contiguous(), a cast, a concatenation) is in the captured HIP graph but not on the tape: every
+  replay would silently skip it.  Count the graph's kernel and copy / fill nodes through the HIP runtime and compare:
+  the node count (an int) if they agree, a RuntimeError if not, the reason (a str) if the graph cannot be counted."""
+  info = ops.tape_info(tape)
+  try:
+    # the runtime torch itself has mapped: RTLD_NOLOAD fails rather than load a second runtime instance (CDLL(None) does
+    # not see it: torch loads it RTLD_LOCAL)
+    hip = ctypes.CDLL(os.path.join(os.path.dirname(torch.__file__), 'lib', 'libamdhip64.so'),
+                      mode=os.RTLD_NOLOAD | os.RTLD_NOW)
+    get_nodes, get_type = hip.hipGraphGetNodes, hip.hipGraphNodeGetType
+    raw = ctypes.c_void_p(g.raw_cuda_graph())
+  except (AttributeError, OSError, RuntimeError) as e:
+    return repr(e)                                # this torch / runtime does not expose the raw graph
+  n = ctypes.c_size_t(0)
+  rc = get_nodes(raw, None, ctypes.byref(n))
+  nodes = (ctypes.c_void_p * n.value)()
+  rc = rc or get_nodes(raw, nodes, ctypes.byref(n))
+  if rc != 0:
+    return 'hipGraphGetNodes: error %d' % rc
+  kernels = copies = 0
+  for h in nodes[:n.value]:
+    ty = ctypes.c_int(-1)
+    rc = get_type(ctypes.c_void_p(h), ctypes.byref(ty))
+    if rc != 0:
+      return 'hipGraphNodeGetType: error %d' % rc
+    kernels += ty.value == 0                      # hipGraphNodeTypeKernel
+    copies += ty.value in (1, 2)                  # hipGraphNodeTypeMemcpy, hipGraphNodeTypeMemset
+  # (compared as one total: whether the runtime keeps a device-to-device copy as a copy node or as a blit kernel is its business)
+  if kernels + copies != info['launches'] + info['fills']:
+    raise RuntimeError('the captured step holds %d kernels and %d copies, the launch tape %d and %d: a framework kernel '
+                       'ran inside the recorded region and would be missing from every replay'
+                       % (kernels, copies, info['launches'], info['fills']))
+  return kernels + copies
+
+
+@dataclass
+class Recording(object):
+  """A captured step (Trainer.capture): everything that exists only while one is held."""
+  graph: object = None      # the captured HIP graph: replayed (replay='graph') or only kept for its memory pool
+  tape: object = None       # the library's launch tape (None: replay='graph')
+  static: tuple = ()        # the static input buffers: images, hard labels, teacher logits, lam1, lam2 (None where unused)
+  out: tuple = None         # (loss_rows, loss_scale, keep_prob) as recorded
+  stream: object = None     # the stream it was recorded on and is replayed on
+  sig: tuple = None         # Trainer._signature of the inputs it was captured with
+  baked: tuple = None       # Trainer._baked_state() at capture time
+  own: bool = False         # made by the trainer's self-recording (which may drop it), not by a caller's capture()
+  checked: object = None    # tape against graph: the node count compared (int), or why nothing was compared (str)
+
+  def fit(self, *inputs):
+    """(images, hard, tlogits, lam1, lam2) of a step: refused unless they are what the static buffers were made from"""
+    for dst, src in zip(self.static, inputs):
+      if (dst is None) != (src is None) or (dst is not None and (dst.shape != src.shape or dst.dtype != src.dtype)):
+        raise ValueError('the captured step takes inputs of the shapes / dtypes it was captured with')
+
+  def load(self, *inputs):
+    """the same five, having passed fit(), into the static buffers (on the current stream)"""
+    for dst, src in zip(self.static, inputs):
+      if dst is not None and dst.data_ptr() != src.data_ptr():
+        dst.copy_(src, non_blocking=True)
+
+  def replay(self, grad_sync):
+    gs = grad_sync
+    if self.tape is not None and gs is not None:
+      try:
+        for k in range(len(gs.recorded)):   # segment k, then the bucket that became ready at its end goes to RCCL
+          ops.tape_replay(self.tape, k)
+          gs.launch_recorded(k)
+        ops.tape_replay(self.tape, len(gs.recorded))
+      except BaseException:
+        gs.abort()        # half a step's buckets are with the collective library: wait for them, forget the watermark
+        raise
+    elif self.tape is not None:
+      ops.tape_replay(self.tape)       # (the recording ends with its side streams joined into the capture stream)
+    else:
+      self.graph.replay()
+
+  def free(self):
+    if self.tape is not None:
+      torch.cuda.synchronize()
+      ops.tape_free(self.tape)
+      self.tape = None
+
+
 class Trainer(object):
   """Holds the model + optimiser state and runs training steps.  ``grad_sync`` (see dp.py) is called
   between backward and the optimiser with the flat fp32 gradient arena."""
 
   AUTO_WARMUP = 3      # eager steps of one input signature before train_step records itself
-  tape_check_skipped = None   # why the last capture could not compare its tape with the captured graph (None: it was compared)
 
   def __init__(self, hparams: HParams, seed: int = 0, device='cuda', grad_sync=None, world_size: int = 1,
                recorded: Optional[bool] = None):
@@ -184,17 +270,15 @@ class Trainer(object):
     self.grad_sync = grad_sync
     self.world_size = world_size
     self.last = {}
-    self._graph = self._static = self._graph_out = None
-    self._tape = self._cap_stream = None
+    self._rec: Optional[Recording] = None    # the captured step, if there is one
     # the stream a captured step is recorded and replayed on: taken from the pool BEFORE the model takes its side streams
     dev = torch.device(device)
     self._step_stream = torch.cuda.Stream(device=dev) if dev.type == 'cuda' else None
     self.recorded = recorded
     self._auto = dev.type == 'cuda' and recorded is not False and ops.knob('ASM_STEP_TAPE', '1') != '0'
-    self._auto_sig, self._auto_n, self._auto_made = None, 0, False
+    self._auto_sig, self._auto_n = None, 0
+    self._auto_error = None                  # why the trainer's own recording failed (it stays eager)
     self._capturing = False
-    self._baked = None
-    self.step_mode = 'eager'                 # 'eager' | 'recorded' | 'eager (recording failed: ...)'
     # DropBlock with its draws and gamma in static device buffers (nn.DropBlockState): what lets the published recipe
     # (scripts/train_assemble_from_scratch.sh: --use_dropblock=True) run as a recorded step
     # (on the CPU test double only on request: recorded=True, for the host-logic tests)
@@ -208,6 +292,22 @@ class Trainer(object):
     the fastest arrangement measured (see _replay)."""
     return self._step_stream
 
+  @property
+  def step_mode(self):
+    """'recorded' | 'eager' | 'eager (recording failed: ...)'"""
+    failed = ' (recording failed: %s)' % self._auto_error if self._auto_error else ''
+    return 'recorded' if self._rec is not None else 'eager' + failed
+
+  _tape = property(lambda self: self._rec.tape if self._rec is not None else None)
+  _graph = property(lambda self: self._rec.graph if self._rec is not None else None)
+
+  def _drop_stale(self, why):
+    """THE rule for a recording that no longer fits what the trainer is asked to do: the trainer's own is dropped (eager
+    again; the next AUTO_WARMUP eager steps record again), a caller's capture() is the caller's to release."""
+    if not self._rec.own:
+      raise RuntimeError(why)
+    self.release_graph()
+
   # -----------------------------------------------------------------------------------------------
   def set_streams(self, on: bool, fresh: bool = False):
     """Side streams on (the default: weight gradients on two streams beside the input-gradient chain, the big branch of
@@ -215,10 +315,8 @@ class Trainer(object):
     either way (tests/test_gpu_model.py); only the overlap changes.  Switching off parks the stream objects and switching
     on again reuses them; ``fresh`` creates new ones instead.  The setting belongs to this trainer's model (the process-wide
     ASM_WGRAD_STREAM / ASM_BL_STREAMS switches are only the default) and cannot change under a recorded step."""
-    if self._graph is not None:
-      if not self._auto_made:
-        raise RuntimeError('the stream setting is frozen into the captured step: release_graph() first')
-      self.release_graph()                 # the trainer's own recording: drop it, the next steps record again
+    if self._rec is not None:
+      self._drop_stale('the stream setting is frozen into the captured step: release_graph() first')
     self.model.side_streams = bool(on)     # this model only: no other Trainer / Model of the process changes
     a = self.model.arena
     if a.finalized:
@@ -262,13 +360,10 @@ class Trainer(object):
       return round(1000.0 * (time.time() - t0) / steps, 3)
 
     # The steps timed here must be EAGER ones: a trainer that records itself (the default on a GPU) would reach AUTO_WARMUP
-    # inside the timed window and time a capture instead.  Self-recording is suspended for the duration and
-    # the trainer's own recording, if any, dropped; a caller-made capture() is frozen with its stream setting (set_streams
-    # raises, as before).
+    # inside the timed window and time a capture instead.  Self-recording is suspended for the duration;
+    # the first set_streams below drops the trainer's own recording, if any, and refuses a caller-made capture().
     auto = self._auto
     self._auto = False
-    if self._graph is not None and self._auto_made:
-      self.release_graph()
     try:
       res = {'side_streams_ms': timed(True), 'single_stream_ms': timed(False), 'redraws': 0}
       keep = res['side_streams_ms'] <= res['single_stream_ms'] * (1.0 + margin)
@@ -280,7 +375,7 @@ class Trainer(object):
     finally:
       self._auto = auto
       self._auto_n = 0
-    if self._graph is not None:
+    if self._rec is not None:
       raise RuntimeError('calibrate_streams: a step was recorded while eager steps were being timed')
     res['chosen'] = 'side streams' if keep else 'single stream'
     return res
@@ -357,21 +452,17 @@ class Trainer(object):
     """One optimisation step.  A recorded step (capture(), or the trainer's own recording after AUTO_WARMUP eager steps) is
     replayed; ``dropblock_uniforms`` (tests: the draws of every DropBlock call in creation order) go into the static
     draw buffers of a recorded step, or straight to the layers of an eager one."""
-    if self._graph is not None and self._baked_state() != self._baked:
-      if not self._auto_made:
-        raise RuntimeError('grad_sync or a by-value hyper-parameter (loss scale, label smoothing, KD temperature, weight '
-                           'decay, momentum, mixup type) changed after capture(): release_graph() and capture again')
-      self.release_graph()                 # the trainer's own recording: drop it, the eager steps below record again
-    if self._graph is not None:
-      if self._auto_made and self._signature(images, labels, lam1, lam2) != self._auto_sig:
-        self.release_graph()               # other shapes: back to the eager step, which records itself again
-      elif dropblock_uniforms is not None and self._db is None:
-        pass                               # a step captured without DropBlock state: run this one eagerly
-      else:
-        return self._replay(images, labels, lam1, lam2, lr, dropblock_uniforms)
+    if self._rec is not None and self._baked_state() != self._rec.baked:
+      self._drop_stale('grad_sync or a by-value hyper-parameter (loss scale, label smoothing, KD temperature, weight '
+                       'decay, momentum, mixup type) changed after capture(): release_graph() and capture again')
+    if self._rec is not None and self._rec.own and self._signature(images, labels, lam1, lam2) != self._rec.sig:
+      self._drop_stale('other shapes')     # (a caller's capture() with other shapes: Recording.fit refuses them in _replay)
+    # (draws for a step that was captured without DropBlock state: that step runs eagerly)
+    if self._rec is not None and not (dropblock_uniforms is not None and self._db is None):
+      return self._replay(images, labels, lam1, lam2, lr, dropblock_uniforms)
     loss_rows, loss_scale, keep_prob = self._forward_backward(images, labels, lam1, lam2, dropblock_uniforms)
     out = self._apply(loss_rows, loss_scale, keep_prob, lr)
-    if self._auto and self._graph is None and not self._capturing:
+    if self._auto and self._rec is None and not self._capturing:
       self._auto_step(images, labels, lam1, lam2)
     return out
 
@@ -392,13 +483,13 @@ class Trainer(object):
       return
     try:
       self.capture(images, labels, lam1, lam2, warmup=0)
-      self._auto_made = True
+      self._rec.own = True
     except Exception as e:                 # loud, once: the trainer stays eager
       if self.recorded is True:
         raise
       import warnings
       self._auto = False
-      self.step_mode = 'eager (recording failed: %s)' % (str(e).splitlines()[0][:200] if str(e) else type(e).__name__)
+      self._auto_error = str(e).splitlines()[0][:200] if str(e) else type(e).__name__
       warnings.warn('assembled_cnn_amd.Trainer: recording the training step failed, staying with the eager step '
                     '(14 ms of host time per step instead of 3): %r' % (e,), RuntimeWarning)
 
@@ -417,7 +508,7 @@ class Trainer(object):
     if db is not None and not db_prepared:
       db.begin(keep_prob, dropblock_uniforms, self._db_rng())
     elif db is not None:
-      db._i = 0
+      db.rewind()
     x, onehot, teacher = self._prepare(images, hard, tlogits, lam1, lam2)
     B = x.shape[0]
     m(x, True, use_resnet_d=p.use_resnet_d, prepadded=True, keep_prob=keep_prob,
@@ -470,11 +561,9 @@ class Trainer(object):
               replay: str = 'tape'):
     """Record inputs -> forward -> loss -> backward (every launch of it, side streams included) over static input buffers;
     train_step then copies its arguments into those buffers, replays the recording with ONE host call instead of ~930
-    launches' worth of Python, and runs the exchange + optimiser as usual (their learning rate is a host scalar).
-
-    Why: the eager step enqueues in 14 - 15 ms of host time against 25 ms of GPU time.  On a busy host -- the GPU boxes this
-    was developed on are shared: 256 hardware threads, load averages of 40 - 65 -- that head-room goes: with one competitor
-    on the Python thread's core the step is host-bound at 30 ms, with two at 48 (tools/debug/host_contention.sh).
+    launches' worth of Python, and runs the exchange + optimiser as usual (their learning rate is a host scalar).  Why: the
+    eager step enqueues in 14 - 15 ms of host time against 25 ms of GPU time, head-room a busy host takes away (the figures:
+    calibrate_streams).
 
     ``replay='tape'`` (default): the library writes the launches down while they are captured (csrc/tape.hip) and
     ``asm_tape_replay`` issues them again through hipLaunchKernel on the recorded streams: ~2 - 3 ms of host time per step.
@@ -486,16 +575,25 @@ class Trainer(object):
     Both replays are bit-identical to the eager step (tests/test_gpu_model.py).  DropBlock (the published recipe,
     scripts/train_assemble_from_scratch.sh:22) is recorded with its draws and its gamma in static device buffers that
     every replay rewrites first (nn.DropBlockState).  KD labels are split into their two halves OUTSIDE the recording
-    (split_labels: framework slices) and everything behind the split is library launches.  The recording is checked
-    against the captured HIP graph: the graph must hold exactly the kernels and copies the tape wrote down -- a framework
-    kernel that slipped into the recorded region would be in the graph only, i.e. silently missing from every replay.
-    With a gradient exchange attached (dp.GradSync) only the tape works: the
-    bucket launches the host interleaves with the backward pass become segment boundaries of the tape, and the replayed
-    step hands bucket k to RCCL after segment k (tests/test_gpu_dp_rccl.py).  ``warmup`` real training steps run first
-    (one-time initialisation must not be recorded).
-    Every activation of a step stays allocated until release_graph(); ``capture_error_mode='thread_local'`` if other
-    threads (an input pipeline) touch the device while capturing.  ASM_* switches are frozen into the recording."""
-    if self._graph is not None:
+    (split_labels: framework slices) and everything behind the split is library launches, which the recording is checked
+    for (_compare_tape_with_graph).  With a gradient exchange attached (dp.GradSync) only the tape works: the bucket
+    launches the host interleaves with the backward pass become segment boundaries of the tape, and the replayed step hands
+    bucket k to RCCL after segment k (tests/test_gpu_dp_rccl.py).  ``warmup`` real training steps run first (one-time
+    initialisation must not be recorded).  Every activation of a step stays allocated until release_graph();
+    ``capture_error_mode='thread_local'`` if other threads (an input pipeline) touch the device while capturing.  ASM_*
+    switches are frozen into the recording."""
+    self._refuse_capture(images, replay)
+    hard, tlogits = self.split_labels(labels)    # framework kernels (cast / column slices): not part of the recorded step
+    static = [t.clone() if t is not None else None for t in (images, hard, tlogits, lam1, lam2)]
+    sig = self._signature(images, labels, lam1, lam2)
+    cap = self._capture_stream(images.device)
+    self._warm_up(cap, warmup, images, labels, lam1, lam2)
+    g, tape, out, checked = self._record(static, cap, replay, capture_error_mode)
+    self._rec = Recording(g, tape, static, out, cap, sig, self._baked_state(), checked=checked)
+    return self
+
+  def _refuse_capture(self, images, replay):
+    if self._rec is not None:
       raise RuntimeError('a step is already captured: release_graph() first')
     if replay not in ('tape', 'graph'):
       raise ValueError("replay must be 'tape' or 'graph'")
@@ -509,29 +607,31 @@ class Trainer(object):
       raise NotImplementedError('capture needs a dp.GradSync as the gradient exchange (segmented replay)')
     if not images.is_cuda:
       raise RuntimeError('capture needs device tensors')
-    hard, tlogits = self.split_labels(labels)    # framework kernels (cast / column slices): not part of the recorded step
-    static = [t.clone() if t is not None else None for t in (images, hard, tlogits, lam1, lam2)]
-    sig = self._signature(images, labels, lam1, lam2)
-    cur = torch.cuda.current_stream(images.device)
-    if cur != torch.cuda.default_stream(images.device):
-      cap = cur           # already on a stream of the caller's: record there (a capture cannot run on the default stream)
-    elif self._step_stream is not None:
-      cap = self._step_stream
-    else:
-      cap = torch.cuda.Stream(device=images.device)
-    if cap != cur:
-      ops.stream_join(cap, cur)
+
+  def _capture_stream(self, device):
+    """the stream to record on, behind everything the caller's stream holds so far"""
+    cur = torch.cuda.current_stream(device)
+    if cur != torch.cuda.default_stream(device):
+      return cur          # already on a stream of the caller's: record there (a capture cannot run on the default stream)
+    cap = self._step_stream if self._step_stream is not None else torch.cuda.Stream(device=device)
+    ops.stream_join(cap, cur)
+    return cap
+
+  def _warm_up(self, cap, warmup, *inputs):
+    """one-time initialisation (workspaces, kernel attributes, side streams) stays out of the recording"""
     with torch.cuda.stream(cap):
-      self._capturing = True      # the warm-up steps below must not start a recording of their own
+      self._capturing = True      # the warm-up steps must not start a recording of their own
       try:
-        for _ in range(warmup):   # one-time initialisation (workspaces, kernel attributes, side streams) stays out of the recording
-          self.train_step(images, labels, lam1, lam2)
+        for _ in range(warmup):
+          self.train_step(*inputs)
       finally:
         self._capturing = False
-      if self._db is not None:
-        if not self._db.known:
-          raise RuntimeError('capture with DropBlock needs one eager step first (warmup >= 1): it discovers the DropBlock calls')
+      if self._db is not None and not self._db.known:
+        raise RuntimeError('capture with DropBlock needs one eager step first (warmup >= 1): it discovers the DropBlock calls')
     torch.cuda.synchronize()
+
+  def _record(self, static, cap, replay, capture_error_mode):
+    """the recorded region and its checks: (graph, tape or None, recorded outputs, outcome of the tape-vs-graph check)"""
     # tape replay never launches the captured graph: it is not even instantiated (keep_graph), only kept for its memory pool
     g = torch.cuda.CUDAGraph(keep_graph=(replay == 'tape'))
     tape = None
@@ -553,55 +653,18 @@ class Trainer(object):
             ops.tape_end()
       if gs is not None and ops.tape_info(tape)['segments'] != len(gs.recorded) + 1:
         raise RuntimeError('tape segments and recorded bucket launches disagree')
-      if tape is not None:
-        self._check_tape_against_graph(g, tape)
+      checked = _compare_tape_with_graph(g, tape) if tape is not None else "replay='graph': there is no tape"
     except BaseException:
       if tape is not None:        # a recording that failed half-way is dropped, the trainer stays eager
         ops.tape_free(tape)
       raise
-    self._graph, self._static, self._graph_out = g, static, out
-    self._tape, self._cap_stream = tape, cap
-    self._auto_sig, self._auto_made = sig, False
-    self._baked = self._baked_state()
-    self.step_mode = 'recorded'
-    return self
+    return g, tape, out, checked
 
   @staticmethod
   def _check_tape_against_graph(g, tape):
-    """A tape replay issues what the LIBRARY launched while the step was captured.  A framework kernel inside the
-    recorded region (a .contiguous(), a cast, a concatenation) is in the captured HIP graph but not on the tape: every
-    replay would silently skip it.  Count the graph's kernel and copy / fill nodes through the HIP runtime and compare."""
-    info = ops.tape_info(tape)
-    try:
-      import ctypes
-      raw = g.raw_cuda_graph()
-      # the runtime torch itself is linked against (already loaded: resolve the symbols from the process image, never
-      # dlopen a second libamdhip64 by name -- a system copy would be another runtime instance)
-      hip = ctypes.CDLL(None)
-      hip.hipGraphGetNodes.restype = ctypes.c_int
-      hip.hipGraphNodeGetType.restype = ctypes.c_int
-      n = ctypes.c_size_t(0)
-      if hip.hipGraphGetNodes(ctypes.c_void_p(raw), None, ctypes.byref(n)) != 0:
-        return None
-      nodes = (ctypes.c_void_p * n.value)()
-      if hip.hipGraphGetNodes(ctypes.c_void_p(raw), nodes, ctypes.byref(n)) != 0:
-        return None
-      kernels = copies = 0
-      for h in nodes[:n.value]:
-        ty = ctypes.c_int(-1)
-        if hip.hipGraphNodeGetType(ctypes.c_void_p(h), ctypes.byref(ty)) != 0:
-          return None
-        kernels += ty.value == 0                  # hipGraphNodeTypeKernel
-        copies += ty.value in (1, 2)              # hipGraphNodeTypeMemcpy, hipGraphNodeTypeMemset
-    except (AttributeError, OSError, RuntimeError) as e:
-      Trainer.tape_check_skipped = repr(e)        # this torch / runtime does not expose the raw graph: nothing to compare with
-      return None
-    # (compared as one total: whether the runtime keeps a device-to-device copy as a copy node or as a blit kernel is its business)
-    if kernels + copies != info['launches'] + info['fills']:
-      raise RuntimeError('the captured step holds %d kernels and %d copies, the launch tape %d and %d: a framework kernel '
-                         'ran inside the recorded region and would be missing from every replay'
-                         % (kernels, copies, info['launches'], info['fills']))
-    return kernels + copies
+    """_compare_tape_with_graph for a caller that only wants the count: None where nothing could be compared"""
+    seen = _compare_tape_with_graph(g, tape)
+    return seen if isinstance(seen, int) else None
 
   def _baked_state(self):
     """what a recording holds BY VALUE: the gradient exchange it was recorded with and the hyper-parameters that reach the
@@ -611,53 +674,32 @@ class Trainer(object):
             float(p.momentum), int(p.mixup_type))
 
   def release_graph(self):
-    if getattr(self, '_tape', None) is not None:
-      torch.cuda.synchronize()
-      ops.tape_free(self._tape)
-    self._graph = self._static = self._graph_out = None
-    self._tape = self._cap_stream = None
-    self._auto_made = False
+    if self._rec is not None:
+      self._rec.free()
+    self._rec = None
     self._auto_n = 0
-    self.step_mode = 'eager'
+    self._auto_error = None
 
   def _replay(self, images, labels, lam1, lam2, lr, dropblock_uniforms=None):
-    srcs = []
-    hard, tlogits = self.split_labels(labels)
-    for dst, src in zip(self._static, (images, hard, tlogits, lam1, lam2)):
-      if (dst is None) != (src is None) or (dst is not None and (dst.shape != src.shape or dst.dtype != src.dtype)):
-        raise ValueError('the captured step takes inputs of the shapes / dtypes it was captured with')
-      srcs.append(src)
+    rec = self._rec
+    inputs = (images,) + self.split_labels(labels) + (lam1, lam2)
+    rec.fit(*inputs)
     # The whole step -- input copies, the recording, the optimiser -- runs on the stream the recording was made on, between
     # two joins with the caller's stream.  Measured (same box, ms per step): everything on that one stream 25.08; recording
     # on it but input copies and optimiser on the default stream 26.2 - 26.5 (the eager step: 25.3 on the default stream,
     # 25.7 - 26.0 on another).
     cur = torch.cuda.current_stream()
-    cap = self._cap_stream
+    cap = rec.stream
     same = cap == cur
     if not same:
       ops.stream_join(cap, cur)
       torch.cuda.set_stream(cap)
     try:
-      for dst, src in zip(self._static, srcs):
-        if dst is not None and dst.data_ptr() != src.data_ptr():
-          dst.copy_(src, non_blocking=True)
+      rec.load(*inputs)
       if self._db is not None:      # this step's keep_prob (gamma) and draws into the static DropBlock buffers
         self._db.begin(self.keep_prob_fn(self.global_step), dropblock_uniforms, self._db_rng())
-      gs = self.grad_sync
-      if self._tape is not None and gs is not None:
-        try:
-          for k in range(len(gs.recorded)):   # segment k, then the bucket that became ready at its end goes to RCCL
-            ops.tape_replay(self._tape, k)
-            gs.launch_recorded(k)
-          ops.tape_replay(self._tape, len(gs.recorded))
-        except BaseException:
-          gs.abort()        # half a step's buckets are with the collective library: wait for them, forget the watermark
-          raise
-      elif self._tape is not None:
-        ops.tape_replay(self._tape)       # (the recording ends with its side streams joined into the capture stream)
-      else:
-        self._graph.replay()
-      loss_rows, loss_scale, keep_prob = self._graph_out
+      rec.replay(self.grad_sync)
+      loss_rows, loss_scale, keep_prob = rec.out
       if self.keep_prob_fn is not None:
         keep_prob = self.keep_prob_fn(self.global_step)
       out = self._apply(loss_rows, loss_scale, keep_prob, lr)

@@ -237,13 +237,53 @@ def test_kd_input_side_is_library_calls_only(cpu_double, monkeypatch):
     assert torch.allclose(onehot, oy, atol=1e-6) and torch.allclose(teacher, ot, atol=1e-6)
 
 
+def test_a_stale_recording_is_dropped_if_the_trainers_own_and_refused_if_the_callers(cpu_double):
+  """Trainer._drop_stale, the one rule for a recording that no longer fits: the stream setting changes, a hyper-parameter
+  the recording holds by value changes, the inputs have another batch size.  The trainer's own recording is dropped, the
+  trainer is eager again and the step runs; a caller's capture() is the caller's to release: the documented RuntimeError
+  (the shapes: Recording.fit's ValueError) and the recording stays.  On a stub Recording: nothing here needs a capture."""
+  from assembled_cnn_amd.train import HParams, Recording, Trainer
+  img2, _, lab2 = MP.inputs(2, 64)
+  img4, _, lab4 = MP.inputs(4, 64)
+
+  def streams(tr):
+    tr.set_streams(False)
+
+  def smoothing(tr):
+    tr.p.label_smoothing = 0.1
+    tr.train_step(img2, lab2)
+
+  def batch(tr):
+    tr.train_step(img4, lab4)
+
+  table = [(streams, 0, RuntimeError, r'release_graph\(\) first'),
+           (smoothing, 1, RuntimeError, r'by-value hyper-parameter .* changed after capture\(\): release_graph\(\)'),
+           (batch, 1, ValueError, 'shapes / dtypes it was captured with')]
+  for trigger, steps_taken, error, text in table:
+    for own in (True, False):
+      tr = Trainer(HParams(resnet_version=1, batch_size=2, learning_rate_decay_type='fixed', base_learning_rate=0.01),
+                   seed=0, device='cpu')
+      tr._rec = Recording(static=(img2.clone(), lab2.to(torch.int32), None, None, None),
+                          sig=tr._signature(img2, lab2, None, None), baked=tr._baked_state(), own=own)
+      assert tr.step_mode == 'recorded'
+      if own:
+        trigger(tr)
+        assert tr._rec is None and tr.step_mode == 'eager' and tr.global_step == steps_taken, trigger.__name__
+        tr.train_step(img2, lab2)
+        assert tr.global_step == steps_taken + 1 and tr.step_mode == 'eager'
+      else:
+        with pytest.raises(error, match=text):
+          trigger(tr)
+        assert tr._rec is not None and tr.step_mode == 'recorded' and tr.global_step == 0, trigger.__name__
+
+
 def test_self_recording_bookkeeping_without_a_gpu(cpu_double, monkeypatch):
   """Trainer.train_step's own recording (train.Trainer._auto_step) with capture() replaced by a counter: it fires after
   AUTO_WARMUP eager steps of ONE input signature, starts counting again when the shapes change, is never attempted with a
   gradient exchange that cannot replay bucket launches, and a failing capture leaves an eager trainer with ONE warning
   (recorded=True: the exception)."""
   import warnings
-  from assembled_cnn_amd.train import HParams, Trainer
+  from assembled_cnn_amd.train import HParams, Recording, Trainer
   hp = HParams(resnet_version=1, batch_size=2, learning_rate_decay_type='fixed', base_learning_rate=0.01)
   img2, _, lab2 = MP.inputs(2, 64)
   img4, _, lab4 = MP.inputs(4, 64)
@@ -259,20 +299,26 @@ def test_self_recording_bookkeeping_without_a_gpu(cpu_double, monkeypatch):
   # the step itself runs on the CPU double; only the bookkeeping is driven with device-flagged tensors
   tr = Trainer(hp, seed=0, device='cpu')
   calls = []
-  monkeypatch.setattr(tr, 'capture', lambda *a, **k: calls.append(tuple(a[0].shape)) or tr)
+
+  def counted(*a, **k):            # what capture() leaves behind: a recording that is not (yet) the trainer's own
+    calls.append(tuple(a[0].shape))
+    tr._rec = Recording()
+    return tr
+  monkeypatch.setattr(tr, 'capture', counted)
   tr._auto = True
   n = Trainer.AUTO_WARMUP
   for i in range(n):
     tr._auto_step(FakeCuda(img2), lab2, None, None)
-  assert calls == [tuple(img2.shape)] and tr._auto_made
-  tr._auto_made = False
+  assert calls == [tuple(img2.shape)] and tr._rec.own
+  tr._rec = None
   for i in range(n - 1):
     tr._auto_step(FakeCuda(img4), lab4, None, None)
   tr._auto_step(FakeCuda(img2), lab2, None, None)          # the signature changed again: the count starts over
   assert len(calls) == 1
   for i in range(n - 1):
     tr._auto_step(FakeCuda(img2), lab2, None, None)
-  assert len(calls) == 2
+  assert len(calls) == 2 and tr._rec.own
+  tr._rec = None
   tr._auto_step(img2, lab2, None, None)                    # host tensors: nothing to record
   assert len(calls) == 2
   tr.grad_sync = object()                                  # an exchange without launch_recorded: not attempted

@@ -15,6 +15,9 @@ Cases = configurations (tests/model_parity.CONFIGS, at the sizes tests/test_fusi
              eval         inference forward without a tape: batch norm folded into the conv epilogue (the stem, whose
                           pre-BN output the walker always taps as 'initial_conv', takes the un-folded tap form)
              eval_taped   inference forward with a tape: moving-statistics batch norm as its own pass in every layer
+             trainer      (on request: --modes trainer; --configs is not used) two train.Trainer.train_step calls of three
+                          trainers: a plain one, one with KD + mixup type 2, one made with recorded=True that runs DropBlock
+                          from its static buffers with given draws; the digest covers both steps' loss rows and the arenas
 
   python tools/host_trace.py [--configs a,b] [--knobs fused,plain,...] [--modes ...] [--jobs N] [--threads N]
 """
@@ -32,6 +35,10 @@ ALONE = SWITCHES[:5]
 KNOB_SETS = ['fused', 'plain'] + [k + '=0' for k in ALONE]
 MODES = ['step', 'train_fwd', 'eval', 'eval_taped']
 BATCH, SIZE = 2, 64
+DROPBLOCK = dict(resnet_version=2, use_sk_block=True, anti_alias_type='sconv', anti_alias_filter_size=3, use_resnet_d=True,
+                 use_dropblock=True, dropblock_kp=[0.9, 0.6], train_epochs=1, num_images_train=8)
+TRAINERS = {'plain': dict(resnet_version=1), 'kd-mixup2': dict(resnet_version=1, kd_temp=2.0, mixup_type=2),
+            'dropblock': DROPBLOCK}
 
 
 def knob_env(knob_set):
@@ -109,14 +116,50 @@ def run_case(name, mode):
   return len(proxy.log), sha('\n'.join(proxy.log).encode()), sha(*data)
 
 
+def run_trainer(name):
+  import torch
+  from assembled_cnn_amd import lib, ops
+  from assembled_cnn_amd.train import HParams, Trainer
+  from tests import model_parity as MP
+  from tests.cpu_double import CpuDouble
+  sigs = dict(lib.SIGNATURES)
+  sigs.update(lib.DEBUG_SIGNATURES)
+  proxy = LoggingLibrary(CpuDouble(), sigs)
+  ops.set_library(proxy, is_double=True)
+  ops.refresh_tuning()
+  g = torch.Generator().manual_seed(7)
+  B, size = (8, 64) if name == 'kd-mixup2' else (2, 224 if name == 'dropblock' else 64)    # DropBlock: maps >= 7 x 7
+  hp = HParams(batch_size=B, learning_rate_decay_type='fixed', base_learning_rate=0.01, **TRAINERS[name])
+  img, _, labels = MP.inputs(B, size)
+  args, kwargs = [(img, labels)] * 2, [{}, {}]
+  if name == 'kd-mixup2':
+    soft = torch.cat([torch.nn.functional.one_hot(labels.long(), hp.num_classes).float(),
+                      torch.randn((B, hp.num_classes), generator=g) * 2.0], 1)
+    args = [(img, soft, torch.rand(B // 2, generator=g), torch.rand(B // 2, generator=g)) for _ in range(2)]
+  if name == 'dropblock':       # a throw-away trainer discovers the shapes of the draws (creation order)
+    probe = Trainer(hp, seed=0, device='cpu', recorded=True)
+    probe.train_step(img, labels)
+    kwargs = [{'dropblock_uniforms': [torch.rand(tuple(u.shape), generator=g) for (u, _, _, _) in probe._db.slots]}
+              for _ in range(2)]
+  tr = Trainer(hp, seed=0, device='cpu', recorded=True if name == 'dropblock' else None)
+  del proxy.log[:]                               # the case starts after the model is built and its weights are loaded
+  losses = [tr.train_step(*a, **k).clone() for a, k in zip(args, kwargs)]
+  a = tr.model.arena
+  data = [t.detach().float().contiguous().numpy().tobytes() for t in losses + [a.g32, a.w32, a.m32, a.state]]
+  return len(proxy.log), sha('\n'.join(proxy.log).encode()), sha(*data)
+
+
 def child(knob_set, configs, modes, threads):
   import torch
   torch.set_num_threads(threads)
   sys.path.insert(0, ROOT)
   for name in configs:
-    for mode in modes:
+    for mode in [m for m in modes if m != 'trainer']:
       n, calls, data = run_case(name, mode)
       print('| %-15s | %-15s | %-10s | %5d | %s | %s |' % (name, knob_set, mode, n, calls, data), flush=True)
+  for name in TRAINERS if 'trainer' in modes else ():
+    n, calls, data = run_trainer(name)
+    print('| %-15s | %-15s | %-10s | %5d | %s | %s |' % (name, knob_set, 'trainer', n, calls, data), flush=True)
 
 
 def main():
