@@ -16,8 +16,6 @@
 
 namespace {
 
-constexpr int RED_FLOATS = 4096;  // 2 stats x 256 threads x 8 lanes
-
 struct RowTiling {
   int vcols;      // C / 8
   int vcb;        // vector columns handled concurrently (<= 256)
@@ -58,22 +56,19 @@ RowTiling make_tiling(int M, int C) {
   return t;
 }
 
-// ---- generic two-stat reduction over rows ------------------------------------------------------
-// MODE 0: (sum x, sum x^2)            inputs: a = x
-// MODE 1: (sum dz, sum dz * xhat)     inputs: a = dy, b = x, c = yout (ReLU mask, optional)
-template <int MODE>
-__global__ __launch_bounds__(256) void rowreduce_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b,
-                                                        const bf16_t* __restrict__ c, int relu, int M, int C,
-                                                        const float* __restrict__ mean,
-                                                        const float* __restrict__ invstd, RowTiling t,
-                                                        float* __restrict__ partial) {
-  __shared__ float red[RED_FLOATS];
+// ---- row reductions: NSTAT sums per channel over the rows of [M, C] ----------------------------------------------------
+// One skeleton for the three reducers.  Thread = (vector column vc0, row lane rr); a workgroup reduces the row tiles of its
+// row block in ONE channel slice and writes one partial row.  `Row` owns what differs: a thread's per-column setup
+// (setup(vc)), the operands of one row (load(ld, element offset, mask-byte index)), their accumulation into acc[NSTAT][8]
+// (accum(ld, acc)) and where statistic `which` of channel ch in row block rblk is stored (store(rblk, which, ch, v)).
+template <int NSTAT, class Row>
+__device__ __forceinline__ void row_reduce(Row row, int M, int C, const RowTiling& t) {
+  __shared__ float red[NSTAT * 2048];   // NSTAT stats x 256 threads x 8 lanes
   const int tid = threadIdx.x;
   const int vc0 = tid % t.vcb;
   const int rr = tid / t.vcb;
   const bool active = rr < t.rpb;
-  const int rdisp = blockIdx.x / t.slices, slice = blockIdx.x - rdisp * t.slices;
-  const int rblk = rdisp;
+  const int rblk = blockIdx.x / t.slices, slice = blockIdx.x - rblk * t.slices;
   const int vc_lo = slice * t.vc_slice, vc_hi = min(t.vcols, vc_lo + t.vc_slice);
   constexpr int U = 2;
   const int row_begin = rblk * (U * t.rpb);
@@ -81,87 +76,124 @@ __global__ __launch_bounds__(256) void rowreduce_kernel(const bf16_t* __restrict
   const int row_step = t.blocks * (U * t.rpb);
   for (int vcbase = vc_lo; vcbase < vc_hi; vcbase += t.vcb) {
     const int vc = vcbase + vc0;
-    float s[8], ss[8];
+    float acc[NSTAT][8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s[e] = ss[e] = 0.f;
+    for (int q = 0; q < NSTAT; ++q)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[q][e] = 0.f;
     if (active && vc < vc_hi) {
-      float mu[8], is[8];
-      if (MODE == 1) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          mu[e] = mean[vc * 8 + e];
-          is[e] = invstd[vc * 8 + e];
-        }
-      }
+      row.setup(vc);
       // 2 rows per trip (4 was ~5 % slower, 8 ~35 %: registers cost occupancy): all loads of a trip are issued before any is consumed (the reduction is
       // bandwidth-bound only if enough bytes are in flight per CU)
-      for (int row = row_begin + rr; row < row_end; row += row_step) {
-        u32x4 va[U], vb[U], vy[U];
-        unsigned mk[U];
+      for (int r0 = row_begin + rr; r0 < row_end; r0 += row_step) {
+        typename Row::Loaded ld[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          const int r = row + u * t.rpb;
-          const bool ok = r < row_end;
-          const size_t off = (size_t)(ok ? r : row) * C + vc * 8;
-          va[u] = BN_LD_RED(reinterpret_cast<const u32x4*>(a + off));
-          if (MODE == 1) {
-            vb[u] = BN_LD_RED(reinterpret_cast<const u32x4*>(b + off));
-            if (relu == 1) vy[u] = *reinterpret_cast<const u32x4*>(c + off);
-            if (relu == 2) mk[u] = reinterpret_cast<const uint8_t*>(c)[(size_t)(ok ? r : row) * t.vcols + vc];
-          }
+          const int r = r0 + u * t.rpb;
+          const size_t rq = (size_t)(r < row_end ? r : r0);   // the tail re-loads row r0 and is not consumed
+          row.load(ld[u], rq * C + vc * 8, rq * t.vcols + vc);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          if (row + u * t.rpb >= row_end) break;
-          float fa[8];
-          unpack8(va[u], fa);
-          if (MODE == 0) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              s[e] += fa[e];
-              ss[e] += fa[e] * fa[e];
-            }
-          } else {
-            float fb[8];
-            unpack8(vb[u], fb);
-            if (relu == 1) {
-              float fy[8];
-              unpack8(vy[u], fy);
-#pragma unroll
-              for (int e = 0; e < 8; ++e) fa[e] = fy[e] > 0.f ? fa[e] : 0.f;
-            } else if (relu == 2) {  // packed ReLU mask: one byte per 8-channel vector
-#pragma unroll
-              for (int e = 0; e < 8; ++e) fa[e] = ((mk[u] >> e) & 1u) ? fa[e] : 0.f;
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              s[e] += fa[e];
-              ss[e] += fa[e] * ((fb[e] - mu[e]) * is[e]);
-            }
-          }
+          if (r0 + u * t.rpb >= row_end) break;
+          row.accum(ld[u], acc);
         }
       }
     }
-    // cross row-lane reduction through LDS: red[stat][rr][vc0*8+e]
-    __syncthreads();
-    if (active) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        red[(0 * t.rpb + rr) * (t.vcb * 8) + vc0 * 8 + e] = s[e];
-        red[(1 * t.rpb + rr) * (t.vcb * 8) + vc0 * 8 + e] = ss[e];
-      }
-    }
-    __syncthreads();
-    const int ncol = t.vcb * 8;
-    for (int i = tid; i < 2 * ncol; i += 256) {
-      const int which = i / ncol, col = i - which * ncol;
-      float acc = 0.f;
-      for (int r = 0; r < t.rpb; ++r) acc += red[(which * t.rpb + r) * ncol + col];
+    __syncthreads();   // the previous column group's sums have been read
+    row_lanes_sum<NSTAT>(red, acc, active, vc0, rr, t.rpb, t.vcb * 8, [&](int which, int col, float v) {
       const int ch = vcbase * 8 + col;
-      if (ch < vc_hi * 8) partial[((size_t)rblk * 2 + which) * C + ch] = acc;
-    }
+      if (ch < vc_hi * 8) row.store(rblk, which, ch, v);
+    });
   }
 }
+
+// (sum x, sum x^2) -> partial [blocks][2][C]
+struct StatsRow {
+  const bf16_t* __restrict__ x;
+  float* __restrict__ partial;
+  int C;
+  struct Loaded { u32x4 vx; };
+  __device__ __forceinline__ void setup(int) {}
+  __device__ __forceinline__ void load(Loaded& ld, size_t off, size_t) const {
+    ld.vx = BN_LD_RED(reinterpret_cast<const u32x4*>(x + off));
+  }
+  __device__ __forceinline__ void accum(const Loaded& ld, float (&acc)[2][8]) const {
+    float f[8];
+    unpack8(ld.vx, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      acc[0][e] += f[e];
+      acc[1][e] += f[e] * f[e];
+    }
+  }
+  __device__ __forceinline__ void store(int rblk, int which, int ch, float v) const {
+    partial[((size_t)rblk * 2 + which) * C + ch] = v;
+  }
+};
+
+// (sum dz, sum dz * xhat) -> partial [blocks][2][C]; dz = dy masked by relu: 0 none, 1 the bf16 forward output > 0,
+// 2 the packed ReLU mask (yout is then the mask bytes)
+struct BwdRow {
+  const bf16_t* __restrict__ dy;
+  const bf16_t* __restrict__ x;
+  const bf16_t* __restrict__ yout;
+  int relu;
+  const float* __restrict__ mean;
+  const float* __restrict__ invstd;
+  float* __restrict__ partial;
+  int C;
+  float mu[8], is[8];
+  struct Loaded { u32x4 vg, vx, vy; unsigned mk; };
+  __device__ __forceinline__ void setup(int vc) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      mu[e] = mean[vc * 8 + e];
+      is[e] = invstd[vc * 8 + e];
+    }
+  }
+  __device__ __forceinline__ void load(Loaded& ld, size_t off, size_t mi) const {
+    ld.vg = BN_LD_RED(reinterpret_cast<const u32x4*>(dy + off));
+    ld.vx = BN_LD_RED(reinterpret_cast<const u32x4*>(x + off));
+    if (relu == 1) ld.vy = *reinterpret_cast<const u32x4*>(yout + off);
+    if (relu == 2) ld.mk = reinterpret_cast<const uint8_t*>(yout)[mi];
+  }
+  __device__ __forceinline__ void accum(const Loaded& ld, float (&acc)[2][8]) const {
+    float g[8], fx[8];
+    unpack8(ld.vg, g);
+    unpack8(ld.vx, fx);
+    if (relu == 1) {
+      float fy[8];
+      unpack8(ld.vy, fy);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] = fy[e] > 0.f ? g[e] : 0.f;
+    } else if (relu == 2) {
+      mask8(g, ld.mk);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      acc[0][e] += g[e];
+      acc[1][e] += g[e] * ((fx[e] - mu[e]) * is[e]);
+    }
+  }
+  __device__ __forceinline__ void store(int rblk, int which, int ch, float v) const {
+    partial[((size_t)rblk * 2 + which) * C + ch] = v;
+  }
+};
+
+__global__ __launch_bounds__(256) void bn_stats_kernel(const bf16_t* __restrict__ x, int M, int C, RowTiling t,
+                                                       float* __restrict__ partial) {
+  row_reduce<2>(StatsRow{x, partial, C}, M, C, t);
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                            const bf16_t* __restrict__ yout, int relu, int M, int C,
+                                                            const float* __restrict__ mean,
+                                                            const float* __restrict__ invstd, RowTiling t,
+                                                            float* __restrict__ partial) {
+  row_reduce<2>(BwdRow{dy, x, yout, relu, mean, invstd, partial, C}, M, C, t);
+}
+
 
 // ---- finalize: partials -> per-channel statistics / coefficients --------------------------------
 // block = 16 channels x FL partial-lanes.  These kernels are pure latency (one per BN layer and direction, ~200 per
@@ -244,13 +276,29 @@ __global__ __launch_bounds__(16 * FL) void partials_compact_kernel(const float* 
   const int b1 = min(blocks, b0 + per_group);
   double s0 = 0.0, s1 = 0.0;
   if (ch < C) sum_rows(in, b0, b1, ry, FL, C, ch, s0, s1);
-  red[0][ry][cx] = s0;
-  red[1][ry][cx] = s1;
-  __syncthreads();
-  if (ry < 2 && ch < C) {
-    double t = 0.0;
-    for (int r = 0; r < FL; ++r) t += red[ry][r][cx];
-    out[((size_t)blockIdx.y * 2 + ry) * C + ch] = (float)t;
+  fl_stage(red, ry, cx, s0, s1);
+  if (ry < 2 && ch < C) out[((size_t)blockIdx.y * 2 + ry) * C + ch] = (float)fl_sum(red, ry, cx);
+}
+
+// One channel's forward statistics from its sums over the M rows (fp64): mean, clamped biased variance, invstd, the
+// Bessel-corrected moving update; -> scale = gamma * invstd, shift = beta - mean * scale.
+__device__ __forceinline__ void bn_fwd_channel(double sum, double sumsq, int M, int ch, const float* __restrict__ gamma,
+                                               const float* __restrict__ beta, float eps, float momentum,
+                                               float* moving_mean, float* moving_var, float* mean, float* invstd,
+                                               float& sc, float& sh) {
+  const double mu = sum / (double)M;
+  double var = sumsq / (double)M - mu * mu;
+  if (var < 0.0) var = 0.0;
+  const float is = (float)(1.0 / sqrt(var + (double)eps));
+  const float s = gamma[ch] * is;
+  sc = s;
+  sh = beta[ch] - (float)mu * s;
+  mean[ch] = (float)mu;
+  invstd[ch] = is;
+  if (moving_mean) {
+    const double unbiased = var * ((double)M / (double)(M > 1 ? M - 1 : 1));
+    moving_mean[ch] = moving_mean[ch] * momentum + (float)mu * (1.f - momentum);
+    moving_var[ch] = moving_var[ch] * momentum + (float)unbiased * (1.f - momentum);
   }
 }
 
@@ -264,29 +312,11 @@ __global__ __launch_bounds__(16 * FL) void bn_finalize_kernel(const float* __res
   const int ch = blockIdx.x * 16 + cx;
   double s0, s1;
   sum_partials(partial, blocks, C, ch, ry, s0, s1);
-  red[0][ry][cx] = s0;
-  red[1][ry][cx] = s1;
-  __syncthreads();
+  fl_stage(red, ry, cx, s0, s1);
   if (ry == 0 && ch < C) {
-    double a = 0.0, b = 0.0;
-    for (int r = 0; r < FL; ++r) {
-      a += red[0][r][cx];
-      b += red[1][r][cx];
-    }
-    const double mu = a / (double)M;
-    double var = b / (double)M - mu * mu;
-    if (var < 0.0) var = 0.0;
-    const float is = (float)(1.0 / sqrt(var + (double)eps));
-    const float sc = gamma[ch] * is;
-    mean[ch] = (float)mu;
-    invstd[ch] = is;
-    scale[ch] = sc;
-    shift[ch] = beta[ch] - (float)mu * sc;
-    if (moving_mean) {
-      const double unbiased = var * ((double)M / (double)(M > 1 ? M - 1 : 1));
-      moving_mean[ch] = moving_mean[ch] * momentum + (float)mu * (1.f - momentum);
-      moving_var[ch] = moving_var[ch] * momentum + (float)unbiased * (1.f - momentum);
-    }
+    double a, b;
+    fl_sum2(red, cx, a, b);
+    bn_fwd_channel(a, b, M, ch, gamma, beta, eps, momentum, moving_mean, moving_var, mean, invstd, scale[ch], shift[ch]);
   }
 }
 
@@ -301,25 +331,15 @@ __global__ __launch_bounds__(16 * FL) void bn_bwd_finalize_kernel(const float* _
   const int ch = blockIdx.x * 16 + cx;
   double s0, s1;
   sum_partials(partial, blocks, C, ch, ry, s0, s1);
-  red[0][ry][cx] = s0;
-  red[1][ry][cx] = s1;
-  __syncthreads();
+  fl_stage(red, ry, cx, s0, s1);
   if (ry == 0 && ch < C) {
-    double db = 0.0, dg = 0.0;
-    for (int r = 0; r < FL; ++r) {
-      db += red[0][r][cx];
-      dg += red[1][r][cx];
-    }
-    const double g = gamma[ch], is = invstd[ch], mu = mean[ch];
+    double db, dg;
+    fl_sum2(red, cx, db, dg);
+    const double is = invstd[ch], mu = mean[ch];
     if (raw) dg = is * (dg - mu * db);      // partials of (sum dz, sum dz * y) from an input-gradient epilogue: -> sum dz * xhat
     dbeta[ch] = (float)db;
     dgamma[ch] = (float)dg;
-    const double A = g * is;
-    const double B = -g * is * is * dg / (double)M;
-    const double Cc = -g * is * db / (double)M - B * mu;
-    coefA[ch] = (float)A;
-    coefB[ch] = (float)B;
-    coefC[ch] = (float)Cc;
+    bn_bwd_coefs(gamma[ch], is, mu, db, dg, (double)M, coefA[ch], coefB[ch], coefC[ch]);
   }
 }
 
@@ -334,45 +354,63 @@ __global__ void bn_infer_coeffs_kernel(int C, const float* gamma, const float* b
   }
 }
 
+// ---- element-wise passes over the nvec = M * C / 8 vectors of [M, C] --------------------------------------------------
+// One skeleton for the four apply kernels: a grid-stride loop that calls body(i, m, vc, k) for vector i = row m x vector
+// column vc, with k[q] = the 8 floats of coefficient row coef[q] at that column.
+// When the grid stride is a multiple of C/8 a thread keeps the same 8 channels on every trip: their coefficients
+// are loaded once (they were 4 extra 16-byte loads per 16-byte data load, all L1 hits but all TA cycles).
+template <int NCOEF, class Body>
+__device__ __forceinline__ void for_each_vec(size_t nvec, int C, const FastDiv& fd_vcols, const float* const (&coef)[NCOEF],
+                                             Body body) {
+  const int vcols = C >> 3;
+  const size_t stride = (size_t)gridDim.x * 256;
+  const bool fixed = (stride % (size_t)vcols) == 0;
+  float k[NCOEF][8];
+  auto load_coef = [&](int vc) {
+#pragma unroll
+    for (int q = 0; q < NCOEF; ++q) {
+      const f32x4 lo = *reinterpret_cast<const f32x4*>(coef[q] + vc * 8);
+      const f32x4 hi = *reinterpret_cast<const f32x4*>(coef[q] + vc * 8 + 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        k[q][e] = lo[e];
+        k[q][e + 4] = hi[e];
+      }
+    }
+  };
+  // Two loops, not one with the reload under a branch: there the compiler kept the loop-carried coefficients and the
+  // freshly loaded ones in different register layouts (132 VGPRs for the 6 rows of bn_bwd_apply2_kernel against 83).
+  const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (fixed) {
+    load_coef((int)(i0 % (size_t)vcols));
+    for (size_t i = i0; i < nvec; i += stride) {
+      const unsigned m = fd_div((unsigned)i, fd_vcols);
+      body(i, m, (int)((unsigned)i - m * (unsigned)vcols), k);
+    }
+  } else {
+    for (size_t i = i0; i < nvec; i += stride) {
+      const unsigned m = fd_div((unsigned)i, fd_vcols);
+      const int vc = (int)((unsigned)i - m * (unsigned)vcols);
+      load_coef(vc);
+      body(i, m, vc, k);
+    }
+  }
+}
+
 // ---- apply: y = [relu](x*scale + shift [+ residual]) ---------------------------------------------
 template <int RES, bool RELU>
-__global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
-                                                       size_t nvec, int C, FastDiv fd_vcols,
+__global__ __launch_bounds__(256) void bn_apply_kernel(size_t nvec, int C, FastDiv fd_vcols,
+                                                       const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
                                                        const float* __restrict__ scale,
                                                        const float* __restrict__ shift,
                                                        const bf16_t* __restrict__ res, FastDiv fd_w, FastDiv fd_h,
                                                        int H, int W, uint8_t* __restrict__ mask) {
-  const int vcols = C >> 3;
-  // When the grid stride is a multiple of C/8 a thread keeps the same 8 channels on every trip: their coefficients
-  // are loaded once (they were 4 extra 16-byte loads per 16-byte data load, all L1 hits but all TA cycles).
-  const size_t stride = (size_t)gridDim.x * 256;
-  const bool fixed = (stride % (size_t)vcols) == 0;
-  f32x4 s0, s1, h0, h1;
-  if (fixed) {
-    const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const int vc0 = (int)(i0 % (size_t)vcols);
-    s0 = *reinterpret_cast<const f32x4*>(scale + vc0 * 8);
-    s1 = *reinterpret_cast<const f32x4*>(scale + vc0 * 8 + 4);
-    h0 = *reinterpret_cast<const f32x4*>(shift + vc0 * 8);
-    h1 = *reinterpret_cast<const f32x4*>(shift + vc0 * 8 + 4);
-  }
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += stride) {
-    const unsigned m = fd_div((unsigned)i, fd_vcols);
-    const int vc = (int)((unsigned)i - m * (unsigned)vcols);
-    const u32x4 vx = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + i * 8));
+  const float* const coef[2] = {scale, shift};
+  for_each_vec<2>(nvec, C, fd_vcols, coef, [&](size_t i, unsigned m, int vc, const float (&k)[2][8]) {
     float f[8];
-    unpack8(vx, f);
-    if (!fixed) {
-      s0 = *reinterpret_cast<const f32x4*>(scale + vc * 8);
-      s1 = *reinterpret_cast<const f32x4*>(scale + vc * 8 + 4);
-      h0 = *reinterpret_cast<const f32x4*>(shift + vc * 8);
-      h1 = *reinterpret_cast<const f32x4*>(shift + vc * 8 + 4);
-    }
+    unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + i * 8)), f);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      f[e] = f[e] * s0[e] + h0[e];
-      f[e + 4] = f[e + 4] * s1[e] + h1[e];
-    }
+    for (int e = 0; e < 8; ++e) f[e] = f[e] * k[0][e] + k[1][e];
     if (RES != 0) {
       size_t ri;
       if (RES == 1) {
@@ -382,51 +420,39 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_t* __restrict_
         const unsigned w = m - nh * (unsigned)W;
         const unsigned n = fd_div(nh, fd_h);
         const unsigned h = nh - n * (unsigned)H;
-        ri = ((((size_t)n * (H >> 1) + (h >> 1)) * (W >> 1) + (w >> 1)) * vcols + vc) * 8;
+        ri = ((((size_t)n * (H >> 1) + (h >> 1)) * (W >> 1) + (w >> 1)) * (C >> 3) + vc) * 8;
       }
-      const u32x4 vr = *reinterpret_cast<const u32x4*>(res + ri);
       float r[8];
-      unpack8(vr, r);
+      unpack8(*reinterpret_cast<const u32x4*>(res + ri), r);
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] += r[e];
     }
     if (RELU) {
-      if (mask) {
-        unsigned mk = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) mk |= (f[e] > 0.f ? 1u : 0u) << e;
-        mask[i] = (uint8_t)mk;
-      }
+      if (mask) mask[i] = (uint8_t)relu_mask8(f);
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
     }
     BN_ST_FWD(pack8(f), reinterpret_cast<u32x4*>(y + i * 8));
-  }
+  });
 }
 
 // ---- backward apply: dx = A*dz + B*x + C ; dz = dy * [yout > 0] -----------------------------------
+// A * dz + B * x has two products and the compiler fuses ONE of them into the add; which one depended on the code around the
+// expression (the rounded product was B * x in every kernel here until the loop moved into for_each_vec, A * dz after).
+// Spelled out, so that dx keeps its bits whatever surrounds it: fma(A, dz, round(B * x)) + C.
+__device__ __forceinline__ float bwd_dx(float A, float dz, float B, float x, float C) {
+  return __builtin_fmaf(A, dz, B * x) + C;
+}
+
 template <int RELU, bool WRITE_DZ>  // RELU: 0 none, 1 mask from the bf16 forward output, 2 packed bitmask
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
-                                                           const bf16_t* __restrict__ yout, size_t nvec, int C,
-                                                           FastDiv fd_vcols, const float* __restrict__ cA,
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(size_t nvec, int C, FastDiv fd_vcols,
+                                                           const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                           const bf16_t* __restrict__ yout, const float* __restrict__ cA,
                                                            const float* __restrict__ cB,
                                                            const float* __restrict__ cC, bf16_t* __restrict__ dx,
                                                            bf16_t* __restrict__ dz) {
-  const int vcols = C >> 3;
-  const size_t stride = (size_t)gridDim.x * 256;
-  const bool fixed = (stride % (size_t)vcols) == 0;   // see bn_apply_kernel
-  float kA[8], kB[8], kC[8];
-  if (fixed) {
-    const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const int vc0 = (int)(i0 % (size_t)vcols);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      kA[e] = cA[vc0 * 8 + e];
-      kB[e] = cB[vc0 * 8 + e];
-      kC[e] = cC[vc0 * 8 + e];
-    }
-  }
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += stride) {
+  const float* const coef[3] = {cA, cB, cC};
+  for_each_vec<3>(nvec, C, fd_vcols, coef, [&](size_t i, unsigned, int, const float (&k)[3][8]) {
     float g[8], fx[8];
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + i * 8)), g);
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + i * 8)), fx);
@@ -436,26 +462,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restr
 #pragma unroll
       for (int e = 0; e < 8; ++e) g[e] = fy[e] > 0.f ? g[e] : 0.f;
     } else if (RELU == 2) {
-      const unsigned mk = reinterpret_cast<const uint8_t*>(yout)[i];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = ((mk >> e) & 1u) ? g[e] : 0.f;
+      mask8(g, reinterpret_cast<const uint8_t*>(yout)[i]);
     }
     if (WRITE_DZ) *reinterpret_cast<u32x4*>(dz + i * 8) = pack8(g);
-    if (!fixed) {
-      const unsigned m = fd_div((unsigned)i, fd_vcols);
-      const int vc = (int)((unsigned)i - m * (unsigned)vcols);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        kA[e] = cA[vc * 8 + e];
-        kB[e] = cB[vc * 8 + e];
-        kC[e] = cC[vc * 8 + e];
-      }
-    }
     float o[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = kA[e] * g[e] + kB[e] * fx[e] + kC[e];
+    for (int e = 0; e < 8; ++e) o[e] = bwd_dx(k[0][e], g[e], k[1][e], fx[e], k[2][e]);
     BN_ST_BWD(pack8(o), reinterpret_cast<u32x4*>(dx + i * 8));
-  }
+  });
 }
 
 // ---- two batch norms behind ONE ReLU: the block-final BN and the projection-shortcut BN of a bottleneck ---------------
@@ -463,191 +477,121 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restr
 // independent BN backwards that is 2 x (reduce: dout, y, mask; apply: dout, y, mask -> dy) = 20.5 B per element; here dout
 // and the mask are read once per pass for both: 16.25 B per element and two launches fewer per projection block.
 // Partials: pa = [blocks][2][C] (sum g, sum g * xhat_a), pb likewise for b (sum g repeated, so the finalize is unchanged).
-__global__ __launch_bounds__(256) void rowreduce2_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ xa,
-                                                         const bf16_t* __restrict__ xb, const uint8_t* __restrict__ mask,
-                                                         int M, int C, const float* __restrict__ mean_a,
-                                                         const float* __restrict__ invstd_a, const float* __restrict__ mean_b,
-                                                         const float* __restrict__ invstd_b, RowTiling t,
-                                                         float* __restrict__ pa, float* __restrict__ pb) {
-  __shared__ float red[3 * 2048];
-  const int tid = threadIdx.x;
-  const int vc0 = tid % t.vcb;
-  const int rr = tid / t.vcb;
-  const bool active = rr < t.rpb;
-  const int rdisp = blockIdx.x / t.slices, slice = blockIdx.x - rdisp * t.slices;
-  const int rblk = rdisp;
-  const int vc_lo = slice * t.vc_slice, vc_hi = min(t.vcols, vc_lo + t.vc_slice);
-  constexpr int U = 2;
-  const int row_begin = rblk * (U * t.rpb);
-  const int row_end = M;
-  const int row_step = t.blocks * (U * t.rpb);
-  for (int vcbase = vc_lo; vcbase < vc_hi; vcbase += t.vcb) {
-    const int vc = vcbase + vc0;
-    float s[8], sa[8], sb[8];
+struct BwdRow2 {
+  const bf16_t* __restrict__ dy;
+  const bf16_t* __restrict__ xa;
+  const bf16_t* __restrict__ xb;
+  const uint8_t* __restrict__ mask;
+  const float* __restrict__ mean_a;
+  const float* __restrict__ invstd_a;
+  const float* __restrict__ mean_b;
+  const float* __restrict__ invstd_b;
+  float* __restrict__ pa;
+  float* __restrict__ pb;
+  int C;
+  float ma[8], ia[8], mb[8], ib[8];
+  struct Loaded { u32x4 vg, va, vb; unsigned mk; };
+  __device__ __forceinline__ void setup(int vc) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) s[e] = sa[e] = sb[e] = 0.f;
-    if (active && vc < vc_hi) {
-      float ma[8], ia[8], mb[8], ib[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        ma[e] = mean_a[vc * 8 + e];
-        ia[e] = invstd_a[vc * 8 + e];
-        mb[e] = mean_b[vc * 8 + e];
-        ib[e] = invstd_b[vc * 8 + e];
-      }
-      for (int row = row_begin + rr; row < row_end; row += row_step) {
-        u32x4 vg[U], va[U], vb[U];
-        unsigned mk[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int r = row + u * t.rpb;
-          const size_t rq = (size_t)(r < row_end ? r : row);
-          const size_t off = rq * C + vc * 8;
-          vg[u] = BN_LD_RED(reinterpret_cast<const u32x4*>(dy + off));
-          va[u] = BN_LD_RED(reinterpret_cast<const u32x4*>(xa + off));
-          vb[u] = BN_LD_RED(reinterpret_cast<const u32x4*>(xb + off));
-          mk[u] = mask[rq * t.vcols + vc];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          if (row + u * t.rpb >= row_end) break;
-          float g[8], fa[8], fb[8];
-          unpack8(vg[u], g);
-          unpack8(va[u], fa);
-          unpack8(vb[u], fb);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float ge = ((mk[u] >> e) & 1u) ? g[e] : 0.f;
-            s[e] += ge;
-            sa[e] += ge * ((fa[e] - ma[e]) * ia[e]);
-            sb[e] += ge * ((fb[e] - mb[e]) * ib[e]);
-          }
-        }
-      }
-    }
-    __syncthreads();
-    const int ncol = t.vcb * 8;
-    if (active) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        red[(0 * t.rpb + rr) * ncol + vc0 * 8 + e] = s[e];
-        red[(1 * t.rpb + rr) * ncol + vc0 * 8 + e] = sa[e];
-        red[(2 * t.rpb + rr) * ncol + vc0 * 8 + e] = sb[e];
-      }
-    }
-    __syncthreads();
-    for (int i = tid; i < 3 * ncol; i += 256) {
-      const int which = i / ncol, col = i - which * ncol;
-      float acc = 0.f;
-      for (int r = 0; r < t.rpb; ++r) acc += red[(which * t.rpb + r) * ncol + col];
-      const int ch = vcbase * 8 + col;
-      if (ch < vc_hi * 8) {
-        if (which == 0) {
-          pa[((size_t)rblk * 2 + 0) * C + ch] = acc;
-          pb[((size_t)rblk * 2 + 0) * C + ch] = acc;
-        } else if (which == 1) {
-          pa[((size_t)rblk * 2 + 1) * C + ch] = acc;
-        } else {
-          pb[((size_t)rblk * 2 + 1) * C + ch] = acc;
-        }
-      }
+    for (int e = 0; e < 8; ++e) {
+      ma[e] = mean_a[vc * 8 + e];
+      ia[e] = invstd_a[vc * 8 + e];
+      mb[e] = mean_b[vc * 8 + e];
+      ib[e] = invstd_b[vc * 8 + e];
     }
   }
+  __device__ __forceinline__ void load(Loaded& ld, size_t off, size_t mi) const {
+    ld.vg = BN_LD_RED(reinterpret_cast<const u32x4*>(dy + off));
+    ld.va = BN_LD_RED(reinterpret_cast<const u32x4*>(xa + off));
+    ld.vb = BN_LD_RED(reinterpret_cast<const u32x4*>(xb + off));
+    ld.mk = mask[mi];
+  }
+  __device__ __forceinline__ void accum(const Loaded& ld, float (&acc)[3][8]) const {
+    float g[8], fa[8], fb[8];
+    unpack8(ld.vg, g);
+    unpack8(ld.va, fa);
+    unpack8(ld.vb, fb);
+    mask8(g, ld.mk);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      acc[0][e] += g[e];
+      acc[1][e] += g[e] * ((fa[e] - ma[e]) * ia[e]);
+      acc[2][e] += g[e] * ((fb[e] - mb[e]) * ib[e]);
+    }
+  }
+  __device__ __forceinline__ void store(int rblk, int which, int ch, float v) const {
+    if (which == 0) {
+      pa[((size_t)rblk * 2 + 0) * C + ch] = v;
+      pb[((size_t)rblk * 2 + 0) * C + ch] = v;
+    } else if (which == 1) {
+      pa[((size_t)rblk * 2 + 1) * C + ch] = v;
+    } else {
+      pb[((size_t)rblk * 2 + 1) * C + ch] = v;
+    }
+  }
+};
+
+__global__ __launch_bounds__(256) void bn_bwd_reduce2_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ xa,
+                                                             const bf16_t* __restrict__ xb, const uint8_t* __restrict__ mask,
+                                                             int M, int C, const float* __restrict__ mean_a,
+                                                             const float* __restrict__ invstd_a, const float* __restrict__ mean_b,
+                                                             const float* __restrict__ invstd_b, RowTiling t,
+                                                             float* __restrict__ pa, float* __restrict__ pb) {
+  row_reduce<3>(BwdRow2{dy, xa, xb, mask, mean_a, invstd_a, mean_b, invstd_b, pa, pb, C}, M, C, t);
 }
 
 // dxa = A_a * g + B_a * xa + C_a ; dxb likewise ; g = dy * [mask bit].  co = [6][C]: A_a, B_a, C_a, A_b, B_b, C_b.
-__global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ xa,
+__global__ __launch_bounds__(256) void bn_bwd_apply2_kernel(size_t nvec, int C, FastDiv fd_vcols,
+                                                            const bf16_t* __restrict__ dy, const bf16_t* __restrict__ xa,
                                                             const bf16_t* __restrict__ xb, const uint8_t* __restrict__ mask,
-                                                            size_t nvec, int C, FastDiv fd_vcols,
                                                             const float* __restrict__ co, bf16_t* __restrict__ dxa,
                                                             bf16_t* __restrict__ dxb) {
-  const int vcols = C >> 3;
-  const size_t stride = (size_t)gridDim.x * 256;
-  const bool fixed = (stride % (size_t)vcols) == 0;   // see bn_apply_kernel
-  float k[6][8];
-  if (fixed) {
-    const size_t i0 = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const int vc0 = (int)(i0 % (size_t)vcols);
-#pragma unroll
-    for (int q = 0; q < 6; ++q)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) k[q][e] = co[(size_t)q * C + vc0 * 8 + e];
-  }
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += stride) {
+  const float* const coef[6] = {co, co + (size_t)C, co + (size_t)2 * C, co + (size_t)3 * C, co + (size_t)4 * C, co + (size_t)5 * C};
+  for_each_vec<6>(nvec, C, fd_vcols, coef, [&](size_t i, unsigned, int, const float (&k)[6][8]) {
     float g[8], fa[8], fb[8];
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + i * 8)), g);
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(xa + i * 8)), fa);
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(xb + i * 8)), fb);
-    const unsigned mk = mask[i];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = ((mk >> e) & 1u) ? g[e] : 0.f;
-    if (!fixed) {
-      const unsigned m = fd_div((unsigned)i, fd_vcols);
-      const int vc = (int)((unsigned)i - m * (unsigned)vcols);
-#pragma unroll
-      for (int q = 0; q < 6; ++q)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) k[q][e] = co[(size_t)q * C + vc * 8 + e];
-    }
+    mask8(g, mask[i]);
     float oa[8], ob[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      oa[e] = k[0][e] * g[e] + k[1][e] * fa[e] + k[2][e];
-      ob[e] = k[3][e] * g[e] + k[4][e] * fb[e] + k[5][e];
+      oa[e] = bwd_dx(k[0][e], g[e], k[1][e], fa[e], k[2][e]);
+      ob[e] = bwd_dx(k[3][e], g[e], k[4][e], fb[e], k[5][e]);
     }
     BN_ST_BWD(pack8(oa), reinterpret_cast<u32x4*>(dxa + i * 8));
     BN_ST_BWD(pack8(ob), reinterpret_cast<u32x4*>(dxb + i * 8));
-  }
+  });
 }
 
 // ---- forward twin of the pair above: out = [relu](bn_a(xa) + bf16(bn_b(xb))) in one pass -----------------------------
 // The projection-shortcut batch norm has no consumer but this add, so its normalised tensor need not exist in HBM: it is
 // evaluated on the fly (and rounded to bf16 exactly where the separate pass stored it: results are bit-identical).
-// Saves the 4 B / element the shortcut's own apply pass moved.  co = [4][C]: scale_a, shift_a, scale_b, shift_b.
+// Saves the 4 B / element the shortcut's own apply pass moved.
 template <bool RELU>
-__global__ __launch_bounds__(256) void bn_apply2_kernel(const bf16_t* __restrict__ xa, const bf16_t* __restrict__ xb,
-                                                        bf16_t* __restrict__ y, size_t nvec, int C, FastDiv fd_vcols,
+__global__ __launch_bounds__(256) void bn_apply2_kernel(size_t nvec, int C, FastDiv fd_vcols, const bf16_t* __restrict__ xa,
+                                                        const bf16_t* __restrict__ xb, bf16_t* __restrict__ y,
                                                         const float* __restrict__ sa, const float* __restrict__ ha,
                                                         const float* __restrict__ sb, const float* __restrict__ hb,
                                                         uint8_t* __restrict__ mask) {
-  const int vcols = C >> 3;
-  const size_t stride = (size_t)gridDim.x * 256;
-  const bool fixed = (stride % (size_t)vcols) == 0;   // see bn_apply_kernel
-  float k[4][8];
-  auto load_coef = [&](int vc) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      k[0][e] = sa[vc * 8 + e];
-      k[1][e] = ha[vc * 8 + e];
-      k[2][e] = sb[vc * 8 + e];
-      k[3][e] = hb[vc * 8 + e];
-    }
-  };
-  if (fixed) load_coef((int)(((size_t)blockIdx.x * 256 + threadIdx.x) % (size_t)vcols));
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += stride) {
+  const float* const coef[4] = {sa, ha, sb, hb};
+  for_each_vec<4>(nvec, C, fd_vcols, coef, [&](size_t i, unsigned, int, const float (&k)[4][8]) {
     float fa[8], fb[8];
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(xa + i * 8)), fa);
     unpack8(__builtin_nontemporal_load(reinterpret_cast<const u32x4*>(xb + i * 8)), fb);
-    if (!fixed) {
-      const unsigned m = fd_div((unsigned)i, fd_vcols);
-      load_coef((int)((unsigned)i - m * (unsigned)vcols));
-    }
 #pragma unroll
     for (int e = 0; e < 8; ++e) fb[e] = fb[e] * k[2][e] + k[3][e];
     float rb[8];
     unpack8(pack8(fb), rb);                 // the bf16 rounding of the materialised shortcut tensor
-    unsigned mk = 0;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      fa[e] = fa[e] * k[0][e] + k[1][e] + rb[e];
-      if (RELU) {
-        mk |= (fa[e] > 0.f ? 1u : 0u) << e;
-        fa[e] = fmaxf(fa[e], 0.f);
-      }
+    for (int e = 0; e < 8; ++e) fa[e] = fa[e] * k[0][e] + k[1][e] + rb[e];
+    if (RELU) {
+      if (mask) mask[i] = (uint8_t)relu_mask8(fa);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) fa[e] = fmaxf(fa[e], 0.f);
     }
-    if (RELU && mask) mask[i] = (uint8_t)mk;
     BN_ST_FWD(pack8(fa), reinterpret_cast<u32x4*>(y + i * 8));
-  }
+  });
 }
 
 // ---- small-tensor batch norm: statistics + finalize + apply in ONE launch (and reduce + finalize + apply backward) ----
@@ -720,20 +664,8 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const bf16_t* __restr
         a += (double)red[0][threadIdx.x][r];
         b += (double)red[1][threadIdx.x][r];
       }
-      const double mu = a / (double)M;
-      double var = b / (double)M - mu * mu;
-      if (var < 0.0) var = 0.0;
-      const float is = (float)(1.0 / sqrt(var + (double)eps));
-      const float sc = gamma[ch] * is;
-      mean[ch] = (float)mu;
-      invstd[ch] = is;
-      coef[0][threadIdx.x] = sc;
-      coef[1][threadIdx.x] = beta[ch] - (float)mu * sc;
-      if (moving_mean) {
-        const double unbiased = var * ((double)M / (double)(M > 1 ? M - 1 : 1));
-        moving_mean[ch] = moving_mean[ch] * momentum + (float)mu * (1.f - momentum);
-        moving_var[ch] = moving_var[ch] * momentum + (float)unbiased * (1.f - momentum);
-      }
+      bn_fwd_channel(a, b, M, ch, gamma, beta, eps, momentum, moving_mean, moving_var, mean, invstd, coef[0][threadIdx.x],
+                     coef[1][threadIdx.x]);
     }
   }
   __syncthreads();
@@ -741,16 +673,13 @@ __global__ __launch_bounds__(256) void bn_small_fwd_kernel(const bf16_t* __restr
     const size_t i = (size_t)r * vcols + vc;
     float f[8];
     unpack8(vx, f);
-    unsigned mk = 0;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      f[e] = f[e] * coef[0][vcl * 8 + e] + coef[1][vcl * 8 + e];
-      if (RELU) {
-        mk |= (f[e] > 0.f ? 1u : 0u) << e;
-        f[e] = fmaxf(f[e], 0.f);
-      }
+    for (int e = 0; e < 8; ++e) f[e] = f[e] * coef[0][vcl * 8 + e] + coef[1][vcl * 8 + e];
+    if (RELU) {
+      if (mask) mask[i] = (uint8_t)relu_mask8(f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
     }
-    if (RELU && mask) mask[i] = (uint8_t)mk;
     *reinterpret_cast<u32x4*>(y + i * 8) = pack8(f);
   };
   if (live && keep) {
@@ -791,10 +720,7 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const bf16_t* __restr
   unsigned km[KU];
   auto masked = [&](const u32x4& vg, unsigned mk, float* g) {
     unpack8(vg, g);
-    if (RELU == 2) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = ((mk >> e) & 1u) ? g[e] : 0.f;
-    }
+    if (RELU == 2) mask8(g, mk);
   };
   auto reduce_row = [&](const u32x4& vg, const u32x4& vx, unsigned mk) {
     float g[8], fx[8];
@@ -843,12 +769,8 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const bf16_t* __restr
       }
       dbeta[ch] = (float)db;
       dgamma[ch] = (float)dg;
-      const double g = gamma[ch], isd = invstd[ch], m = mean[ch];
-      const double A = g * isd;
-      const double B = -g * isd * isd * dg / (double)M;
-      coef[0][threadIdx.x] = (float)A;
-      coef[1][threadIdx.x] = (float)B;
-      coef[2][threadIdx.x] = (float)(-g * isd * db / (double)M - B * m);
+      bn_bwd_coefs(gamma[ch], invstd[ch], mean[ch], db, dg, (double)M, coef[0][threadIdx.x], coef[1][threadIdx.x],
+                   coef[2][threadIdx.x]);
     }
   }
   __syncthreads();
@@ -880,6 +802,13 @@ inline unsigned ew_grid(size_t nvec) {
   return (unsigned)(b < 4096 ? (b ? b : 1) : 4096);
 }
 
+// launch a for_each_vec kernel -- parameters (nvec, C, fastdiv(C / 8), rest...) -- over the M * C / 8 vectors of [M, C]
+template <class... P, class... A>
+void launch_vecs(void (*kernel)(size_t, int, FastDiv, P...), void* stream, int M, int C, A... rest) {
+  const size_t nvec = (size_t)M * (C / 8);
+  ASM_LAUNCH(kernel, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, nvec, C, make_fastdiv((unsigned)(C / 8)), rest...);
+}
+
 }  // namespace
 
 extern "C" int asm_bn_stats_blocks(int M, int C) {
@@ -890,8 +819,8 @@ extern "C" int asm_bn_stats_blocks(int M, int C) {
 extern "C" int asm_bn_stats(const void* x, int M, int C, float* stats_partial, void* stream) {
   ASM_REQUIRE(x && stats_partial && M > 0 && C > 0 && C % 8 == 0, "bn_stats: bad arguments (M=%d C=%d)", M, C);
   RowTiling t = make_tiling(M, C);
-  ASM_LAUNCH((rowreduce_kernel<0>), dim3(t.blocks * t.slices), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, nullptr, nullptr, 0, M, C, nullptr, nullptr, t, stats_partial);
+  ASM_LAUNCH(bn_stats_kernel, dim3(t.blocks * t.slices), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, M, C, t,
+             stats_partial);
   ASM_CHECK_LAUNCH("bn_stats");
   return ASM_OK;
 }
@@ -937,18 +866,13 @@ extern "C" int asm_bn_apply(const void* x, void* y, int M, int C, const float* s
   ASM_REQUIRE((size_t)M * (C / 8) < 0x7fffffffull, "bn_apply: tensor too large");
   if (res_mode == 2)
     ASM_REQUIRE(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && M % (H * W) == 0, "bn_apply: bad upsample geometry");
-  const size_t nvec = (size_t)M * (C / 8);
-  const FastDiv fv = make_fastdiv((unsigned)(C / 8));
   const FastDiv fw = make_fastdiv((unsigned)(W > 0 ? W : 1)), fh = make_fastdiv((unsigned)(H > 0 ? H : 1));
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(ew_grid(nvec)), block(256);
-#define LAUNCH_APPLY(RES, RELU)                                                                          \
-  ASM_LAUNCH((bn_apply_kernel<RES, RELU>), grid, block, 0, st, (const bf16_t*)x, (bf16_t*)y, nvec, C, fv, \
-                     scale, shift, (const bf16_t*)residual, fw, fh, H, W, relu_mask_out)
-  if (res_mode == 0) { if (relu) LAUNCH_APPLY(0, true); else LAUNCH_APPLY(0, false); }
-  else if (res_mode == 1) { if (relu) LAUNCH_APPLY(1, true); else LAUNCH_APPLY(1, false); }
-  else { if (relu) LAUNCH_APPLY(2, true); else LAUNCH_APPLY(2, false); }
-#undef LAUNCH_APPLY
+  static constexpr decltype(&bn_apply_kernel<0, false>) kernels[3][2] = {
+      {bn_apply_kernel<0, false>, bn_apply_kernel<0, true>},
+      {bn_apply_kernel<1, false>, bn_apply_kernel<1, true>},
+      {bn_apply_kernel<2, false>, bn_apply_kernel<2, true>}};   // [res_mode][relu]
+  launch_vecs(kernels[res_mode][relu != 0], stream, M, C, (const bf16_t*)x, (bf16_t*)y, scale, shift, (const bf16_t*)residual,
+              fw, fh, H, W, relu_mask_out);
   ASM_CHECK_LAUNCH("bn_apply");
   return ASM_OK;
 }
@@ -958,7 +882,7 @@ extern "C" int asm_bn_bwd_reduce(const void* dy, const void* x, const void* yout
   ASM_REQUIRE(dy && x && mean && invstd && partial && M > 0 && C > 0 && C % 8 == 0, "bn_bwd_reduce: bad arguments");
   ASM_REQUIRE(relu >= 0 && relu <= 2 && (!relu || yout), "bn_bwd_reduce: relu mask needs the forward output / bitmask");
   RowTiling t = make_tiling(M, C);
-  ASM_LAUNCH((rowreduce_kernel<1>), dim3(t.blocks * t.slices), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
+  ASM_LAUNCH(bn_bwd_reduce_kernel, dim3(t.blocks * t.slices), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
                      (const bf16_t*)x, (const bf16_t*)yout, relu, M, C, mean, invstd, t, partial);
   ASM_CHECK_LAUNCH("bn_bwd_reduce");
   return ASM_OK;
@@ -992,17 +916,12 @@ extern "C" int asm_bn_bwd_apply(const void* dy, const void* x, const void* yout,
   ASM_REQUIRE(dy && x && dx && coefA && coefB && coefC && M > 0 && C > 0 && C % 8 == 0, "bn_bwd_apply: bad arguments");
   ASM_REQUIRE(relu >= 0 && relu <= 2 && (!relu || yout), "bn_bwd_apply: relu mask needs the forward output / bitmask");
   ASM_REQUIRE((size_t)M * (C / 8) < 0x7fffffffull, "bn_bwd_apply: tensor too large");
-  const size_t nvec = (size_t)M * (C / 8);
-  const FastDiv fv = make_fastdiv((unsigned)(C / 8));
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid(ew_grid(nvec)), block(256);
-#define LAUNCH_BWD(RELU, DZ)                                                                              \
-  ASM_LAUNCH((bn_bwd_apply_kernel<RELU, DZ>), grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x, \
-                     (const bf16_t*)yout, nvec, C, fv, coefA, coefB, coefC, (bf16_t*)dx, (bf16_t*)dz_out)
-  if (relu == 1) { if (dz_out) LAUNCH_BWD(1, true); else LAUNCH_BWD(1, false); }
-  else if (relu == 2) { if (dz_out) LAUNCH_BWD(2, true); else LAUNCH_BWD(2, false); }
-  else { if (dz_out) LAUNCH_BWD(0, true); else LAUNCH_BWD(0, false); }
-#undef LAUNCH_BWD
+  static constexpr decltype(&bn_bwd_apply_kernel<0, false>) kernels[3][2] = {
+      {bn_bwd_apply_kernel<0, false>, bn_bwd_apply_kernel<0, true>},
+      {bn_bwd_apply_kernel<1, false>, bn_bwd_apply_kernel<1, true>},
+      {bn_bwd_apply_kernel<2, false>, bn_bwd_apply_kernel<2, true>}};   // [relu kind][writes dz]
+  launch_vecs(kernels[relu][dz_out != nullptr], stream, M, C, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)yout, coefA,
+              coefB, coefC, (bf16_t*)dx, (bf16_t*)dz_out);
   ASM_CHECK_LAUNCH("bn_bwd_apply");
   return ASM_OK;
 }
@@ -1048,7 +967,7 @@ extern "C" int asm_bn_bwd_reduce2(const void* dy, const void* xa, const void* xb
   ASM_REQUIRE(dy && xa && xb && relu_mask && mean_a && invstd_a && mean_b && invstd_b && partial_a && partial_b && M > 0 &&
                   C > 0 && C % 8 == 0, "bn_bwd_reduce2: bad arguments");
   RowTiling t = make_tiling(M, C);
-  ASM_LAUNCH(rowreduce2_kernel, dim3(t.blocks * t.slices), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
+  ASM_LAUNCH(bn_bwd_reduce2_kernel, dim3(t.blocks * t.slices), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
                      (const bf16_t*)xa, (const bf16_t*)xb, relu_mask, M, C, mean_a, invstd_a, mean_b, invstd_b, t, partial_a,
                      partial_b);
   ASM_CHECK_LAUNCH("bn_bwd_reduce2");
@@ -1059,10 +978,8 @@ extern "C" int asm_bn_bwd_apply2(const void* dy, const void* xa, const void* xb,
                                  const float* coef6, void* dxa, void* dxb, void* stream) {
   ASM_REQUIRE(dy && xa && xb && relu_mask && coef6 && dxa && dxb && M > 0 && C > 0 && C % 8 == 0, "bn_bwd_apply2: bad arguments");
   ASM_REQUIRE((size_t)M * (C / 8) < 0x7fffffffull, "bn_bwd_apply2: tensor too large");
-  const size_t nvec = (size_t)M * (C / 8);
-  ASM_LAUNCH(bn_bwd_apply2_kernel, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                     (const bf16_t*)xa, (const bf16_t*)xb, relu_mask, nvec, C, make_fastdiv((unsigned)(C / 8)), coef6,
-                     (bf16_t*)dxa, (bf16_t*)dxb);
+  launch_vecs(bn_bwd_apply2_kernel, stream, M, C, (const bf16_t*)dy, (const bf16_t*)xa, (const bf16_t*)xb, relu_mask, coef6,
+              (bf16_t*)dxa, (bf16_t*)dxb);
   ASM_CHECK_LAUNCH("bn_bwd_apply2");
   return ASM_OK;
 }
@@ -1072,15 +989,8 @@ extern "C" int asm_bn_apply2(const void* xa, const void* xb, void* y, int M, int
                              uint8_t* relu_mask_out, void* stream) {
   ASM_REQUIRE(xa && xb && y && scale_a && shift_a && scale_b && shift_b && M > 0 && C > 0 && C % 8 == 0, "bn_apply2: bad arguments");
   ASM_REQUIRE((size_t)M * (C / 8) < 0x7fffffffull, "bn_apply2: tensor too large");
-  const size_t nvec = (size_t)M * (C / 8);
-  const FastDiv fv = make_fastdiv((unsigned)(C / 8));
-  const dim3 grid(ew_grid(nvec)), block(256);
-  if (relu)
-    ASM_LAUNCH(bn_apply2_kernel<true>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)xa, (const bf16_t*)xb,
-                       (bf16_t*)y, nvec, C, fv, scale_a, shift_a, scale_b, shift_b, relu_mask_out);
-  else
-    ASM_LAUNCH(bn_apply2_kernel<false>, grid, block, 0, (hipStream_t)stream, (const bf16_t*)xa, (const bf16_t*)xb,
-                       (bf16_t*)y, nvec, C, fv, scale_a, shift_a, scale_b, shift_b, nullptr);
+  launch_vecs(relu ? bn_apply2_kernel<true> : bn_apply2_kernel<false>, stream, M, C, (const bf16_t*)xa, (const bf16_t*)xb,
+              (bf16_t*)y, scale_a, shift_a, scale_b, shift_b, relu ? relu_mask_out : nullptr);
   ASM_CHECK_LAUNCH("bn_apply2");
   return ASM_OK;
 }

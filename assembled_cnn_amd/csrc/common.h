@@ -106,6 +106,71 @@ __device__ __forceinline__ u32x4 pack8(const float* f) {
   return v;
 }
 
+// packed ReLU mask: one byte per 8-channel vector, bit e = [lane e of the forward output > 0]
+__device__ __forceinline__ void mask8(float* g, unsigned mk) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) g[e] = ((mk >> e) & 1u) ? g[e] : 0.f;
+}
+__device__ __forceinline__ unsigned relu_mask8(const float* f) {
+  unsigned mk = 0;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) mk |= (f[e] > 0.f ? 1u : 0u) << e;
+  return mk;
+}
+
+// ---- batch-norm reductions shared by bn.hip and sk_fused.hip -------------------------------------
+// Tail of a row reducer with 256 threads = ncol / 8 vector columns x rpb row lanes: thread (vc0, rr) stages its NSTAT x 8
+// sums as red[stat][rr][vc0 * 8 + e] (inactive threads stage nothing), then column `col` of statistic `which` is summed
+// over the rpb row lanes in lane order (bit-reproducible) and handed to out(which, col, sum).
+template <int NSTAT, class Out>
+__device__ __forceinline__ void row_lanes_sum(float* red, const float (&acc)[NSTAT][8], bool active, int vc0, int rr, int rpb,
+                                              int ncol, Out out) {
+  if (active) {
+#pragma unroll
+    for (int q = 0; q < NSTAT; ++q)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[(q * rpb + rr) * ncol + vc0 * 8 + e] = acc[q][e];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < NSTAT * ncol; i += 256) {
+    const int which = i / ncol, col = i - which * ncol;
+    float a = 0.f;
+    for (int r = 0; r < rpb; ++r) a += red[(which * rpb + r) * ncol + col];
+    out(which, col, a);
+  }
+}
+// Column sums of the finalize kernels (block = 16 channels x FL partial lanes): every thread stages its two fp64 lane sums,
+// then fl_sum adds the FL lanes of one statistic of channel column cx in lane order (fl_sum2: of both, in one loop).
+template <int FL>
+__device__ __forceinline__ void fl_stage(double (&red)[2][FL][16], int ry, int cx, double s0, double s1) {
+  red[0][ry][cx] = s0;
+  red[1][ry][cx] = s1;
+  __syncthreads();
+}
+template <int FL>
+__device__ __forceinline__ double fl_sum(const double (&red)[2][FL][16], int stat, int cx) {
+  double t = 0.0;
+  for (int r = 0; r < FL; ++r) t += red[stat][r][cx];
+  return t;
+}
+template <int FL>
+__device__ __forceinline__ void fl_sum2(const double (&red)[2][FL][16], int cx, double& a, double& b) {
+  a = b = 0.0;
+  for (int r = 0; r < FL; ++r) {
+    a += red[0][r][cx];
+    b += red[1][r][cx];
+  }
+}
+// Coefficients of dx = A * dz + B * x + C from db = sum dz, dg = sum dz * xhat over the M rows of a channel (fp64).
+__device__ __forceinline__ void bn_bwd_coefs(double g, double is, double mu, double db, double dg, double M, float& A,
+                                             float& B, float& C) {
+  const double a = g * is;
+  const double b = -g * is * is * dg / M;
+  A = (float)a;
+  B = (float)b;
+  C = (float)(-g * is * db / M - b * mu);
+}
+
 // ---- wave / block reductions -------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -40,7 +40,7 @@ struct IGemmArgs {
   // batch-norm backward sums in the epilogue of an input gradient (asm_conv2d_dgrad_bnred): the tensor this launch writes is the
   // gradient dout of a conv -> BN [-> + shortcut] [-> ReLU] output; with red_y the STATS partials are not (sum y, sum y^2) but
   // (sum dz, sum dz * y), dz = bf16(dout) * [mask bit], y = that layer's pre-BN convolution output at the same element --
-  // what rowreduce_kernel<1> (bn.hip) reads dout and y again for.  asm_bn_bwd_finalize_raw turns sum dz * y into sum dz * xhat.
+  // what bn_bwd_reduce_kernel (bn.hip) reads dout and y again for.  asm_bn_bwd_finalize_raw turns sum dz * y into sum dz * xhat.
   const void* red_y;           // bf16 [M][ldy] or null
   const uint8_t* red_mask;     // packed ReLU mask [M][ldy / 8] or null (no ReLU: dz = dout)
   const void* pool_dy;   // bf16 [N][pool_Hp][pool_Wp][Co] or null

@@ -360,9 +360,9 @@ __global__ __launch_bounds__(256) void sk_bn_bwd_reduce_kernel(const bf16_t* __r
   const int C2 = 2 * g.F;
   const int fv = g.F >> 3;
   const int cv = vc >= fv ? vc - fv : vc;   // vector column inside dV
-  float s[8], ss[8];
+  float acc[2][8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) s[e] = ss[e] = 0.f;
+  for (int e = 0; e < 8; ++e) acc[0][e] = acc[1][e] = 0.f;
   if (active) {
     Coef8 k;
     load_coef(scale, shift, vc * 8, k);
@@ -394,28 +394,15 @@ __global__ __launch_bounds__(256) void sk_bn_bwd_reduce_kernel(const bf16_t* __r
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const float dz = (fy[e] * k.sc[e] + k.sh[e] > 0.f) ? (ab[e] * fg[e] + u[e]) : 0.f;
-          s[e] += dz;
-          ss[e] += dz * ((fy[e] - mu[e]) * is[e]);
+          acc[0][e] += dz;
+          acc[1][e] += dz * ((fy[e] - mu[e]) * is[e]);
         }
       }
     }
   }
-  const int ncol = g.vcols * 8;
-  if (active) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      red[(0 * g.rpb + rr) * ncol + vc * 8 + e] = s[e];
-      red[(1 * g.rpb + rr) * ncol + vc * 8 + e] = ss[e];
-    }
-  }
-  __syncthreads();
   const size_t prow = (size_t)n * g.chunks + blockIdx.x;
-  for (int i = tid; i < 2 * ncol; i += 256) {
-    const int which = i / ncol, col = i - which * ncol;
-    float acc = 0.f;
-    for (int r = 0; r < g.rpb; ++r) acc += red[(which * g.rpb + r) * ncol + col];
-    partial[(prow * 2 + which) * C2 + col] = acc;
-  }
+  row_lanes_sum<2>(red, acc, active, vc, rr, g.rpb, g.vcols * 8,
+                   [&](int which, int col, float v) { partial[(prow * 2 + which) * C2 + col] = v; });
 }
 
 // ---- factorised reduce + finalize ---------------------------------------------------------------------------------------
@@ -454,24 +441,13 @@ __global__ __launch_bounds__(1024) void sk_bn_bwd_finalize_kernel(const float* _
     }
     s1 *= (double)invstd[ch];     // xhat = (y - mean) * invstd
   }
-  red[0][ry][cx] = s0;
-  red[1][ry][cx] = s1;
-  __syncthreads();
+  fl_stage(red, ry, cx, s0, s1);
   if (ry == 0 && ch < C2) {
-    double db = 0.0, dg = 0.0;
-    for (int r = 0; r < 64; ++r) {
-      db += red[0][r][cx];
-      dg += red[1][r][cx];
-    }
+    double db, dg;
+    fl_sum2(red, cx, db, dg);
     dbeta[ch] = (float)db;
     dgamma[ch] = (float)dg;
-    const double M = (double)N * (double)HW;
-    const double g = gamma[ch], is = invstd[ch], mu = mean[ch];
-    const double A = g * is;
-    const double B = -g * is * is * dg / M;
-    coefA[ch] = (float)A;
-    coefB[ch] = (float)B;
-    coefC[ch] = (float)(-g * is * db / M - B * mu);
+    bn_bwd_coefs(gamma[ch], invstd[ch], mean[ch], db, dg, (double)N * (double)HW, coefA[ch], coefB[ch], coefC[ch]);
   }
 }
 

@@ -629,3 +629,62 @@ def test_bn_apply_dual_is_bit_identical_to_two_passes(hip_lib, M, Cn, relu):
   c = [t.cpu() for t in co]
   want = xa.float().cpu() * c[0] + c[1] + (xb.float().cpu() * c[2] + c[3]).to(BF).float()
   _close(y2, torch.relu(want) if relu else want, name='dual apply vs definition')
+
+
+@pytest.mark.parametrize('shape', [(3, 256, 256, 64), (3, 256, 256, 72)])
+def test_bn_apply_passes_over_more_than_one_grid_stride_trip(hip_lib, shape):
+  """The element-wise batch-norm passes cap their grid at 4096 blocks of 256 threads: these tensors (M * C / 8 > 2^20
+  vectors) need a second trip of the grid-stride loop, and with C / 8 = 9 the stride 2^20 is no multiple of C / 8, so a
+  thread changes channels between trips and re-derives its coefficients.  An apply pass is element-wise: the op on the
+  whole tensor must equal, bit for bit, the same op run image by image (one image = one trip) and concatenated."""
+  from assembled_cnn_amd import ops
+  from assembled_cnn_amd.ops import L, _ptr, _stream, check
+  N, H, W, Cn = shape
+  HW = H * W
+  assert N * HW * (Cn // 8) > 4096 * 256 >= HW * (Cn // 8)
+  g = torch.Generator(device='cuda').manual_seed(11)
+  xa = torch.randn((N * HW, Cn), generator=g, device='cuda').to(BF)
+  xb = (torch.randn((N * HW, Cn), generator=g, device='cuda') * 2 + 0.3).to(BF)
+  dy = torch.randn((N * HW, Cn), generator=g, device='cuda').to(BF)
+  half = torch.randn((N, H // 2, W // 2, Cn), generator=g, device='cuda').to(BF)
+  mask = torch.randint(0, 256, (N * HW, Cn // 8), generator=g, device='cuda', dtype=torch.uint8)
+  co = torch.randn((6, Cn), generator=g, device='cuda') * 0.5
+
+  def same(name, fn):
+    """fn(rows, n0, n1) -> tensors of images n0 .. n1 - 1; rows(t) = the rows of those images in a [N * HW, ...] tensor"""
+    def run(n0, n1):
+      out = fn(lambda t: t[n0 * HW:n1 * HW], n0, n1)
+      return out if isinstance(out, tuple) else (out,)
+    whole = run(0, N)
+    parts = [run(n, n + 1) for n in range(N)]
+    for i, w in enumerate(whole):
+      assert torch.equal(w, torch.cat([p[i] for p in parts])), '%s output %d' % (name, i)
+
+  same('bn_apply', lambda r, n0, n1: ops.bn_apply(r(xa), (n1 - n0) * HW, Cn, co[0], co[1], relu=True, want_mask=True))
+  same('bn_apply + residual', lambda r, n0, n1: ops.bn_apply(r(xa), (n1 - n0) * HW, Cn, co[0], co[1], residual=r(xb),
+                                                             res_mode=1, relu=True, want_mask=True))
+  same('bn_apply + upsampled residual', lambda r, n0, n1: ops.bn_apply(r(xa), (n1 - n0) * HW, Cn, co[0], co[1],
+                                                                       residual=half[n0:n1], res_mode=2, relu=True, H=H, W=W,
+                                                                       want_mask=True))
+  same('bn_apply_dual', lambda r, n0, n1: ops.bn_apply_dual(r(xa), r(xb), (n1 - n0) * HW, Cn, co[0], co[1], co[2], co[3],
+                                                            True, want_mask=True))
+
+  def bwd_apply(rk, want_dz):
+    yout = (None, xb, mask)[rk]          # nothing / a bf16 forward output / the packed ReLU mask
+    def fn(r, n0, n1):
+      dx = torch.empty_like(r(xa))
+      dz = torch.empty_like(dx) if want_dz else None
+      check(L().asm_bn_bwd_apply(_ptr(r(dy)), _ptr(r(xa)), _ptr(r(yout)) if rk else None, rk, (n1 - n0) * HW, Cn, _ptr(co[0]),
+                                 _ptr(co[1]), _ptr(co[2]), _ptr(dx), _ptr(dz), _stream()), 'bn_bwd_apply')
+      return (dx, dz) if want_dz else dx
+    return fn
+  for rk in (0, 1, 2):
+    for want_dz in (False, True):
+      same('bn_bwd_apply relu=%d dz=%d' % (rk, want_dz), bwd_apply(rk, want_dz))
+
+  def bwd_apply2(r, n0, n1):
+    dxa, dxb = torch.empty_like(r(xa)), torch.empty_like(r(xb))
+    check(L().asm_bn_bwd_apply2(_ptr(r(dy)), _ptr(r(xa)), _ptr(r(xb)), _ptr(r(mask)), (n1 - n0) * HW, Cn, _ptr(co), _ptr(dxa),
+                                _ptr(dxb), _stream()), 'bn_bwd_apply2')
+    return dxa, dxb
+  same('bn_bwd_apply2', bwd_apply2)

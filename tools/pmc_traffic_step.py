@@ -40,7 +40,7 @@ def conv3x3(k):
 
 
 def bn_family(k):
-  return k.startswith(('bn_', 'rowreduce', 'partials_compact', 'sk_bn_bwd'))
+  return k.startswith(('bn_', 'partials_compact', 'sk_bn_bwd'))
 
 
 def main():
