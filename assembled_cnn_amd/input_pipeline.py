@@ -20,6 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import autoaugment as _aa
 from . import ops
 from .lib import ImageDesc
 
@@ -179,9 +180,16 @@ def pack_batch(images: Sequence[np.ndarray], windows: Sequence[dict], out_h: int
 def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, image_size: int = 224,
                      preprocessing_type: str = 'imagenet', use_random_crop: bool = True,
                      rng: Optional[np.random.Generator] = None, subtract_mean: bool = True,
-                     windows: Optional[List[dict]] = None) -> torch.Tensor:
+                     windows: Optional[List[dict]] = None, autoaugment_type: Optional[str] = None,
+                     augment: Optional[np.ndarray] = None) -> torch.Tensor:
   """The imagenet* branches of data_util.preprocess_image for a batch of decoded images; float32 NHWC on `device`.
-  `windows` overrides the sampled / computed windows (tests share them with the oracle)."""
+  `windows` overrides the sampled / computed windows (tests share them with the oracle).
+  `autoaugment_type` ('imagenet' | 'good' | 'v0' | 'test'): in training mode the policy runs on the resized image, clipped
+  and cast to uint8, before the mean subtraction (imagenet_preprocessing.py:280-289), as a second launch; the reference
+  applies it in the training branch only, so evaluation ignores it.  `augment` overrides the sampled descriptors
+  (autoaugment.sample / autoaugment.descriptor), the way `windows` overrides the windows."""
+  if autoaugment_type is not None:
+    _aa.check_policy_name(autoaugment_type)
   side, crop_type = output_size_and_crop_type(preprocessing_type, is_training, image_size)
   if windows is None:
     if is_training:
@@ -196,4 +204,14 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
     ev = torch.cuda.Event()
     ev.record()
     _STAGING['event'] = ev
-  return ops.resize_crop_flip(bd, td, len(images), side, side, subtract_mean)
+  if autoaugment_type is None or not is_training:
+    return ops.resize_crop_flip(bd, td, len(images), side, side, subtract_mean)
+  if augment is None:
+    rng = rng if rng is not None else np.random.default_rng()
+    augment = _aa.sample(autoaugment_type, len(images), side, side, rng)
+  _aa.validate(augment, side, side)
+  if len(augment) != len(images):
+    raise ValueError('one augmentation descriptor per image')
+  ad = torch.from_numpy(np.ascontiguousarray(augment).view(np.uint8).copy()).to(dev, non_blocking=False)
+  resized = ops.resize_crop_flip(bd, td, len(images), side, side, False)
+  return ops.autoaugment(resized, ad, subtract_mean)

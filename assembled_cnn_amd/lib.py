@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ASM_HIP_LIB') or os.path.join(HERE, 'libasm_hip.so')
 
 ASM_OK, ASM_EINVAL, ASM_ENOTSUP, ASM_EHIP = 0, -1, -2, -3
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class AsmError(RuntimeError):
@@ -25,6 +25,19 @@ class ImageDesc(C.Structure):
               ('crop_y', C.c_int32), ('crop_x', C.c_int32), ('crop_h', C.c_int32), ('crop_w', C.c_int32),
               ('resize_h', C.c_int32), ('resize_w', C.c_int32), ('out_y', C.c_int32), ('out_x', C.c_int32),
               ('flip', C.c_int32), ('reserved', C.c_int32)]
+
+
+class AugmentOp(C.Structure):
+  """struct asm_augment_op"""
+  _fields_ = [('op', C.c_int32), ('a', C.c_int32), ('b', C.c_int32), ('reserved', C.c_int32), ('f', C.c_float * 6)]
+
+
+class AugmentDesc(C.Structure):
+  """struct asm_augment_desc"""
+  _fields_ = [('slot', AugmentOp * 2)]
+
+
+assert C.sizeof(AugmentOp) == 40 and C.sizeof(AugmentDesc) == 80
 
 
 class ConvDesc(C.Structure):
@@ -208,6 +221,8 @@ SIGNATURES = {
     'asm_dense_small': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     'asm_dense_small_wgrad': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
     'asm_resize_crop_flip': (_I, [_P, C.c_int64, _P, _I, _I, _I, _I, _P, _P]),
+    'asm_autoaugment_workspace_bytes': (_I, [_I, _I, _I, C.POINTER(C.c_int64)]),
+    'asm_autoaugment': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, C.c_int64, _P]),
     'asm_model_plan': (_I, [C.POINTER(ModelCfg), _I, _I, _I, C.POINTER(PlanEntry), _I, C.POINTER(PlanSummary)]),
 }
 

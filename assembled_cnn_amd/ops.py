@@ -965,6 +965,25 @@ def resize_crop_flip(src_u8, descs_dev, n, out_h, out_w, subtract_mean):
   return out
 
 
+def autoaugment(images_f32, descs_dev, subtract_mean):
+  """images_f32: float32 [n, H, W, 3] (resize_crop_flip's output without the mean subtraction); descs_dev: uint8 device
+  view of n packed struct asm_augment_desc (80 bytes each; autoaugment.sample / autoaugment.descriptor).  Returns the
+  augmented batch, float32 [n, H, W, 3], integer-valued, minus CHANNEL_MEANS if subtract_mean.  One launch."""
+  if images_f32.dim() != 4 or images_f32.shape[3] != 3 or images_f32.dtype != F32:
+    raise ValueError('images must be float32 [n, H, W, 3]')
+  n, H, W = int(images_f32.shape[0]), int(images_f32.shape[1]), int(images_f32.shape[2])
+  if descs_dev.numel() != 80 * n or descs_dev.dtype != torch.uint8:
+    raise ValueError('descriptor table must hold %d bytes' % (80 * n))
+  out = torch.empty_like(images_f32)
+  if n:
+    need = C.c_int64(0)
+    check(L().asm_autoaugment_workspace_bytes(n, H, W, C.byref(need)), 'autoaugment_workspace_bytes')
+    ws = _workspace(need.value, images_f32)
+    check(L().asm_autoaugment(_ptr(images_f32), _ptr(descs_dev), n, H, W, 1 if subtract_mean else 0, _ptr(out), _ptr(ws),
+                              need.value, _stream()), 'autoaugment')
+  return out
+
+
 # ---------------------------------------------------------------------------------------------------
 # retrieval evaluation (metric/recall_metric.py)
 # ---------------------------------------------------------------------------------------------------

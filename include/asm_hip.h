@@ -35,7 +35,7 @@ extern "C" {
 #define ASM_ENOTSUP (-2)
 #define ASM_EHIP (-3)
 
-#define ASM_ABI_VERSION 8
+#define ASM_ABI_VERSION 9
 
 const char* asm_last_error(void);
 int asm_abi_version(void);
@@ -572,6 +572,40 @@ typedef struct asm_image_desc {
 } asm_image_desc;                          /* 56 bytes */
 int asm_resize_crop_flip(const uint8_t* src, int64_t src_bytes, const asm_image_desc* descs, int N,
                          int out_h, int out_w, int subtract_mean, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * AutoAugment (preprocessing/autoaugment.py), applied where the reference applies it: after the resize, on
+ * clip(image, 0, 255) cast to uint8, before the mean subtraction (preprocessing/imagenet_preprocessing.py:280-289).
+ *   in   float32 [N][H][W][3]: what asm_resize_crop_flip(..., subtract_mean = 0) writes
+ *   out  float32 [N][H][W][3]: integer-valued, minus CHANNEL_MEANS if subtract_mean; feeds asm_mixup_meansub or the
+ *        trainer exactly as the resize output does
+ * Every image carries one descriptor: the two ops of the sub-policy drawn for it, applied in order.  ALL randomness is
+ * resolved by the caller into the descriptor (which sub-policy, whether a slot fires, the sign of rotate / shear /
+ * translate, the cutout centre), and so is all transcendental math: the kernel never calls sin or cos.
+ *   op   0 = slot not applied; 1..16 = the names of NAME_TO_FUNC (:682-699) in that order:
+ *        1 AutoContrast  2 Equalize  3 Invert  4 Rotate  5 Posterize  6 Solarize  7 SolarizeAdd  8 Color  9 Contrast
+ *        10 Brightness  11 Sharpness  12 ShearX  13 ShearY  14 TranslateX  15 TranslateY  16 Cutout
+ *   a, b integer arguments: Posterize a = shift = 8 - bits (0..8; 8 gives 0); Solarize a = threshold (0..256, compared
+ *        as int); SolarizeAdd a = addition (-255..255), b = threshold; Cutout a = pad size (0 fills nothing),
+ *        b = centre_y << 16 | centre_x
+ *   f    Color / Contrast / Brightness / Sharpness: f[0] = blend factor.  Rotate / Shear / Translate: the six affine
+ *        coefficients -- output pixel (x, y) reads input (round(f0 x + f1 y + f2), round(f3 x + f4 y + f5)), rounding half
+ *        away from zero, a sample outside the image becomes 128 (tf.contrib.image.transform NEAREST + wrap / unwrap)
+ * An op id or argument outside these ranges leaves the image unchanged for that slot (memory safety only: the host mirror,
+ * assembled_cnn_amd/autoaugment.py, validates and raises).  One launch for the batch, one workgroup per image; integer
+ * histograms, no floating-point atomics: the output of an image depends on nothing but that image and its descriptor.
+ * workspace: asm_autoaugment_workspace_bytes (two uint8 planes per image).  H, W <= 32767, H * W < 2^24.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct asm_augment_op {
+  int32_t op, a, b, reserved;
+  float f[6];
+} asm_augment_op;                          /* 40 bytes */
+typedef struct asm_augment_desc {
+  asm_augment_op slot[2];
+} asm_augment_desc;                        /* 80 bytes, one per image */
+int asm_autoaugment_workspace_bytes(int N, int H, int W, int64_t* bytes);
+int asm_autoaugment(const float* in, const asm_augment_desc* descs, int N, int H, int W, int subtract_mean, float* out,
+                    void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Flag surface and topology planner.  asm_model_cfg carries the flags of nets/hparams_config.py:30-292 (+

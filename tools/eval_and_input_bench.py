@@ -5,7 +5,7 @@ import os, sys, time
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from assembled_cnn_amd import input_pipeline as P, ops
+from assembled_cnn_amd import autoaugment as A, input_pipeline as P, ops
 from assembled_cnn_amd.train import HParams, Trainer
 
 
@@ -31,6 +31,16 @@ for training, side, ptype in ((True, 224, 'imagenet'), (False, 256, 'imagenet_22
   t0 = time.time(); P.preprocess_batch(imgs, training, 'cuda', preprocessing_type=ptype, windows=wins); torch.cuda.synchronize()
   print('input tail %-5s %dx%d: kernel %.3f ms for 256 images (%.0f k img/s, %.2f TB/s out+in), host pack+H2D+kernel %.1f ms'
         % ('train' if training else 'eval', side, side, ms, 256 / ms, (out_bytes + buf.numel()) / ms / 1e9, 1e3 * (time.time() - t0)))
+  if training:    # AutoAugment on the same batch, in the same run: the recipe's policy as sampled, then the per-op worst cases
+    resized = ops.resize_crop_flip(bd, td, len(imgs), side, side, False)
+    both = lambda *spec: np.repeat(A.descriptor([spec, spec], side, side), len(imgs))
+    for what, descs in (('imagenet policy, sampled', A.sample('imagenet', len(imgs), side, side, rng)),
+                        ('both slots Equalize', both('Equalize')), ('both slots Rotate 30', both('Rotate', 30.0)),
+                        ('both slots Sharpness 1.9', both('Sharpness', 1.9)), ('pass-through', np.repeat(A.descriptor([], side, side), len(imgs)))):
+      ad = torch.from_numpy(descs.view(np.uint8).copy()).cuda()
+      ms_aa = ev(lambda: ops.autoaugment(resized, ad, True))
+      print('autoaugment %-26s %dx%d: kernel %.3f ms for 256 images (%.0f k img/s; resize_crop_flip above: %.3f ms)'
+            % (what, side, side, ms_aa, 256 / ms_aa, ms))
 
 for name, kw, side in (('ResNet-50 v1.5 eval 224', dict(resnet_version=1), 224),
                        ('Assemble-ResNet-50 eval 256', dict(resnet_version=2, use_sk_block=True, anti_alias_type='sconv',
