@@ -1,0 +1,271 @@
+// Baseline JPEG entropy decode (ITU-T T.81 F.2.2) of one restart interval, as plain functions shared by the device
+// kernel (jpeg.hip) and a host program (tools/probes/jpeg_entropy_host.cpp, built with the address and undefined-behaviour
+// sanitizers): the same text is compiled for both, so what the host program proves about bounds holds for the kernel.
+//
+// Rules: canonical codes of 1..16 bits; a 9-bit lookup, longer codes through maxcode / valoff; EXTEND;
+// one DC predictor per component, zero at the start of the interval; EOB and ZRL; FF 00 -> FF; pad bits ignored.
+// Safety: every byte read lies in [begin, end); every coefficient index is <= 63; every block index lies inside the
+// component's block grid; a violation returns a non-zero ASM_JPEG_E* and stops.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+#include "../../include/asm_hip.h"
+
+#if defined(__HIPCC__)
+#define JPEG_HD __host__ __device__ inline
+#else
+#define JPEG_HD inline
+#endif
+
+#define JPEG_LOOK_BITS 9
+
+// decode form of one Huffman table: look[prefix] = length << 8 | symbol for codes of <= 9 bits (0: longer, or none)
+struct jpeg_dtab {
+  uint16_t look[1 << JPEG_LOOK_BITS];
+  int32_t maxcode[17];       // [l] largest code of length l, -1 if there is none
+  int32_t valoff[17];        // [l] index in vals of the first code of length l, minus that code
+  uint8_t vals[256];
+};
+
+// geometry of one image as the entropy decoder needs it
+struct jpeg_geom {
+  int ncomp;
+  int mcus_x, n_mcus;        // MCUs per row, MCUs in the image
+  int ch[3], cv[3];          // blocks per MCU of each component, horizontally and vertically
+  int bw[3];                 // blocks per row of each component's (padded) grid
+  int64_t base[3];           // first coefficient of each component, relative to the image's first
+  int64_t n_coefs;           // all components
+};
+
+// T.81 figure A.6, index -> position in the 8x8 block
+#define JPEG_ZIGZAG_INIT                                                                                            \
+  {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, \
+   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
+
+// false: the descriptor's geometry is not one this decoder handles
+JPEG_HD bool jpeg_make_geom(const asm_jpeg_desc& d, jpeg_geom* g) {
+  if (d.width < 1 || d.height < 1 || d.width > 8192 || d.height > 8192) return false;
+  if (d.ncomp != 1 && d.ncomp != 3) return false;
+  const int hs = d.ncomp == 1 ? 1 : d.hs, vs = d.ncomp == 1 ? 1 : d.vs;
+  if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return false;
+  if (d.hs != hs || d.vs != vs) return false;
+  if (d.mcus_x != (d.width + 8 * hs - 1) / (8 * hs) || d.mcus_y != (d.height + 8 * vs - 1) / (8 * vs)) return false;
+  g->ncomp = d.ncomp;
+  g->mcus_x = d.mcus_x;
+  g->n_mcus = d.mcus_x * d.mcus_y;
+  int64_t at = 0;
+  for (int c = 0; c < 3; ++c) {
+    g->ch[c] = c == 0 ? hs : 1;
+    g->cv[c] = c == 0 ? vs : 1;
+    g->bw[c] = d.mcus_x * g->ch[c];
+    g->base[c] = at;
+    if (c < d.ncomp) at += (int64_t)g->bw[c] * (d.mcus_y * g->cv[c]) * 64;
+  }
+  g->n_coefs = at;
+  return true;
+}
+
+// maxcode / valoff / vals of a table (T.81 F.2.2.3, figure F.15); any bits[] is safe: indices into vals are masked
+JPEG_HD void jpeg_dtab_prepare(const asm_jpeg_huff& h, jpeg_dtab* t) {
+  int code = 0, k = 0;
+  t->maxcode[0] = -1;
+  t->valoff[0] = 0;
+  for (int l = 1; l <= 16; ++l) {
+    const int n = h.bits[l - 1];
+    t->valoff[l] = k - code;
+    t->maxcode[l] = n ? code + n - 1 : -1;
+    code = (code + n) << 1;
+    k += n;
+  }
+  for (int i = 0; i < 256; ++i) t->vals[i] = h.vals[i];
+}
+
+// the code that starts the 16 bits `peek` (first bit = bit 15), lengths lo..hi: length << 8 | symbol, 0 if none
+JPEG_HD unsigned jpeg_code_lookup(const jpeg_dtab* t, unsigned peek, int lo, int hi) {
+  for (int l = lo; l <= hi; ++l) {
+    const int code = (int)(peek >> (16 - l));
+    if (code <= t->maxcode[l]) return ((unsigned)l << 8) | t->vals[(t->valoff[l] + code) & 255];
+  }
+  return 0;
+}
+
+JPEG_HD void jpeg_dtab_fill_look(jpeg_dtab* t, int first, int step) {
+  for (int i = first; i < (1 << JPEG_LOOK_BITS); i += step)
+    t->look[i] = (uint16_t)jpeg_code_lookup(t, (unsigned)i << (16 - JPEG_LOOK_BITS), 1, JPEG_LOOK_BITS);
+}
+
+// bit reader over [p, end): `n` bits are held in the low end of buf, the last `pad` of them are zeros invented after the
+// end of the data (or after a marker); consuming one of those is the overrun error
+struct jpeg_bits {
+  const uint8_t* p;
+  const uint8_t* end;
+  uint64_t buf, word;
+  int n, pad, wn;
+  bool done;
+};
+
+JPEG_HD void jpeg_bits_init(jpeg_bits* b, const uint8_t* p, const uint8_t* end) {
+  b->p = p;
+  b->end = end;
+  b->buf = b->word = 0;
+  b->n = b->pad = b->wn = 0;
+  b->done = false;
+}
+
+// next byte of the interval, -1 at its end; reads eight bytes at a time while eight remain
+JPEG_HD int jpeg_next_byte(jpeg_bits* b) {
+  if (b->wn == 0) {
+    const int64_t left = b->end - b->p;
+    if (left >= 8) {
+      memcpy(&b->word, b->p, 8);
+      b->p += 8;
+      b->wn = 8;
+    } else if (left > 0) {
+      b->word = *b->p++;
+      b->wn = 1;
+    } else {
+      return -1;
+    }
+  }
+  const int v = (int)(b->word & 255u);
+  b->word >>= 8;
+  --b->wn;
+  return v;
+}
+
+JPEG_HD void jpeg_bits_fill(jpeg_bits* b) {
+  while (b->n <= 56) {
+    int v = b->done ? -1 : jpeg_next_byte(b);
+    if (v == 0xFF) {
+      const int s = jpeg_next_byte(b);       // FF 00 is the data byte FF; FF + anything else (or nothing) ends the data
+      if (s != 0) v = -1;
+    }
+    if (v < 0) {
+      b->done = true;
+      b->pad += 8;
+      v = 0;
+    }
+    b->buf = (b->buf << 8) | (uint64_t)v;
+    b->n += 8;
+  }
+}
+
+JPEG_HD unsigned jpeg_bits_peek16(const jpeg_bits* b) { return (unsigned)(b->buf >> (b->n - 16)) & 0xFFFFu; }
+
+// one Huffman symbol; -1 and *err set if no code matches or the data ran out
+JPEG_HD int jpeg_decode_symbol(jpeg_bits* b, const jpeg_dtab* t, int* err) {
+  if (b->n < 32) jpeg_bits_fill(b);
+  const unsigned peek = jpeg_bits_peek16(b);
+  unsigned e = t->look[peek >> (16 - JPEG_LOOK_BITS)];
+  if (e == 0) e = jpeg_code_lookup(t, peek, JPEG_LOOK_BITS + 1, 16);
+  if (e == 0) {
+    *err |= ASM_JPEG_EBADCODE;
+    return -1;
+  }
+  b->n -= (int)(e >> 8);
+  if (b->n < b->pad) {
+    *err |= ASM_JPEG_EOVERRUN;
+    return -1;
+  }
+  return (int)(e & 255u);
+}
+
+// s bits (1..15; the caller filled at least 32 before the symbol) -> EXTEND(value, s) (T.81 F.2.2.1)
+JPEG_HD int jpeg_receive_extend(jpeg_bits* b, int s, int* err) {
+  b->n -= s;
+  if (b->n < b->pad) {
+    *err |= ASM_JPEG_EOVERRUN;
+    return 0;
+  }
+  const int v = (int)((b->buf >> b->n) & ((1u << s) - 1u));
+  return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
+}
+
+// Decode MCUs [first_mcu, first_mcu + n_mcus) of one image from the bytes [begin, end) into coefs (the image's own region
+// of g.n_coefs int16, already zero).  dc[c] / ac[c]: the tables of component c.  Returns 0 or ASM_JPEG_E*.
+JPEG_HD int jpeg_decode_interval(const uint8_t* begin, const uint8_t* end, const jpeg_geom& g, const jpeg_dtab* const* dc,
+                                 const jpeg_dtab* const* ac, const uint8_t* zigzag, int first_mcu, int n_mcus,
+                                 int16_t* coefs) {
+  if (first_mcu < 0 || n_mcus < 1 || first_mcu > g.n_mcus - n_mcus) return ASM_JPEG_EDESC;
+  jpeg_bits b;
+  jpeg_bits_init(&b, begin, end);
+  int err = 0;
+  int pred[3] = {0, 0, 0};
+  int my = first_mcu / g.mcus_x, mx = first_mcu - my * g.mcus_x;
+  for (int m = 0; m < n_mcus; ++m) {
+    for (int c = 0; c < g.ncomp; ++c) {
+      for (int v = 0; v < g.cv[c]; ++v) {
+        for (int h = 0; h < g.ch[c]; ++h) {
+          const int64_t blk = (int64_t)(my * g.cv[c] + v) * g.bw[c] + (mx * g.ch[c] + h);
+          const int64_t at = g.base[c] + blk * 64;
+          if (at < 0 || at + 64 > g.n_coefs) return err | ASM_JPEG_EDESC;
+          int16_t* out = coefs + at;
+          int s = jpeg_decode_symbol(&b, dc[c], &err);
+          if (s < 0) return err;
+          if (s > 15) return err | ASM_JPEG_EBADCODE;
+          if (s) {
+            const int diff = jpeg_receive_extend(&b, s, &err);
+            if (err) return err;
+            pred[c] = (int16_t)(pred[c] + diff);
+          }
+          if (pred[c]) out[0] = (int16_t)pred[c];
+          for (int k = 1; k < 64; ++k) {
+            const int rs = jpeg_decode_symbol(&b, ac[c], &err);
+            if (rs < 0) return err;
+            const int r = rs >> 4;
+            s = rs & 15;
+            if (s == 0) {
+              if (r != 15) break;      // EOB
+              k += 15;                 // ZRL: sixteen zeros
+              continue;
+            }
+            k += r;
+            if (k > 63) return err | ASM_JPEG_EBADCODE;
+            const int val = jpeg_receive_extend(&b, s, &err);
+            if (err) return err;
+            out[zigzag[k]] = (int16_t)val;
+          }
+        }
+      }
+    }
+    if (++mx == g.mcus_x) {
+      mx = 0;
+      ++my;
+    }
+  }
+  return 0;
+}
+
+// intervals a workgroup expects for the image: one without DRI, else one per restart_interval MCUs
+JPEG_HD int jpeg_expected_intervals(const asm_jpeg_desc& d, const jpeg_geom& g) {
+  return d.restart_interval > 0 ? (int)(((int64_t)g.n_mcus + d.restart_interval - 1) / d.restart_interval) : 1;
+}
+
+// What lane `lane` of `lanes` does for image `img`: its share (k = lane, lane + lanes, ...) of the image's rows of the
+// interval table, each checked against the descriptor before a byte of it is read.  tab: dc 0, dc 1, ac 0, ac 1.
+// The caller has checked the descriptor itself (geometry, offsets, selectors < 2, first_interval + n_intervals in range).
+JPEG_HD int jpeg_decode_lane(const uint8_t* files, const asm_jpeg_desc& d, const jpeg_geom& g,
+                             const asm_jpeg_interval* intervals, int img, const jpeg_dtab* tab, const uint8_t* zigzag,
+                             int lane, int lanes, int16_t* coefs) {
+  const jpeg_dtab* dc[3] = {&tab[d.dcsel[0] & 1], &tab[d.dcsel[1] & 1], &tab[d.dcsel[2] & 1]};
+  const jpeg_dtab* ac[3] = {&tab[2 + (d.acsel[0] & 1)], &tab[2 + (d.acsel[1] & 1)], &tab[2 + (d.acsel[2] & 1)]};
+  int err = 0;
+  for (int k = lane; k < d.n_intervals; k += lanes) {
+    const asm_jpeg_interval iv = intervals[d.first_interval + k];
+    const int first = d.restart_interval > 0 ? k * d.restart_interval : 0;
+    const int left = g.n_mcus - first;
+    const int count = d.restart_interval > 0 ? (d.restart_interval < left ? d.restart_interval : left) : g.n_mcus;
+    const bool last = k == d.n_intervals - 1;
+    if (iv.image != img || iv.byte_begin < d.scan_offset || iv.byte_end < iv.byte_begin ||
+        iv.byte_end > d.scan_offset + d.scan_bytes) {
+      err |= ASM_JPEG_EDESC;
+      continue;
+    }
+    if (iv.first_mcu != first || iv.n_mcus != count || iv.rst != (last ? -1 : (k & 7))) {
+      err |= ASM_JPEG_ERESTART;
+      continue;
+    }
+    err |= jpeg_decode_interval(files + iv.byte_begin, files + iv.byte_end, g, dc, ac, zigzag, first, count, coefs);
+  }
+  return err;
+}

@@ -2,9 +2,11 @@
 
 Mirrors ``utils/data_util.py:267-386 preprocess_image`` + ``preprocessing/imagenet_preprocessing.py:269-313`` from
 the point where the reference holds a decoded uint8 image: window selection (random box / whole image), flip,
-legacy bilinear resize, central crop and mean subtraction.  JPEG decoding and record parsing stay on the host
-(out of scope); the window arithmetic below is host integer/float32 math done exactly as the reference's graph
-does it, and the pixel work is one HIP launch for the whole ragged batch (ops.resize_crop_flip).
+legacy bilinear resize, central crop and mean subtraction.  Record parsing stays on the host (out of scope); the
+window arithmetic below is host integer/float32 math done exactly as the reference's graph does it, and the pixel work
+is one HIP launch for the whole ragged batch (ops.resize_crop_flip).  An entry of the batch may also be the ENCODED file
+(tf.image.decode_jpeg / decode_and_crop_jpeg, imagenet_preprocessing.py:81,92-93,296): those are decoded on the device
+(jpeg.py, csrc/jpeg.hip) straight into the packed buffer the resize reads.
 
 The output of ``preprocess_batch(..., subtract_mean=True)`` is what the reference's ``preprocess_image`` returns
 before ``tf.cast(image, dtype)`` (float32, mean-subtracted, NHWC) and feeds ``Model.__call__`` directly; with
@@ -21,6 +23,7 @@ import numpy as np
 import torch
 
 from . import autoaugment as _aa
+from . import jpeg as _jpeg
 from . import ops
 from .lib import ImageDesc
 
@@ -144,6 +147,40 @@ def _staging(nbytes: int, pin: bool) -> torch.Tensor:
   return cur
 
 
+def _fill_table(desc: np.ndarray, offs, sizes, windows, out_h: int, out_w: int):
+  """rows [0, n) of a struct asm_image_desc table from the slot offsets, the (height, width) of every image and its window;
+  raises ValueError for a window that does not fit"""
+  n = len(sizes)
+  for (h, w), win in zip(sizes, windows):
+    _validate(win, h, w, out_h, out_w)
+  if n:
+    desc['src_offset'][:n] = offs
+    desc['Hs'][:n] = [s[0] for s in sizes]
+    desc['Ws'][:n] = [s[1] for s in sizes]
+    for f in ('crop_y', 'crop_x', 'crop_h', 'crop_w', 'resize_h', 'resize_w', 'out_y', 'out_x', 'flip'):
+      desc[f][:n] = [int(w[f]) for w in windows]
+
+
+def _staging_in_flight(dev):
+  """an asynchronous H2D copy out of the pinned staging buffer was just enqueued: the next user waits for it"""
+  if dev.type == 'cuda':
+    ev = torch.cuda.Event()
+    ev.record()
+    _STAGING['event'] = ev
+
+
+def stage_into(region: torch.Tensor, arrays, offsets):
+  """Decoded uint8 arrays -> the staging buffer at `offsets` -> ONE host-to-device copy into `region` (a uint8 device view
+  whose first byte is offset 0): the decoded entries of a batch that is otherwise decoded on the device."""
+  pin = region.is_cuda
+  buf = _staging(max(region.numel(), 16), pin)
+  host = buf.numpy()
+  for a, o in zip(arrays, offsets):
+    host[int(o):int(o) + a.size] = a.reshape(-1)
+  region.copy_(buf[:region.numel()], non_blocking=True)
+  _staging_in_flight(region.device)
+
+
 def pack_batch(images: Sequence[np.ndarray], windows: Sequence[dict], out_h: int, out_w: int, pin: bool = False):
   """Decoded images (uint8 [H, W, 3], any sizes) -> (packed uint8 buffer, descriptor table bytes) as CPU tensors
   (pinned when ``pin``).  One memcpy per image into the staging buffer and a vectorised descriptor table: ~10 GB/s
@@ -163,34 +200,74 @@ def pack_batch(images: Sequence[np.ndarray], windows: Sequence[dict], out_h: int
   dst = buf.numpy()
   table = torch.zeros(max(n, 1) * 56, dtype=torch.uint8, pin_memory=pin)
   desc = table.numpy().view(_DESC_DTYPE)
-  for k, (im, win) in enumerate(zip(images, windows)):
-    _validate(win, im.shape[0], im.shape[1], out_h, out_w)
+  _fill_table(desc, offs, [im.shape[:2] for im in images], windows, out_h, out_w)
+  for k, im in enumerate(images):
     o = int(offs[k])
     dst[o:o + im.size] = im.reshape(-1)                                       # one memcpy (copies if not contiguous)
-  if n:
-    desc['src_offset'][:n] = offs
-    desc['Hs'][:n] = [im.shape[0] for im in images]
-    desc['Ws'][:n] = [im.shape[1] for im in images]
-    for f in ('crop_y', 'crop_x', 'crop_h', 'crop_w', 'resize_h', 'resize_w', 'out_y', 'out_x', 'flip'):
-      desc[f][:n] = [int(w[f]) for w in windows]
   buf = buf[:max(total, 16)]
   return buf, table[:56 * n]
+
+
+def _augment_tail(bd, td, n, side, is_training, dev, rng, subtract_mean, autoaugment_type, augment):
+  """resize (+ AutoAugment in training) of a packed device buffer: the tail of preprocess_batch"""
+  if autoaugment_type is None or not is_training:
+    return ops.resize_crop_flip(bd, td, n, side, side, subtract_mean)
+  if augment is None:
+    rng = rng if rng is not None else np.random.default_rng()
+    augment = _aa.sample(autoaugment_type, n, side, side, rng)
+  _aa.validate(augment, side, side)
+  if len(augment) != n:
+    raise ValueError('one augmentation descriptor per image')
+  ad = torch.from_numpy(np.ascontiguousarray(augment).view(np.uint8).copy()).to(dev, non_blocking=False)
+  resized = ops.resize_crop_flip(bd, td, n, side, side, False)
+  return ops.autoaugment(resized, ad, subtract_mean)
+
+
+def _preprocess_encoded(images, is_training, device, side, crop_type, use_random_crop, rng, subtract_mean, windows,
+                        autoaugment_type, augment, dct_method, jpeg_fallback):
+  """preprocess_batch for a batch with encoded files in it: the files are decoded on the device into their slots of the
+  packed buffer, decoded arrays (given, or returned by the fallback) are copied into theirs; same windows, same table."""
+  _jpeg.check_dct_method(dct_method)
+  n = len(images)
+  pk = _jpeg.pack(images, jpeg_fallback)
+  if windows is None:
+    if is_training:
+      rng = rng if rng is not None else np.random.default_rng()
+      windows = [train_window(h, w, side, side, rng, use_random_crop) for h, w in pk.sizes]
+    else:
+      windows = [eval_window(h, w, side, side, crop_type) for h, w in pk.sizes]
+  if n != len(windows):
+    raise ValueError('one window per image')
+  desc = np.zeros(n, dtype=_DESC_DTYPE)
+  _fill_table(desc, pk.offsets, pk.sizes, windows, side, side)
+  dev = torch.device(device)
+  bd = _jpeg.decode_packed(pk, dev)[0]
+  td = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev, non_blocking=False)
+  return _augment_tail(bd, td, n, side, is_training, dev, rng, subtract_mean, autoaugment_type, augment)
 
 
 def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, image_size: int = 224,
                      preprocessing_type: str = 'imagenet', use_random_crop: bool = True,
                      rng: Optional[np.random.Generator] = None, subtract_mean: bool = True,
                      windows: Optional[List[dict]] = None, autoaugment_type: Optional[str] = None,
-                     augment: Optional[np.ndarray] = None) -> torch.Tensor:
+                     augment: Optional[np.ndarray] = None, dct_method: str = '',
+                     jpeg_fallback=None) -> torch.Tensor:
   """The imagenet* branches of data_util.preprocess_image for a batch of decoded images; float32 NHWC on `device`.
   `windows` overrides the sampled / computed windows (tests share them with the oracle).
   `autoaugment_type` ('imagenet' | 'good' | 'v0' | 'test'): in training mode the policy runs on the resized image, clipped
   and cast to uint8, before the mean subtraction (imagenet_preprocessing.py:280-289), as a second launch; the reference
   applies it in the training branch only, so evaluation ignores it.  `augment` overrides the sampled descriptors
-  (autoaugment.sample / autoaugment.descriptor), the way `windows` overrides the windows."""
+  (autoaugment.sample / autoaugment.descriptor), the way `windows` overrides the windows.
+  An entry of `images` that is bytes, a bytearray or a 1-D uint8 array is an encoded JPEG file: it is decoded on the device
+  (`dct_method` '' or 'INTEGER_ACCURATE'; 'INTEGER_FAST' raises NotImplementedError), its size for the window arithmetic
+  comes from its header, and a file of a kind the device does not decode goes through `jpeg_fallback(bytes) -> uint8
+  [H, W, 3]` (NotImplementedError without one).  A training crop is a window of the full decode."""
   if autoaugment_type is not None:
     _aa.check_policy_name(autoaugment_type)
   side, crop_type = output_size_and_crop_type(preprocessing_type, is_training, image_size)
+  if any(_jpeg.is_encoded(im) for im in images):
+    return _preprocess_encoded(images, is_training, device, side, crop_type, use_random_crop, rng, subtract_mean, windows,
+                               autoaugment_type, augment, dct_method, jpeg_fallback)
   if windows is None:
     if is_training:
       rng = rng if rng is not None else np.random.default_rng()
@@ -200,18 +277,5 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
   dev = torch.device(device)
   buf, table = pack_batch(images, windows, side, side, pin=dev.type == 'cuda')
   bd, td = buf.to(dev, non_blocking=True), table.to(dev, non_blocking=True)
-  if dev.type == 'cuda':
-    ev = torch.cuda.Event()
-    ev.record()
-    _STAGING['event'] = ev
-  if autoaugment_type is None or not is_training:
-    return ops.resize_crop_flip(bd, td, len(images), side, side, subtract_mean)
-  if augment is None:
-    rng = rng if rng is not None else np.random.default_rng()
-    augment = _aa.sample(autoaugment_type, len(images), side, side, rng)
-  _aa.validate(augment, side, side)
-  if len(augment) != len(images):
-    raise ValueError('one augmentation descriptor per image')
-  ad = torch.from_numpy(np.ascontiguousarray(augment).view(np.uint8).copy()).to(dev, non_blocking=False)
-  resized = ops.resize_crop_flip(bd, td, len(images), side, side, False)
-  return ops.autoaugment(resized, ad, subtract_mean)
+  _staging_in_flight(dev)
+  return _augment_tail(bd, td, len(images), side, is_training, dev, rng, subtract_mean, autoaugment_type, augment)

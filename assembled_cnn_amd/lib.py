@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ASM_HIP_LIB') or os.path.join(HERE, 'libasm_hip.so')
 
 ASM_OK, ASM_EINVAL, ASM_ENOTSUP, ASM_EHIP = 0, -1, -2, -3
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class AsmError(RuntimeError):
@@ -38,6 +38,34 @@ class AugmentDesc(C.Structure):
 
 
 assert C.sizeof(AugmentOp) == 40 and C.sizeof(AugmentDesc) == 80
+
+
+class JpegDesc(C.Structure):
+  """struct asm_jpeg_desc"""
+  _fields_ = [(n, C.c_int64) for n in ('scan_offset', 'scan_bytes', 'coef_offset', 'plane_offset', 'dst_offset')] + [
+      (n, C.c_int32) for n in ('width', 'height', 'ncomp', 'hs', 'vs', 'mcus_x', 'mcus_y', 'restart_interval',
+                               'first_interval', 'n_intervals')] + [
+      ('qsel', C.c_uint8 * 4), ('dcsel', C.c_uint8 * 4), ('acsel', C.c_uint8 * 4), ('reserved', C.c_int32)]
+
+
+class JpegHuff(C.Structure):
+  """struct asm_jpeg_huff"""
+  _fields_ = [('bits', C.c_uint8 * 16), ('vals', C.c_uint8 * 256)]
+
+
+class JpegTables(C.Structure):
+  """struct asm_jpeg_tables"""
+  _fields_ = [('quant', (C.c_uint16 * 64) * 4), ('dc', JpegHuff * 2), ('ac', JpegHuff * 2)]
+
+
+class JpegInterval(C.Structure):
+  """struct asm_jpeg_interval"""
+  _fields_ = [('image', C.c_int32), ('first_mcu', C.c_int32), ('n_mcus', C.c_int32), ('rst', C.c_int32),
+              ('byte_begin', C.c_int64), ('byte_end', C.c_int64)]
+
+
+assert (C.sizeof(JpegDesc), C.sizeof(JpegHuff), C.sizeof(JpegTables), C.sizeof(JpegInterval)) == (96, 272, 1600, 32)
+JPEG_EBADCODE, JPEG_EOVERRUN, JPEG_ERESTART, JPEG_EDESC = 1, 2, 4, 8      # asm_jpeg_decode's status bits
 
 
 class ConvDesc(C.Structure):
@@ -223,6 +251,8 @@ SIGNATURES = {
     'asm_resize_crop_flip': (_I, [_P, C.c_int64, _P, _I, _I, _I, _I, _P, _P]),
     'asm_autoaugment_workspace_bytes': (_I, [_I, _I, _I, C.POINTER(C.c_int64)]),
     'asm_autoaugment': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, C.c_int64, _P]),
+    'asm_jpeg_decode_workspace_bytes': (_I, [C.c_int64, C.POINTER(C.c_int64)]),
+    'asm_jpeg_decode': (_I, [_P, C.c_int64, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _P, C.c_int64, _P, _P, C.c_int64, _I, _P]),
     'asm_model_plan': (_I, [C.POINTER(ModelCfg), _I, _I, _I, C.POINTER(PlanEntry), _I, C.POINTER(PlanSummary)]),
 }
 

@@ -984,6 +984,36 @@ def autoaugment(images_f32, descs_dev, subtract_mean):
   return out
 
 
+def jpeg_decode(files_u8, descs_dev, tables_dev, intervals_dev, n, n_intervals, total_blocks, max_blocks, max_pixels, dst,
+                stages=3, check_status=True, names=None, return_workspace=False):
+  """asm_jpeg_decode for a batch packed by jpeg.pack: uint8 device views of the entropy-coded bytes, n struct asm_jpeg_desc
+  (96 bytes), n struct asm_jpeg_tables (1600 bytes) and n_intervals struct asm_jpeg_interval (32 bytes); dst: uint8 device
+  buffer the [H][W][3] images are written into.  Three launches.  Returns the int32 [n] status (on the host when
+  check_status, which waits for the decode and raises ValueError naming the entries whose entropy-coded data is corrupt;
+  `names` maps a row to the index to report).  return_workspace: (status, workspace) instead -- the uint8 device buffer
+  with the int16 coefficients [total_blocks][64] first, then the planes (tests compare the coefficients)."""
+  if descs_dev.numel() != 96 * n or tables_dev.numel() != 1600 * n or intervals_dev.numel() != 32 * n_intervals:
+    raise ValueError('jpeg_decode: table sizes do not match n = %d, n_intervals = %d' % (n, n_intervals))
+  status = torch.empty((max(n, 1),), dtype=torch.int32, device=dst.device)[:n]
+  if n == 0:
+    status = status.cpu() if check_status else status
+    return (status, None) if return_workspace else status
+  need = C.c_int64(0)
+  check(L().asm_jpeg_decode_workspace_bytes(total_blocks, C.byref(need)), 'jpeg_decode_workspace_bytes')
+  ws = _workspace(max(need.value, 16), dst)
+  check(L().asm_jpeg_decode(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev), _ptr(intervals_dev), n,
+                            n_intervals, total_blocks, max_blocks, max_pixels, _ptr(dst), dst.numel(), _ptr(status),
+                            _ptr(ws), ws.numel(), stages, _stream()), 'jpeg_decode')
+  if not check_status:
+    return (status, ws) if return_workspace else status
+  host = status.cpu()
+  bad = torch.nonzero(host).reshape(-1).tolist()
+  if bad:
+    raise ValueError('jpeg_decode: corrupt entropy-coded data in entries %s (status %s)' % (
+        [names[b] if names is not None else b for b in bad], [int(host[b]) for b in bad]))
+  return (host, ws) if return_workspace else host
+
+
 # ---------------------------------------------------------------------------------------------------
 # retrieval evaluation (metric/recall_metric.py)
 # ---------------------------------------------------------------------------------------------------

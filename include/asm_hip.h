@@ -35,7 +35,7 @@ extern "C" {
 #define ASM_ENOTSUP (-2)
 #define ASM_EHIP (-3)
 
-#define ASM_ABI_VERSION 9
+#define ASM_ABI_VERSION 10
 
 const char* asm_last_error(void);
 int asm_abi_version(void);
@@ -606,6 +606,68 @@ typedef struct asm_augment_desc {
 int asm_autoaugment_workspace_bytes(int N, int H, int W, int64_t* bytes);
 int asm_autoaugment(const float* in, const asm_augment_desc* descs, int N, int H, int W, int subtract_mean, float* out,
                     void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * JPEG decode (tf.image.decode_jpeg / decode_and_crop_jpeg, preprocessing/imagenet_preprocessing.py:81,92-93,296, with
+ * dct_method = INTEGER_ACCURATE, nets/hparams_config.py:223, and fancy_upscaling): a ragged batch of baseline /
+ * extended-sequential Huffman files (SOF0 / SOF1, 8 bit, one interleaved scan; grey, or YCbCr with luma sampling 1x1, 2x1
+ * or 2x2 and chroma 1x1) -> [H][W][3] uint8 at dst + dst_offset, which is the `src` layout of asm_resize_crop_flip.
+ * The HOST parses the headers (assembled_cnn_amd/jpeg.py: classification, tables, restart-interval byte ranges); the
+ * device does the entropy decode (ITU-T T.81 F.2.2; one 64-lane workgroup per image, lane s decodes restart intervals
+ * s, s + 64, ...), then dequantisation + libjpeg's integer ISLOW inverse DCT (one thread per 8x8 block), then libjpeg's
+ * "fancy" chroma upsampling + 16-bit fixed-point YCbCr -> RGB (one thread per pixel): three launches for the batch, no
+ * host synchronisation.  DESIGN.md section 1.2 states every rule; the result equals libjpeg's bit for bit.
+ *   files      the entropy-coded segments (everything between SOS header and the next non-RST marker), packed
+ *   descs      N descriptors; tables: N table blocks; intervals: n_intervals rows, those of image i at
+ *              [first_interval, first_interval + n_intervals) in restart order
+ *   status     int32 [N], written by the call: 0 = decoded; else a bit set of ASM_JPEG_E*.  An image with a non-zero
+ *              status has an all-zero output -- with one exception: under ASM_JPEG_EDESC, a descriptor whose width,
+ *              height (1..8192) and dst_offset do not describe a slot inside dst gets nothing written at all.  No table or byte string makes the kernels read or write out of range: every
+ *              bitstream read is bounded by the interval's byte range, every coefficient index by 63, every block index by
+ *              the image's own geometry, every offset by the sizes passed here.
+ *   workspace  asm_jpeg_decode_workspace_bytes(total_blocks): int16 coefficients [total_blocks][64], stored raw and in
+ *              natural order, then uint8 planes [total_blocks * 64]; total_blocks = sum over images of their 8x8 blocks
+ *              (all components, padded to whole MCUs); a descriptor's coef_offset counts blocks * 64 and its plane_offset
+ *              bytes from the start of their regions.  max_blocks / max_pixels: the largest per-image block count and
+ *              W * H (they size the ragged grids).  stages: 1 = entropy decode, 2 = pixel stages, 3 = both.
+ * ---------------------------------------------------------------------------------------------- */
+#define ASM_JPEG_EBADCODE 1   /* a bit string that is no Huffman code, or a coefficient index past 63              */
+#define ASM_JPEG_EOVERRUN 2   /* the interval's bytes ran out (or an unexpected marker came) before its last MCU   */
+#define ASM_JPEG_ERESTART 4   /* restart markers out of sequence, or more / fewer intervals than the geometry has  */
+#define ASM_JPEG_EDESC 8      /* descriptor / interval row that does not fit the buffers or the geometry           */
+typedef struct asm_jpeg_desc {
+  int64_t scan_offset, scan_bytes;         /* the image's entropy-coded bytes in files                              */
+  int64_t coef_offset;                     /* int16 elements from the start of the coefficient region              */
+  int64_t plane_offset;                    /* bytes from the start of the plane region                             */
+  int64_t dst_offset;                      /* bytes; [height][width][3] uint8                                      */
+  int32_t width, height;                   /* 1..8192                                                              */
+  int32_t ncomp;                           /* 1 (grey) or 3 (YCbCr)                                                */
+  int32_t hs, vs;                          /* luma sampling: 1x1, 2x1 or 2x2 (chroma is 1x1); grey: 1x1            */
+  int32_t mcus_x, mcus_y;                  /* ceil(width / (8 hs)), ceil(height / (8 vs))                          */
+  int32_t restart_interval;                /* MCUs per interval (DRI); 0 = the whole scan is one interval          */
+  int32_t first_interval, n_intervals;     /* rows of the interval table                                           */
+  uint8_t qsel[4], dcsel[4], acsel[4];     /* per component: quantisation table 0..3, Huffman slots 0..1           */
+  int32_t reserved;
+} asm_jpeg_desc;                           /* 96 bytes */
+typedef struct asm_jpeg_huff {
+  uint8_t bits[16];                        /* codes of length 1..16 (T.81 B.2.4.2)                                 */
+  uint8_t vals[256];                       /* symbols in code order                                                */
+} asm_jpeg_huff;                           /* 272 bytes */
+typedef struct asm_jpeg_tables {
+  uint16_t quant[4][64];                   /* natural (row-major) order, 8-bit precision values                    */
+  asm_jpeg_huff dc[2], ac[2];
+} asm_jpeg_tables;                         /* 1600 bytes, one per image */
+typedef struct asm_jpeg_interval {
+  int32_t image;                           /* row of descs                                                         */
+  int32_t first_mcu, n_mcus;
+  int32_t rst;                             /* m of the RSTm that ends the interval, -1 after the last              */
+  int64_t byte_begin, byte_end;            /* in files, markers excluded                                           */
+} asm_jpeg_interval;                       /* 32 bytes */
+int asm_jpeg_decode_workspace_bytes(int64_t total_blocks, int64_t* bytes);
+int asm_jpeg_decode(const uint8_t* files, int64_t files_bytes, const asm_jpeg_desc* descs, const asm_jpeg_tables* tables,
+                    const asm_jpeg_interval* intervals, int N, int n_intervals, int64_t total_blocks, int max_blocks,
+                    int max_pixels, uint8_t* dst, int64_t dst_bytes, int32_t* status, void* workspace,
+                    int64_t workspace_bytes, int stages, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Flag surface and topology planner.  asm_model_cfg carries the flags of nets/hparams_config.py:30-292 (+

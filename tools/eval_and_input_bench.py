@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Throughput of the rows either side of the training step: the GPU input-pipeline tail (resize/crop/flip/mean-sub
-kernel) and evaluation-mode inference with the on-device metrics (BASELINE configs 1 and 3-eval)."""
+kernel), the device JPEG decoder in front of it, and evaluation-mode inference with the on-device metrics (BASELINE
+configs 1 and 3-eval).  `--only jpeg` runs the JPEG leg alone."""
 import os, sys, time
 import numpy as np
 import torch
@@ -18,6 +19,74 @@ def ev(fn, iters=10):
   b.record(); torch.cuda.synchronize()
   return a.elapsed_time(b) / iters
 
+
+def jpeg_leg(n=256):
+  """Device JPEG decode of n files of about 500 x 375, 4:2:0, quality 90, no restart markers: the entropy stage, the pixel
+  stages, the whole decode_batch (host parse and packing included), the same files through Pillow on 16 threads, and what
+  the decoded arrays cost today (pack_batch + H2D)."""
+  import concurrent.futures, io
+  from assembled_cnn_amd import jpeg
+  rng = np.random.default_rng(1)
+  try:
+    from PIL import Image
+  except ImportError:
+    Image = None
+  if Image is not None:
+    files = []
+    for _ in range(n):
+      w, h = int(rng.integers(440, 561)), int(rng.integers(330, 421))
+      low = Image.fromarray(rng.integers(0, 256, size=(h // 24 + 2, w // 24 + 2, 3), dtype=np.uint8)).resize((w, h), Image.BICUBIC)
+      arr = np.clip(np.asarray(low).astype(np.float32) + rng.normal(0, 9, size=(h, w, 3)), 0, 255).astype(np.uint8)
+      b = io.BytesIO()
+      Image.fromarray(arr).save(b, 'JPEG', quality=90, subsampling=2)
+      files.append(b.getvalue())
+    source = 'generated with Pillow: smooth fields + sigma-9 noise, 440..560 x 330..420, 4:2:0, quality 90'
+  else:
+    fx = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden', 'jpeg_fixtures.npz'))
+    big = sorted((str(k) for k in fx['names'] if str(fx['kind_' + str(k)]) == 'device'), key=lambda k: -fx['file_' + k].size)[:8]
+    files = [fx['file_' + big[k % len(big)]].tobytes() for k in range(n)]
+    source = 'Pillow not importable: the 8 largest test fixtures tiled (%s)' % ', '.join(big)
+  print('jpeg: %d files, %s; mean %.1f KB' % (n, source, sum(map(len, files)) / n / 1e3))
+  pk = jpeg.pack(files)
+  up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1)).cuda()
+  fd, dd, td, ivd = up(pk.files), up(pk.descs), up(pk.tables), up(pk.intervals)
+  dst = torch.empty(pk.total_bytes, dtype=torch.uint8, device='cuda')
+  run = lambda stages: ops.jpeg_decode(fd, dd, td, ivd, n, len(pk.intervals), pk.total_blocks, pk.max_blocks, pk.max_pixels, dst,
+                                       stages=stages, check_status=False)
+  assert not ops.jpeg_decode(fd, dd, td, ivd, n, len(pk.intervals), pk.total_blocks, pk.max_blocks, pk.max_pixels, dst).any()
+  ms_e, ms_p = ev(lambda: run(1), iters=3), ev(lambda: run(2), iters=10)
+  whole = []
+  for _ in range(3):
+    t0 = time.time(); jpeg.decode_batch(files, 'cuda'); torch.cuda.synchronize(); whole.append(1e3 * (time.time() - t0))
+  t0 = time.time(); jpeg.pack(files); ms_host = 1e3 * (time.time() - t0)
+  print('jpeg entropy stage : %8.2f ms per batch of %d (%6.0f img/s)' % (ms_e, n, n / ms_e * 1e3))
+  print('jpeg pixel stages  : %8.2f ms per batch of %d (%6.0f img/s)' % (ms_p, n, n / ms_p * 1e3))
+  print('jpeg decode_batch  : %8.2f ms per batch of %d (%6.0f img/s), host parse + pack %.1f ms of it; runs %s'
+        % (min(whole), n, n / min(whole) * 1e3, ms_host, ' '.join('%.1f' % w for w in whole)))
+  if Image is not None:
+    dec = lambda f: np.asarray(Image.open(io.BytesIO(f)).convert('RGB'))
+    with concurrent.futures.ThreadPoolExecutor(16) as ex:
+      list(ex.map(dec, files[:32]))
+      t0 = time.time(); arrays = list(ex.map(dec, files)); ms_pil = 1e3 * (time.time() - t0)
+    t0 = time.time(); one = [dec(f) for f in files[:64]]; ms_one = 1e3 * (time.time() - t0) * n / 64
+    print('Pillow, 16 threads : %8.2f ms per batch of %d (%6.0f img/s); one thread %.1f ms (%.0f img/s)'
+          % (ms_pil, n, n / ms_pil * 1e3, ms_one, n / ms_one * 1e3))
+    got = dst.cpu().numpy()
+    assert all(np.array_equal(got[int(o):int(o) + a.size].reshape(a.shape), a) for o, a in zip(pk.offsets, arrays)), 'device != Pillow'
+    print('jpeg: the device output equals Pillow\'s on all %d files' % n)
+  else:
+    arrays = [np.zeros((h, w, 3), np.uint8) for h, w in pk.sizes]
+  wins = [P.eval_window(a.shape[0], a.shape[1], 224, 224) for a in arrays]
+  best = 1e9
+  for _ in range(3):
+    t0 = time.time(); buf, table = P.pack_batch(arrays, wins, 224, 224, pin=True); buf.cuda(); table.cuda(); torch.cuda.synchronize()
+    best = min(best, 1e3 * (time.time() - t0))
+  print('decoded arrays today: pack_batch + H2D %.2f ms per batch of %d (%.1f MB)' % (best, n, sum(a.size for a in arrays) / 1e6))
+
+
+if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] == 'jpeg':
+  jpeg_leg()
+  sys.exit(0)
 
 rng = np.random.default_rng(0)
 imgs = [rng.integers(0, 256, size=(int(rng.integers(300, 600)), int(rng.integers(300, 600)), 3), dtype=np.uint8) for _ in range(256)]
@@ -41,6 +110,8 @@ for training, side, ptype in ((True, 224, 'imagenet'), (False, 256, 'imagenet_22
       ms_aa = ev(lambda: ops.autoaugment(resized, ad, True))
       print('autoaugment %-26s %dx%d: kernel %.3f ms for 256 images (%.0f k img/s; resize_crop_flip above: %.3f ms)'
             % (what, side, side, ms_aa, 256 / ms_aa, ms))
+
+jpeg_leg()
 
 for name, kw, side in (('ResNet-50 v1.5 eval 224', dict(resnet_version=1), 224),
                        ('Assemble-ResNet-50 eval 256', dict(resnet_version=2, use_sk_block=True, anti_alias_type='sconv',
