@@ -2,7 +2,8 @@
 vs the CPU oracle on identical seeded bf16 inputs.
 
 Tolerance: outputs are bf16 -> relative L2 <= 4e-3 and max |err| <= 2^-7 max|ref|; fp32 outputs
-(statistics, parameter gradients, losses) relative <= 1e-4 unless noted."""
+(statistics, parameter gradients, losses) relative <= 1e-4 unless noted.
+Edge shapes, ties and guard bands of the pooling, SK and SE kernels, element-wise: tests/test_gpu_pool_edges.py."""
 import numpy as np
 import pytest
 import torch

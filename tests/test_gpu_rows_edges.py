@@ -23,76 +23,10 @@ import pytest
 import torch
 
 from tests import rows_ref as R
+from tests.gpu_guard import (_ALIVE, BF, DEV, FLANK, PATTERN, Out, _abi, _release_inputs, _report, call,  # noqa: F401
+                             close_bf16, close_rel, close_sum, close_ulp, dev, exact, ptr)
 
 pytestmark = pytest.mark.gpu
-BF = torch.bfloat16
-DEV = 'cuda'
-FLANK = 4096
-PATTERN = 0xA5
-
-
-def _abi():
-  from assembled_cnn_amd import ops
-  return ops
-
-
-def call(name, *args):
-  ops = _abi()
-  ops.check(getattr(ops.L(), name)(*args, ops._stream()), name)
-
-
-def ptr(t):
-  return _abi()._ptr(t)
-
-
-class Out(object):
-  """``shape`` elements of ``dtype`` between two 4 KiB flanks of one allocation, all bytes 0xA5 before the call"""
-
-  def __init__(self, shape, dtype, init=None):
-    n = int(np.prod(shape))
-    self.pad = FLANK // torch.empty((), dtype=dtype).element_size()
-    self.buf = torch.empty(n + 2 * self.pad, dtype=dtype, device=DEV)
-    self.buf.view(torch.uint8).fill_(PATTERN)
-    self.t = self.buf[self.pad:self.pad + n].view(*shape)
-    if init is not None:
-      self.t.copy_(init)
-
-  @property
-  def p(self):
-    return ptr(self.t)
-
-  def check_flanks(self):
-    raw = self.buf.view(torch.uint8)
-    assert bool((raw[:FLANK] == PATTERN).all()) and bool((raw[-FLANK:] == PATTERN).all()), 'a flank was written'
-
-  def np(self):
-    """flanks intact -> the output as float64 (int64 for integer outputs); NaN and huge values are failures"""
-    self.check_flanks()
-    a = self.t.detach().cpu()
-    if a.dtype in (torch.int32, torch.uint8):
-      return a.numpy().astype(np.int64)
-    a = a.double().numpy()
-    assert np.isfinite(a).all() and (np.abs(a) < 1e29).all() if a.size else True, 'NaN or huge value in an output'
-    return a
-
-
-def dev(a, dtype=torch.float32):
-  """numpy -> device tensor (bf16: the values are bf16 already or get rounded here)"""
-  t = torch.from_numpy(np.ascontiguousarray(a))
-  if dtype == BF:
-    t = t.float()
-  t = t.to(dtype).to(DEV)
-  _ALIVE.append(t)        # an input handed over as a bare pointer must outlive the call
-  return t
-
-
-_ALIVE = []
-
-
-@pytest.fixture(autouse=True)
-def _release_inputs():
-  yield
-  del _ALIVE[:]
 
 
 def padded(a, ld, fill):
@@ -102,42 +36,6 @@ def padded(a, ld, fill):
   return out
 
 
-# ---- bounds -------------------------------------------------------------------------------------------------------------
-def _report(case, err, bound):
-  worst = float(np.max(err / np.maximum(bound, 1e-300))) if err.size else 0.0
-  print('\nrows-edges %-46s worst |err| %.3e = %.3f of its bound' % (case, float(err.max()) if err.size else 0.0, worst), end='')
-
-
-def close_bf16(case, out, ref, floor):
-  out, ref = np.asarray(out, np.float64), np.asarray(ref, np.float64)
-  err, bound = np.abs(out - ref), R.BF16_ULP * np.abs(ref) + 4.0 * floor
-  _report(case, err, bound)
-  print('  (reference floor %.3e)' % floor, end='')
-  assert (err <= bound).all(), '%s: |err| %.3e at %s' % (case, err.max(), np.unravel_index(np.argmax(err - bound), err.shape))
-
-
-def close_sum(case, out, ref, n, sum_abs):
-  out, ref = np.asarray(out, np.float64), np.asarray(ref, np.float64)
-  err, bound = np.abs(out - ref), n * R.U24 * np.asarray(sum_abs, np.float64) + np.zeros_like(ref)
-  _report(case, err, bound)
-  assert (err <= bound).all(), '%s: |err| %.3e, bound %.3e' % (case, err.max(), bound.max())
-
-
-def close_rel(case, out, ref):
-  out, ref = np.asarray(out, np.float64), np.asarray(ref, np.float64)
-  err, bound = np.abs(out - ref), 1e-4 * np.abs(ref) + 1e-8
-  _report(case, err, bound)
-  assert (err <= bound).all(), '%s: |err| %.3e' % (case, err.max())
-
-
-def close_ulp(case, out, ref, ulps=1):
-  """the float32 nearest the float64 reference, give or take ``ulps``"""
-  r32 = np.asarray(ref, np.float64).astype(np.float32)
-  err, bound = np.abs(np.asarray(out, np.float64) - r32.astype(np.float64)), ulps * R.ulp32(r32)
-  _report(case, err, bound)
-  assert (err <= bound).all(), '%s: %.2f ulp' % (case, float(np.max(err / bound)))
-
-
 def close_terms(case, out, terms, roundings):
   """a float32 expression the kernel evaluates from already rounded float32 values: ``roundings`` half-ulps of the sum of the
   magnitudes of its terms"""
@@ -145,12 +43,6 @@ def close_terms(case, out, terms, roundings):
   err, bound = np.abs(np.asarray(out, np.float64) - ref), roundings * R.U24 * sum(np.abs(t) for t in terms)
   _report(case, err, bound)
   assert (err <= bound).all(), '%s: |err| %.3e, bound %.3e' % (case, err.max(), bound.max())
-
-
-def exact(case, out, ref):
-  out, ref = np.asarray(out), np.asarray(ref)
-  assert out.shape == ref.shape and np.array_equal(out, ref), \
-      '%s: %d of %d elements differ' % (case, int((out != ref).sum()) if out.shape == ref.shape else -1, ref.size)
 
 
 # ---- bias gradient / bias add ---------------------------------------------------------------------------------------------
