@@ -13,6 +13,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from . import lib
+
 _MAX_LEVEL = 10.          # autoaugment.py:28
 CUTOUT_CONST = 100        # autoaugment.py:899-901 (augmentation_hparams)
 TRANSLATE_CONST = 250
@@ -25,9 +27,8 @@ OP_IDS = {name: i + 1 for i, name in enumerate(OP_NAMES)}
 SIGNED = ('Rotate', 'ShearX', 'ShearY', 'TranslateX', 'TranslateY')      # _randomly_negate_tensor (:702-706)
 _BLEND = ('Color', 'Contrast', 'Brightness', 'Sharpness')
 
-OP_DTYPE = np.dtype([('op', '<i4'), ('a', '<i4'), ('b', '<i4'), ('reserved', '<i4'), ('f', '<f4', (6,))])
-DESC_DTYPE = np.dtype([('slot', OP_DTYPE, (2,))])
-assert OP_DTYPE.itemsize == 40 and DESC_DTYPE.itemsize == 80      # struct asm_augment_op / asm_augment_desc
+OP_DTYPE = np.dtype(lib.AugmentOp)           # struct asm_augment_op
+DESC_DTYPE = np.dtype(lib.AugmentDesc)       # struct asm_augment_desc
 
 
 def _p(*rows):

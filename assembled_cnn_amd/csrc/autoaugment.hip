@@ -262,7 +262,7 @@ autoaugment_kernel(const float* __restrict__ in, const asm_augment_desc* __restr
     }
     if (swapped) { uint8_t* t = cur; cur = alt; alt = t; }
   }
-  const float means[3] = {123.68f, 116.78f, 103.94f};   // CHANNEL_MEANS, imagenet_preprocessing.py:46-49
+  const float means[3] = ASM_CHANNEL_MEANS;
   float* dst = out + (size_t)n * HW * 3;
   for (int p = tid; p < HW; p += AA_THREADS)
 #pragma unroll

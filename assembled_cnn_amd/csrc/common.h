@@ -81,6 +81,10 @@ inline void asm_launch(void (*kernel)(P...), dim3 grid, dim3 block, unsigned shm
     if (e__ != hipSuccess) ASM_FAIL(ASM_EHIP, "%s: %s", name, hipGetErrorString(e__)); \
   } while (0)
 
+// ---- preprocessing constants --------------------------------------------------------------------
+// CHANNEL_MEANS (preprocessing/imagenet_preprocessing.py:46-49), R G B: `const float means[3] = ASM_CHANNEL_MEANS;`
+#define ASM_CHANNEL_MEANS {123.68f, 116.78f, 103.94f}
+
 // ---- bf16 <-> f32 ----------------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(bf16_t b) { return __uint_as_float(((unsigned)b) << 16); }
 // round-to-nearest-even; lowers to v_cvt_pk_bf16_f32 on gfx950

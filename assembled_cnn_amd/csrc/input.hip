@@ -39,7 +39,7 @@ resize_crop_flip_kernel(const uint8_t* __restrict__ src, long long src_bytes, co
   const uint8_t* base = src + d.src_offset;
   const uint8_t* r0 = base + ((size_t)(d.crop_y + ly) * d.Ws + d.crop_x) * 3;
   const uint8_t* r1 = base + ((size_t)(d.crop_y + uy) * d.Ws + d.crop_x) * 3;
-  const float means[3] = {123.68f, 116.78f, 103.94f};
+  const float means[3] = ASM_CHANNEL_MEANS;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float tl = (float)r0[cl * 3 + c], tr = (float)r0[cu * 3 + c];

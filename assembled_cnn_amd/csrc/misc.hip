@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256) void mixup_meansub_kernel(const void* __restri
         for (int c = 0; c < 3; ++c) vb[c] = p[pb + c];
       }
     }
-    const float mean[3] = {123.68f, 116.78f, 103.94f};
+    const float mean[3] = ASM_CHANNEL_MEANS;
     float r[3];
     for (int c = 0; c < 3; ++c) {
       const float xa = va[c] - mean[c];
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(64) void mixup_meansub_rows_kernel(const uint8_t* _
   }
   const unsigned* pa = reinterpret_cast<const unsigned*>(images + ((size_t)ia * H + h) * W * 3);
   const unsigned* pb = ib >= 0 ? reinterpret_cast<const unsigned*>(images + ((size_t)ib * H + h) * W * 3) : nullptr;
-  const float mean[3] = {123.68f, 116.78f, 103.94f};
+  const float mean[3] = ASM_CHANNEL_MEANS;
   for (int q = threadIdx.x; q < (W >> 2); q += 64) {
     unsigned a[3], bb[3] = {0u, 0u, 0u};
 #pragma unroll

@@ -14,7 +14,6 @@ before ``tf.cast(image, dtype)`` (float32, mean-subtracted, NHWC) and feeds ``Mo
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import re
 from typing import List, Optional, Sequence, Tuple
@@ -24,8 +23,7 @@ import torch
 
 from . import autoaugment as _aa
 from . import jpeg as _jpeg
-from . import ops
-from .lib import ImageDesc
+from . import lib, ops, staging
 
 _RESIZE_MIN = 256   # preprocessing/imagenet_preprocessing.py:54
 
@@ -125,26 +123,7 @@ def _validate(win: dict, Hs: int, Ws: int, out_h: int, out_w: int):
     raise ValueError('window %r does not fit a %dx%d image / %dx%d output' % (win, Hs, Ws, out_h, out_w))
 
 
-_DESC_DTYPE = np.dtype([('src_offset', '<i8'), ('Hs', '<i4'), ('Ws', '<i4'), ('crop_y', '<i4'), ('crop_x', '<i4'),
-                        ('crop_h', '<i4'), ('crop_w', '<i4'), ('resize_h', '<i4'), ('resize_w', '<i4'),
-                        ('out_y', '<i4'), ('out_x', '<i4'), ('flip', '<i4'), ('reserved', '<i4')])
-assert _DESC_DTYPE.itemsize == ctypes.sizeof(ImageDesc) == 56
-
-
-_STAGING = {}
-
-
-def _staging(nbytes: int, pin: bool) -> torch.Tensor:
-  """Grow-only host staging buffer (re-used across batches: a fresh 150 MB allocation costs more in page faults than
-  the copy itself).  The caller must have consumed the previous batch's H2D copy before packing the next one."""
-  ev = _STAGING.get('event')
-  if pin and ev is not None:
-    ev.synchronize()            # the previous batch's asynchronous H2D copy reads this buffer
-  cur = _STAGING.get(pin)
-  if cur is None or cur.numel() < nbytes:
-    cur = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, pin_memory=pin)
-    _STAGING[pin] = cur
-  return cur
+_DESC_DTYPE = np.dtype(lib.ImageDesc)       # struct asm_image_desc
 
 
 def _fill_table(desc: np.ndarray, offs, sizes, windows, out_h: int, out_w: int):
@@ -161,51 +140,21 @@ def _fill_table(desc: np.ndarray, offs, sizes, windows, out_h: int, out_w: int):
       desc[f][:n] = [int(w[f]) for w in windows]
 
 
-def _staging_in_flight(dev):
-  """an asynchronous H2D copy out of the pinned staging buffer was just enqueued: the next user waits for it"""
-  if dev.type == 'cuda':
-    ev = torch.cuda.Event()
-    ev.record()
-    _STAGING['event'] = ev
-
-
-def stage_into(region: torch.Tensor, arrays, offsets):
-  """Decoded uint8 arrays -> the staging buffer at `offsets` -> ONE host-to-device copy into `region` (a uint8 device view
-  whose first byte is offset 0): the decoded entries of a batch that is otherwise decoded on the device."""
-  pin = region.is_cuda
-  buf = _staging(max(region.numel(), 16), pin)
-  host = buf.numpy()
-  for a, o in zip(arrays, offsets):
-    host[int(o):int(o) + a.size] = a.reshape(-1)
-  region.copy_(buf[:region.numel()], non_blocking=True)
-  _staging_in_flight(region.device)
-
-
 def pack_batch(images: Sequence[np.ndarray], windows: Sequence[dict], out_h: int, out_w: int, pin: bool = False):
   """Decoded images (uint8 [H, W, 3], any sizes) -> (packed uint8 buffer, descriptor table bytes) as CPU tensors
-  (pinned when ``pin``).  One memcpy per image into the staging buffer and a vectorised descriptor table: ~10 GB/s
+  (pinned when ``pin``): the host half of preprocess_batch for a batch without encoded files.  The buffer is the staging
+  buffer itself, valid until the next batch is packed.  One memcpy per image and a vectorised descriptor table: ~10 GB/s
   on one core, so the host side keeps up with the GPU (the per-image tensor ops of the first version did 670 img/s)."""
   n = len(images)
   if n != len(windows):
     raise ValueError('one window per image')
-  sizes = np.empty(n, dtype=np.int64)
-  for k, im in enumerate(images):
+  for im in images:
     if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
       raise ValueError('Input must be of size [height, width, 3] uint8')     # imagenet_preprocessing.py:143-144
-    sizes[k] = im.size
-  padded = (sizes + 15) // 16 * 16
-  offs = np.concatenate([[0], np.cumsum(padded)[:-1]]) if n else np.zeros(0, np.int64)
-  total = int(padded.sum()) if n else 0
-  buf = _staging(max(total, 16), pin)
-  dst = buf.numpy()
-  table = torch.zeros(max(n, 1) * 56, dtype=torch.uint8, pin_memory=pin)
-  desc = table.numpy().view(_DESC_DTYPE)
-  _fill_table(desc, offs, [im.shape[:2] for im in images], windows, out_h, out_w)
-  for k, im in enumerate(images):
-    o = int(offs[k])
-    dst[o:o + im.size] = im.reshape(-1)                                       # one memcpy (copies if not contiguous)
-  buf = buf[:max(total, 16)]
-  return buf, table[:56 * n]
+  offs, total = staging.slot_layout([im.size for im in images])
+  table = torch.zeros(n * _DESC_DTYPE.itemsize, dtype=torch.uint8, pin_memory=pin)
+  _fill_table(table.numpy().view(_DESC_DTYPE), offs, [im.shape[:2] for im in images], windows, out_h, out_w)
+  return staging.fill(max(total, 16), images, offs, pin), table
 
 
 def _augment_tail(bd, td, n, side, is_training, dev, rng, subtract_mean, autoaugment_type, augment):
@@ -218,32 +167,8 @@ def _augment_tail(bd, td, n, side, is_training, dev, rng, subtract_mean, autoaug
   _aa.validate(augment, side, side)
   if len(augment) != n:
     raise ValueError('one augmentation descriptor per image')
-  ad = torch.from_numpy(np.ascontiguousarray(augment).view(np.uint8).copy()).to(dev, non_blocking=False)
   resized = ops.resize_crop_flip(bd, td, n, side, side, False)
-  return ops.autoaugment(resized, ad, subtract_mean)
-
-
-def _preprocess_encoded(images, is_training, device, side, crop_type, use_random_crop, rng, subtract_mean, windows,
-                        autoaugment_type, augment, dct_method, jpeg_fallback):
-  """preprocess_batch for a batch with encoded files in it: the files are decoded on the device into their slots of the
-  packed buffer, decoded arrays (given, or returned by the fallback) are copied into theirs; same windows, same table."""
-  _jpeg.check_dct_method(dct_method)
-  n = len(images)
-  pk = _jpeg.pack(images, jpeg_fallback)
-  if windows is None:
-    if is_training:
-      rng = rng if rng is not None else np.random.default_rng()
-      windows = [train_window(h, w, side, side, rng, use_random_crop) for h, w in pk.sizes]
-    else:
-      windows = [eval_window(h, w, side, side, crop_type) for h, w in pk.sizes]
-  if n != len(windows):
-    raise ValueError('one window per image')
-  desc = np.zeros(n, dtype=_DESC_DTYPE)
-  _fill_table(desc, pk.offsets, pk.sizes, windows, side, side)
-  dev = torch.device(device)
-  bd = _jpeg.decode_packed(pk, dev)[0]
-  td = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(dev, non_blocking=False)
-  return _augment_tail(bd, td, n, side, is_training, dev, rng, subtract_mean, autoaugment_type, augment)
+  return ops.autoaugment(resized, staging.upload_table(augment, dev), subtract_mean)
 
 
 def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, image_size: int = 224,
@@ -266,16 +191,22 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
     _aa.check_policy_name(autoaugment_type)
   side, crop_type = output_size_and_crop_type(preprocessing_type, is_training, image_size)
   if any(_jpeg.is_encoded(im) for im in images):
-    return _preprocess_encoded(images, is_training, device, side, crop_type, use_random_crop, rng, subtract_mean, windows,
-                               autoaugment_type, augment, dct_method, jpeg_fallback)
+    _jpeg.check_dct_method(dct_method)
+  # encoded files are decoded on the device into their slots of the packed buffer, decoded arrays (given, or returned by
+  # the fallback) travel to theirs in one staged copy; one window and one descriptor per slot
+  pk = _jpeg.pack(images, jpeg_fallback)
   if windows is None:
     if is_training:
       rng = rng if rng is not None else np.random.default_rng()
-      windows = [train_window(im.shape[0], im.shape[1], side, side, rng, use_random_crop) for im in images]
+      windows = [train_window(h, w, side, side, rng, use_random_crop) for h, w in pk.sizes]
     else:
-      windows = [eval_window(im.shape[0], im.shape[1], side, side, crop_type) for im in images]
+      windows = [eval_window(h, w, side, side, crop_type) for h, w in pk.sizes]
+  n = len(images)
+  if n != len(windows):
+    raise ValueError('one window per image')
+  desc = np.zeros(n, dtype=_DESC_DTYPE)
+  _fill_table(desc, pk.offsets, pk.sizes, windows, side, side)
   dev = torch.device(device)
-  buf, table = pack_batch(images, windows, side, side, pin=dev.type == 'cuda')
-  bd, td = buf.to(dev, non_blocking=True), table.to(dev, non_blocking=True)
-  _staging_in_flight(dev)
-  return _augment_tail(bd, td, len(images), side, is_training, dev, rng, subtract_mean, autoaugment_type, augment)
+  bd = _jpeg.decode_packed(pk, dev)[0]
+  return _augment_tail(bd, staging.upload_table(desc, dev), n, side, is_training, dev, rng, subtract_mean,
+                       autoaugment_type, augment)

@@ -4,38 +4,31 @@
 the byte range of the scan and of each restart interval, and whether the file is one the device path decodes.  ``pack``
 turns a batch of files into the tables ``asm_jpeg_decode`` reads, ``decode_batch`` runs it.  Everything a kernel could
 trip over in a HEADER (truncated segments, table ids and sizes that disagree) is rejected here with ValueError; what can
-go wrong in the entropy-coded bytes is the kernel's to detect (per-image status, ops.jpeg_decode raises ValueError).
+go wrong in the entropy-coded bytes is the kernel's to detect (per-image status, decode_packed raises ValueError).
 
 Replaces tf.image.decode_jpeg / decode_and_crop_jpeg (preprocessing/imagenet_preprocessing.py:81,92-93,296) for
 dct_method '' / 'INTEGER_ACCURATE' (nets/hparams_config.py:223).
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from .lib import JpegDesc, JpegInterval, JpegTables
+from . import lib, ops
+from .staging import slot_layout, stage_into, upload_table
 
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7,
                    14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39,
                    46, 53, 60, 61, 54, 47, 55, 62, 63], dtype=np.int64)
 MAX_SIDE = 8192
 
-DESC_DTYPE = np.dtype([('scan_offset', '<i8'), ('scan_bytes', '<i8'), ('coef_offset', '<i8'), ('plane_offset', '<i8'),
-                       ('dst_offset', '<i8'), ('width', '<i4'), ('height', '<i4'), ('ncomp', '<i4'), ('hs', '<i4'),
-                       ('vs', '<i4'), ('mcus_x', '<i4'), ('mcus_y', '<i4'), ('restart_interval', '<i4'),
-                       ('first_interval', '<i4'), ('n_intervals', '<i4'), ('qsel', 'u1', 4), ('dcsel', 'u1', 4),
-                       ('acsel', 'u1', 4), ('reserved', '<i4')])
-HUFF_DTYPE = np.dtype([('bits', 'u1', 16), ('vals', 'u1', 256)])
-TABLES_DTYPE = np.dtype([('quant', '<u2', (4, 64)), ('dc', HUFF_DTYPE, 2), ('ac', HUFF_DTYPE, 2)])
-INTERVAL_DTYPE = np.dtype([('image', '<i4'), ('first_mcu', '<i4'), ('n_mcus', '<i4'), ('rst', '<i4'),
-                           ('byte_begin', '<i8'), ('byte_end', '<i8')])
-assert DESC_DTYPE.itemsize == ctypes.sizeof(JpegDesc) == 96
-assert TABLES_DTYPE.itemsize == ctypes.sizeof(JpegTables) == 1600
-assert INTERVAL_DTYPE.itemsize == ctypes.sizeof(JpegInterval) == 32
+# the device tables, as numpy sees the structs of lib.py (include/asm_hip.h)
+DESC_DTYPE = np.dtype(lib.JpegDesc)
+HUFF_DTYPE = np.dtype(lib.JpegHuff)
+TABLES_DTYPE = np.dtype(lib.JpegTables)
+INTERVAL_DTYPE = np.dtype(lib.JpegInterval)
 
 
 def check_dct_method(dct_method: str):
@@ -333,13 +326,10 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
   # output slots, 16-byte aligned (the src layout of asm_resize_crop_flip): the device-decoded entries first, then the
   # already decoded ones back to back, so that those travel in one host-to-device copy
   pk.sizes = [(infos[k].height, infos[k].width) if k not in pk.fallback else pk.fallback[k].shape[:2] for k in range(n)]
-  padded = np.array([(h * w * 3 + 15) // 16 * 16 for h, w in pk.sizes], dtype=np.int64)
-  order = pk.dev_index + sorted(pk.fallback)
-  pk.offsets = np.zeros(n, np.int64)
-  if n:
-    pk.offsets[order] = np.concatenate([[0], np.cumsum(padded[order])[:-1]])
-  pk.host_begin = int(padded[pk.dev_index].sum())
-  pk.total_bytes = max(int(padded.sum()), 16)
+  hosted = sorted(pk.fallback)
+  pk.offsets, total = slot_layout([h * w * 3 for h, w in pk.sizes], pk.dev_index + hosted)
+  pk.host_begin = int(pk.offsets[hosted[0]]) if hosted else total
+  pk.total_bytes = max(total, 16)
   scan_at, blocks_at, rows = 0, 0, []
   chunks = []
   for row, k in enumerate(pk.dev_index):
@@ -395,18 +385,22 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
 def decode_packed(pk: Packed, device, stages: int = 3, check: bool = True, return_workspace: bool = False):
   """Run the device decode of a packed batch and copy the already decoded entries into their slots (one staged copy).
   Returns (uint8 device buffer of pk.total_bytes, int32 status per device row), plus ops.jpeg_decode's workspace
-  (raw coefficients first) when return_workspace."""
-  from . import ops
+  (raw coefficients first) when return_workspace.  check: wait for the decode, return the status on the host and raise
+  ValueError naming the entries whose entropy-coded data is corrupt."""
   dev = torch.device(device)
   dst = torch.empty(pk.total_bytes, dtype=torch.uint8, device=dev)
   status = ws = None
   if pk.dev_index:
-    up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1)).to(dev, non_blocking=False)
-    status, ws = ops.jpeg_decode(up(pk.files), up(pk.descs), up(pk.tables), up(pk.intervals), len(pk.dev_index),
-                                 len(pk.intervals), pk.total_blocks, pk.max_blocks, pk.max_pixels, dst, stages=stages,
-                                 check_status=check, names=pk.dev_index, return_workspace=True)
+    status, ws = ops.jpeg_decode(*(upload_table(t, dev) for t in (pk.files, pk.descs, pk.tables, pk.intervals)),
+                                 len(pk.dev_index), len(pk.intervals), pk.total_blocks, pk.max_blocks, pk.max_pixels, dst,
+                                 stages=stages)
+    if check:
+      status = status.cpu()
+      bad = torch.nonzero(status).reshape(-1).tolist()
+      if bad:
+        raise ValueError('jpeg_decode: corrupt entropy-coded data in entries %s (status %s)' % (
+            [pk.dev_index[b] for b in bad], [int(status[b]) for b in bad]))
   if pk.fallback:
-    from .input_pipeline import stage_into      # (input_pipeline imports this module)
     keys = sorted(pk.fallback)
     stage_into(dst[pk.host_begin:], [pk.fallback[k] for k in keys], [pk.offsets[k] - pk.host_begin for k in keys])
   return (dst, status, ws) if return_workspace else (dst, status)

@@ -27,6 +27,8 @@ class ImageDesc(C.Structure):
               ('flip', C.c_int32), ('reserved', C.c_int32)]
 
 
+assert C.sizeof(ImageDesc) == 56
+
 class AugmentOp(C.Structure):
   """struct asm_augment_op"""
   _fields_ = [('op', C.c_int32), ('a', C.c_int32), ('b', C.c_int32), ('reserved', C.c_int32), ('f', C.c_float * 6)]

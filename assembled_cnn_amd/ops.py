@@ -955,9 +955,9 @@ def eval_accumulate(conf, top1, top5, state33):
 
 def resize_crop_flip(src_u8, descs_dev, n, out_h, out_w, subtract_mean):
   """src_u8: 1-D uint8 device buffer with the decoded images back to back; descs_dev: uint8 device view of
-  n packed struct asm_image_desc (56 bytes each).  Returns float32 [n, out_h, out_w, 3]."""
-  if descs_dev.numel() != 56 * n:
-    raise ValueError('descriptor table must hold %d bytes' % (56 * n))
+  n packed struct asm_image_desc.  Returns float32 [n, out_h, out_w, 3]."""
+  if descs_dev.numel() != C.sizeof(_lib.ImageDesc) * n:
+    raise ValueError('descriptor table must hold %d bytes' % (C.sizeof(_lib.ImageDesc) * n))
   out = torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=src_u8.device)
   if n:
     check(L().asm_resize_crop_flip(_ptr(src_u8), src_u8.numel(), _ptr(descs_dev), n, out_h, out_w,
@@ -967,13 +967,13 @@ def resize_crop_flip(src_u8, descs_dev, n, out_h, out_w, subtract_mean):
 
 def autoaugment(images_f32, descs_dev, subtract_mean):
   """images_f32: float32 [n, H, W, 3] (resize_crop_flip's output without the mean subtraction); descs_dev: uint8 device
-  view of n packed struct asm_augment_desc (80 bytes each; autoaugment.sample / autoaugment.descriptor).  Returns the
+  view of n packed struct asm_augment_desc (autoaugment.sample / autoaugment.descriptor).  Returns the
   augmented batch, float32 [n, H, W, 3], integer-valued, minus CHANNEL_MEANS if subtract_mean.  One launch."""
   if images_f32.dim() != 4 or images_f32.shape[3] != 3 or images_f32.dtype != F32:
     raise ValueError('images must be float32 [n, H, W, 3]')
   n, H, W = int(images_f32.shape[0]), int(images_f32.shape[1]), int(images_f32.shape[2])
-  if descs_dev.numel() != 80 * n or descs_dev.dtype != torch.uint8:
-    raise ValueError('descriptor table must hold %d bytes' % (80 * n))
+  if descs_dev.numel() != C.sizeof(_lib.AugmentDesc) * n or descs_dev.dtype != torch.uint8:
+    raise ValueError('descriptor table must hold %d bytes' % (C.sizeof(_lib.AugmentDesc) * n))
   out = torch.empty_like(images_f32)
   if n:
     need = C.c_int64(0)
@@ -985,33 +985,25 @@ def autoaugment(images_f32, descs_dev, subtract_mean):
 
 
 def jpeg_decode(files_u8, descs_dev, tables_dev, intervals_dev, n, n_intervals, total_blocks, max_blocks, max_pixels, dst,
-                stages=3, check_status=True, names=None, return_workspace=False):
-  """asm_jpeg_decode for a batch packed by jpeg.pack: uint8 device views of the entropy-coded bytes, n struct asm_jpeg_desc
-  (96 bytes), n struct asm_jpeg_tables (1600 bytes) and n_intervals struct asm_jpeg_interval (32 bytes); dst: uint8 device
-  buffer the [H][W][3] images are written into.  Three launches.  Returns the int32 [n] status (on the host when
-  check_status, which waits for the decode and raises ValueError naming the entries whose entropy-coded data is corrupt;
-  `names` maps a row to the index to report).  return_workspace: (status, workspace) instead -- the uint8 device buffer
-  with the int16 coefficients [total_blocks][64] first, then the planes (tests compare the coefficients)."""
-  if descs_dev.numel() != 96 * n or tables_dev.numel() != 1600 * n or intervals_dev.numel() != 32 * n_intervals:
+                stages=3):
+  """asm_jpeg_decode for a batch packed by jpeg.pack: uint8 device views of the entropy-coded bytes, n struct asm_jpeg_desc,
+  n struct asm_jpeg_tables and n_intervals struct asm_jpeg_interval; dst: uint8 device buffer the [H][W][3] images are
+  written into.  Three launches, no synchronisation.  Returns (int32 [n] device status, one word of JPEG_E* bits per image;
+  workspace: the uint8 device buffer with the int16 coefficients [total_blocks][64] first, then the planes; None for n = 0).
+  jpeg.decode_packed reads the status and raises for corrupt entropy-coded data."""
+  if (descs_dev.numel() != C.sizeof(_lib.JpegDesc) * n or tables_dev.numel() != C.sizeof(_lib.JpegTables) * n or
+      intervals_dev.numel() != C.sizeof(_lib.JpegInterval) * n_intervals):
     raise ValueError('jpeg_decode: table sizes do not match n = %d, n_intervals = %d' % (n, n_intervals))
   status = torch.empty((max(n, 1),), dtype=torch.int32, device=dst.device)[:n]
   if n == 0:
-    status = status.cpu() if check_status else status
-    return (status, None) if return_workspace else status
+    return status, None
   need = C.c_int64(0)
   check(L().asm_jpeg_decode_workspace_bytes(total_blocks, C.byref(need)), 'jpeg_decode_workspace_bytes')
   ws = _workspace(max(need.value, 16), dst)
   check(L().asm_jpeg_decode(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev), _ptr(intervals_dev), n,
                             n_intervals, total_blocks, max_blocks, max_pixels, _ptr(dst), dst.numel(), _ptr(status),
                             _ptr(ws), ws.numel(), stages, _stream()), 'jpeg_decode')
-  if not check_status:
-    return (status, ws) if return_workspace else status
-  host = status.cpu()
-  bad = torch.nonzero(host).reshape(-1).tolist()
-  if bad:
-    raise ValueError('jpeg_decode: corrupt entropy-coded data in entries %s (status %s)' % (
-        [names[b] if names is not None else b for b in bad], [int(host[b]) for b in bad]))
-  return (host, ws) if return_workspace else host
+  return status, ws
 
 
 # ---------------------------------------------------------------------------------------------------

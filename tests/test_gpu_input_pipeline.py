@@ -70,3 +70,27 @@ def test_hip_pipeline_equals_reference_preprocess_image(hip_lib):
   (two crop types) and training branches, ragged sizes incl. 1 x 1 (tests/golden/reference_step.json)"""
   from tests.test_reference_step import check_preprocessing_against_reference
   check_preprocessing_against_reference('cuda', 'product')
+
+
+@pytest.mark.parametrize('subtract_mean', [True, False])
+def test_preprocess_batch_equals_the_pack_batch_route(hip_lib, subtract_mean):
+  from tests.test_input_path_cpu import check_preprocess_batch_equals_the_pack_batch_route
+  check_preprocess_batch_equals_the_pack_batch_route('cuda', subtract_mean)
+
+
+def test_back_to_back_batches_share_the_staging_buffer(hip_lib):
+  """The second batch is packed into the pinned buffer the first one's asynchronous copy reads: it must wait for that
+  copy (staging.fill), or the first result is made of the second batch's pixels."""
+  from assembled_cnn_amd import input_pipeline as P
+  first = [_img(32, 32, 40 + k) for k in range(4)]
+  second = [_img(16, 16, 50 + k) for k in range(2)]
+  run = lambda imgs: P.preprocess_batch(imgs, False, 'cuda', image_size=16)
+  alone = []
+  for imgs in (first, second):
+    out = run(imgs)
+    torch.cuda.synchronize()
+    alone.append(out.cpu())
+  a = run(first)
+  b = run(second)
+  assert torch.equal(a.cpu(), alone[0]) and torch.equal(b.cpu(), alone[1])
+  assert a.shape == (4, 16, 16, 3) and b.shape == (2, 16, 16, 3) and not torch.equal(alone[0][:2], alone[1])

@@ -65,12 +65,15 @@ def test_dataset_and_preprocessing_constants_match_reference():
   assert [float(v) for v in O.CHANNEL_MEANS] == means
   assert [round(float(v), 2) for v in IO.CHANNEL_MEANS] == means
   assert input_pipeline._RESIZE_MIN == GOLD['preprocessing']['RESIZE_MIN']
-  # the kernels carry the same three literals (mean subtraction fused into the input kernels)
-  here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-  for src in ('misc.hip', 'input.hip'):
-    text = open(os.path.join(here, 'assembled_cnn_amd', 'csrc', src)).read()
+  # the kernels carry the same three literals (mean subtraction fused into the input kernels): once, as common.h's
+  # ASM_CHANNEL_MEANS, which every kernel that subtracts the means initialises its array from
+  csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'assembled_cnn_amd', 'csrc')
+  assert ('#define ASM_CHANNEL_MEANS {%s}' % ', '.join('%.2ff' % m for m in means)) in open(os.path.join(csrc, 'common.h')).read()
+  for src, uses in (('misc.hip', 2), ('input.hip', 1), ('autoaugment.hip', 1)):
+    text = open(os.path.join(csrc, src)).read()
+    assert text.count('= ASM_CHANNEL_MEANS;') == uses, src
     for m in means:
-      assert ('%.2ff' % m) in text, (src, m)
+      assert ('%.2f' % m) not in text, (src, m)
 
 
 def test_loss_scale_rule_matches_reference():

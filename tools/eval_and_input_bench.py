@@ -6,7 +6,7 @@ import os, sys, time
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from assembled_cnn_amd import autoaugment as A, input_pipeline as P, ops
+from assembled_cnn_amd import autoaugment as A, input_pipeline as P, ops, staging
 from assembled_cnn_amd.train import HParams, Trainer
 
 
@@ -48,12 +48,11 @@ def jpeg_leg(n=256):
     source = 'Pillow not importable: the 8 largest test fixtures tiled (%s)' % ', '.join(big)
   print('jpeg: %d files, %s; mean %.1f KB' % (n, source, sum(map(len, files)) / n / 1e3))
   pk = jpeg.pack(files)
-  up = lambda a: torch.from_numpy(a.view(np.uint8).reshape(-1)).cuda()
-  fd, dd, td, ivd = up(pk.files), up(pk.descs), up(pk.tables), up(pk.intervals)
+  fd, dd, td, ivd = (staging.upload_table(t, 'cuda') for t in (pk.files, pk.descs, pk.tables, pk.intervals))
   dst = torch.empty(pk.total_bytes, dtype=torch.uint8, device='cuda')
   run = lambda stages: ops.jpeg_decode(fd, dd, td, ivd, n, len(pk.intervals), pk.total_blocks, pk.max_blocks, pk.max_pixels, dst,
-                                       stages=stages, check_status=False)
-  assert not ops.jpeg_decode(fd, dd, td, ivd, n, len(pk.intervals), pk.total_blocks, pk.max_blocks, pk.max_pixels, dst).any()
+                                       stages=stages)
+  assert not run(3)[0].any()
   ms_e, ms_p = ev(lambda: run(1), iters=3), ev(lambda: run(2), iters=10)
   whole = []
   for _ in range(3):
@@ -106,7 +105,7 @@ for training, side, ptype in ((True, 224, 'imagenet'), (False, 256, 'imagenet_22
     for what, descs in (('imagenet policy, sampled', A.sample('imagenet', len(imgs), side, side, rng)),
                         ('both slots Equalize', both('Equalize')), ('both slots Rotate 30', both('Rotate', 30.0)),
                         ('both slots Sharpness 1.9', both('Sharpness', 1.9)), ('pass-through', np.repeat(A.descriptor([], side, side), len(imgs)))):
-      ad = torch.from_numpy(descs.view(np.uint8).copy()).cuda()
+      ad = staging.upload_table(descs, 'cuda')
       ms_aa = ev(lambda: ops.autoaugment(resized, ad, True))
       print('autoaugment %-26s %dx%d: kernel %.3f ms for 256 images (%.0f k img/s; resize_crop_flip above: %.3f ms)'
             % (what, side, side, ms_aa, 256 / ms_aa, ms))
