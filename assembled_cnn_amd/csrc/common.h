@@ -37,7 +37,7 @@ inline thread_local int asm_unchecked_launches = 0;
 // which convolution kernel family the last forward / input-gradient call of this thread launched (tests assert the plan a
 // shape gets: asm_debug_last_conv_kernel, include/asm_hip_debug.h), numbered as ConvFamily (igemm_common.h): 0 FAM_GENERAL
 // (igemm_kernel), 1 FAM_GEMM1 (conv_gemm1), 2 FAM_IGEMM2, 3 FAM_IGEMM3, 4 FAM_HALO (conv_halo), 5 FAM_DGRAD_S2 (conv_dgrad_s2),
-// 8 FAM_IGEMM8
+// 6 FAM_DENSE (dense_small), 8 FAM_IGEMM8
 inline thread_local int asm_last_conv_kernel = -1;
 void asm_count_launch();             // plan.hip: process-wide kernel-launch counter (asm_launch_count)
 // tape.hip: while THIS host thread records a launch tape (asm_tape_begin .. asm_tape_end) every launch is also written

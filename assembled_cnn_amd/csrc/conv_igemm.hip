@@ -996,6 +996,7 @@ unsigned family_variants(int family, const IGemmArgs& a, const ConvTile& t) {
     case FAM_GENERAL: return epi_bit(EPI_F32) | epi_bit(EPI_BNRED) | epi_bit(EPI_STATS) | epi_bit(EPI_PLAIN);
     case FAM_IGEMM2: return igemm2_variants(a.R, a.S, t.bm, t.bn, t.bk);
     case FAM_HALO: return epi_bit(EPI_STATS) | epi_bit(EPI_PLAIN);
+    case FAM_DENSE: return epi_bit(EPI_F32) | epi_bit(EPI_PLAIN);
     case FAM_GEMM1: return epi_bit(EPI_BNRED) | epi_bit(EPI_STATS) | epi_bit(EPI_POOL) | epi_bit(EPI_PFA) | epi_bit(EPI_PLAIN);
     default: return epi_bit(EPI_BNRED) | epi_bit(EPI_STATS) | epi_bit(EPI_PFA) | epi_bit(EPI_PLAIN);   // igemm3, igemm8
   }
@@ -1028,10 +1029,25 @@ ConvLaunch tiled(int family, ConvTile t, const IGemmArgs& a, ConvOut out, int M,
 ConvPlan single(const ConvLaunch& L) { return ConvPlan{1, {L, {}}, nullptr}; }
 ConvPlan no_plan(const char* why) { return ConvPlan{0, {}, why}; }
 
+// asm_dense_shaped as fprop_impl / dgrad_args describe the layer (they resolve a zero pitch to the packed one)
+bool dense_shaped(const IGemmArgs& a) {
+  return a.Hi == 1 && a.Wi == 1 && a.HoWo == 1 && a.R == 1 && a.S == 1 && a.x_img_pitch == a.Ci && a.x_row_pitch == a.Ci &&
+         a.x_pix_pitch == a.Ci;
+}
+// Does dense_small_kernel take the launch?  Forward and input gradient alike (dgrad_args maps dy / wt / dx onto x / w / y): a
+// dense-shaped layer that writes the plain product (+ an unmasked addend) to rows asm_dense_small accepts, from 16-byte aligned
+// operands (an absent one counts as aligned); asm_tuning.dense_small = 0: never.
+bool dense_covers(const IGemmArgs& a, ConvOut out) {
+  if (!asm_tune().dense_small || !dense_shaped(a) || a.Ci % 16 || (out != ConvOut::bf16 && out != ConvOut::f32)) return false;
+  if (a.addend_mask || a.pool_dy || a.bn_scale || a.y_strided) return false;
+  if (a.ldy % 4 || a.ldy > cdiv(a.Co, 32) * 32) return false;   // the pad columns end inside the last 32-column tile
+  return asm_aligned16(a.x) && asm_aligned16(a.w) && asm_aligned16(a.y) && asm_aligned16(a.addend);
+}
+
 // The kernel of a forward / input-gradient layer: family, tile, epilogue variant, grid.  Pure: reads the arguments,
 // asm_tuning and the CU count only.  Where a family's coverage predicate accepts the layer, it takes it, in this order:
-// conv_halo (the narrow 112-wide 3x3 layers), igemm1 (the 1x1 layers of conv_gemm1.hip's table), igemm8 / igemm3 (3x3 stride 1),
-// igemm2 (the gather-free general form), the general kernel.  asm_tuning.igemm_mode = 1 sends every layer to the general kernel,
+// dense_small (the [N,1,1,C] layers, whatever igemm_mode / igemm_tile say), conv_halo (the narrow 112-wide 3x3 layers), igemm1
+// (the 1x1 layers of conv_gemm1.hip's table), igemm8 / igemm3 (3x3 stride 1), igemm2 (the gather-free general form), the general kernel.  asm_tuning.igemm_mode = 1 sends every layer to the general kernel,
 // igemm_tile != 0 keeps the specialised families out.
 ConvPlan plan_conv(const IGemmArgs& a, ConvOut out) {
   const asm_tuning& tu = asm_tune();
@@ -1040,6 +1056,10 @@ ConvPlan plan_conv(const IGemmArgs& a, ConvOut out) {
   // the batch-norm backward sums of a 3x3 input gradient: only igemm8 and igemm3 have that instantiation (in the bandwidth-bound
   // halo kernel of the 112-wide maps the y reads cost 0.22 ms per step and saved 0.09 of reduce passes: measured, removed)
   const bool bnred3 = out == ConvOut::bnred && !k1;
+  // (32 x 32 output tiles, 16-channel steps split over the workgroup's four waves)
+  if (dense_covers(a, out)) return single(tiled(FAM_DENSE, ConvTile{32, 32, 16, 1, 1}, a, out, a.M, 0));
+  if (dense_shaped(a) && (a.pool_dy || out == ConvOut::bnred))
+    return no_plan("conv dgrad: the fused input-gradient forms do not take a [N,1,1,C] layer");
   if (a.pool_dy && (tu.igemm_mode != 0 || out != ConvOut::bf16 || !k1 || a.y_strided))
     return no_plan("conv dgrad_pooled: only the 1x1 stride-1 igemm2 path folds an average-pool backward in");
   if (tu.igemm_mode == 0 && tu.igemm_tile == 0) {
@@ -1130,6 +1150,9 @@ int run_plan(const ConvPlan& p, IGemmArgs a, hipStream_t st) {
                           : (L.t.bk == 64 ? launch_halo<64, 64, 2, 2>(L, a, st) : launch_halo<64, 32, 2, 2>(L, a, st));
         break;
       case FAM_IGEMM8: rc = asm_igemm8_launch(L, a, st); break;
+      case FAM_DENSE:
+        rc = asm_dense_small_launch(a.x, a.Ci, a.w, a.Ci, a.M, a.Co, a.Ci, a.y, a.ldy, L.epi == EPI_F32, a.addend, st);
+        break;
       default: ASM_FAIL(ASM_EINVAL, "conv: no kernel family %d", L.family);
     }
     if (rc != ASM_OK) return rc;
@@ -1248,8 +1271,9 @@ bool asm_dgrad_s2_covers(const asm_conv_desc* d);
 int asm_dgrad_s2_launch(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend, const uint8_t* addend_mask,
                         void* dx, void* stream);
 
-// The kernels of an input gradient, all chosen before the first launch: dgrad_s2_kernel, the parity classes of a stride-2 layer,
-// or the plan_conv plan of the generic gather (which also carries an ASM_ENOTSUP).
+// The kernels of an input gradient, all chosen before the first launch: dense_small_kernel (through plan_conv, whatever the
+// stride of the [N,1,1,C] layer), dgrad_s2_kernel, the parity classes of a stride-2 layer, or the plan_conv plan of the generic
+// gather (which also carries an ASM_ENOTSUP).
 enum class DgradForm { conv, parity, s2 };
 struct DgradPlan {
   DgradForm form;
@@ -1266,6 +1290,10 @@ static DgradPlan plan_dgrad(const asm_conv_desc* d, const IGemmArgs& a, ConvOut 
   DgradPlan p = {};
   const asm_tuning& tu = asm_tune();
   const bool k3 = d->R == 3 && d->S == 3, k1 = d->R == 1 && d->S == 1 && d->pad == 0;
+  if (dense_covers(a, out)) {
+    p.conv = plan_conv(a, out);
+    return p;
+  }
   if (aligned && !a.pool_dy && asm_dgrad_s2_covers(d)) {   // all four parity classes in one launch
     p.form = DgradForm::s2;
     return p;

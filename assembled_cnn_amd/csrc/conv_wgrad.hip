@@ -14,6 +14,7 @@
 // [split][Co][cols]; asm_wgrad_reduce sums the slabs in a fixed order (no atomics ->
 // bit-reproducible).  With one split the tile goes straight to dW.
 #include "common.h"
+#include "igemm_common.h"
 #include "../../include/asm_hip_debug.h"
 #include <math.h>
 #include <stdlib.h>
@@ -740,11 +741,11 @@ __global__ __launch_bounds__((WHalo<KF, CI, PH, PW>::NTHR)) void wgrad_halo_kern
 
 // ---- the plan: plan_wgrad decides, asm_conv2d_wgrad launches ----
 // the kernel forms: wgrad_halo_kernel; wgrad_kernel with 128-wide column tiles, register-staged or (1x1, LIN) by LDS-DMA into a
-// two-stage ring; wgrad8_kernel, the 256 x 256 tile
-enum class WgradForm { halo, reg, ring, big };
+// two-stage ring; wgrad8_kernel, the 256 x 256 tile; dense_small_wgrad_kernel (dense_small.hip) for the [N,1,1,C] layers
+enum class WgradForm { halo, reg, ring, big, dense };
 
 // asm_conv2d_wgrad_plan reports a plan as {bnw, bcw, tiles_n, tiles_c, splits, m_per_split}, the halo form as {K, -1, 1, 1,
-// workgroups per K / KF slice (= slabs), pixels per workgroup}.
+// workgroups per K / KF slice (= slabs), pixels per workgroup}, the dense form as {K, -2, cdiv(K, 32), cdiv(C, 32), 1, N}.
 struct WgradPlan {
   WgradForm form;
   int kf, ci, pw;                 // halo: output channels per workgroup (64 for K = 128), input channels, patch width (16 / 56 / 28)
@@ -816,6 +817,15 @@ bool wgrad_ring(const asm_conv_desc* d) {
 // asm_tuning only.
 WgradPlan plan_wgrad(const asm_conv_desc* d) {
   WgradPlan p = {};
+  // a [N,1,1,C] layer: dw = dy^T . x over a few hundred rows, 32 x 32 tiles of dW each written by one workgroup (no slabs);
+  // asm_tuning.dense_small = 0 keeps it on wgrad_kernel
+  if (asm_tune().dense_small && asm_dense_shaped(d) && d->N <= 1024) {
+    p.form = WgradForm::dense;
+    p.bnw = d->K; p.bcw = -2;                   // what asm_conv2d_wgrad_plan reports for the form
+    p.tiles_n = cdiv(d->K, 32); p.tiles_c = cdiv(d->C, 32); p.splits = 1; p.m_per_split = d->N;
+    p.grid = p.tiles_n * p.tiles_c; p.block = 256;
+    return p;
+  }
   const int cols = d->R * d->S * d->C;
   const int pw = halo_patch_w(d);
   if (const int hb = wgrad_halo_blocks(d, pw)) {
@@ -958,6 +968,10 @@ extern "C" int asm_conv2d_wgrad(const asm_conv_desc* d, const void* x, const voi
   const WgradPlan pl = plan_wgrad(d);
   ASM_REQUIRE(pl.workspace == 0 || (workspace && workspace_bytes >= pl.workspace), "conv wgrad: workspace too small (%zu < %zu)",
               workspace_bytes, pl.workspace);
+  if (pl.form == WgradForm::dense) {
+    ASM_REQUIRE(asm_aligned16(dw), "conv wgrad: unaligned dw");
+    return asm_dense_small_wgrad_launch(x, d->C, dy, ldy, d->N, d->C, d->K, dw, d->C, (hipStream_t)stream);
+  }
   WgradArgs a;
   a.dy = dy; a.x = x;
   a.out = pl.slabs ? reinterpret_cast<float*>(workspace) : dw;

@@ -13,6 +13,7 @@
 // Fragment convention (as csrc/conv_igemm.hip): acc = mfma_32x32x16(A = q rows, B = p rows): lane l holds row (l & 31),
 // reduction elements (l >> 5) * 8 .. +8; acc[r] = out[m = l & 31][n = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5)].
 #include "common.h"
+#include "igemm_common.h"
 
 namespace {
 
@@ -184,9 +185,23 @@ __global__ __launch_bounds__(256) void dense_small_wgrad_kernel(DenseWgradArgs a
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
+
+int asm_dense_small_launch(const void* p, int ldp, const void* q, int ldq, int M, int N, int K, void* out, int ldo, bool out_f32,
+                           const void* addend, hipStream_t st) {
+  const DenseArgs a = {(const bf16_t*)p, (const bf16_t*)q, out, (const bf16_t*)addend, ldp, ldq, ldo, M, N, K, out_f32 ? 1 : 0};
+  ASM_LAUNCH(dense_small_kernel, dim3(cdiv(N, 32), cdiv(M, 32)), dim3(256), 0, st, a);
+  ASM_CHECK_LAUNCH("dense_small");
+  return ASM_OK;
+}
+
+int asm_dense_small_wgrad_launch(const void* x, int ldx, const void* dy, int ldy, int M, int Cin, int Cout, float* dw, int ldw,
+                                 hipStream_t st) {
+  const DenseWgradArgs a = {(const bf16_t*)x, (const bf16_t*)dy, dw, ldx, ldy, ldw, M, Cin, Cout};
+  ASM_LAUNCH(dense_small_wgrad_kernel, dim3(cdiv(Cin, 32), cdiv(Cout, 32)), dim3(256), 0, st, a);
+  ASM_CHECK_LAUNCH("dense_small_wgrad");
+  return ASM_OK;
+}
 
 extern "C" int asm_dense_small(const void* p, int ldp, const void* q, int ldq, int M, int N, int K, void* out, int ldo,
                                int out_f32, const void* addend, void* stream) {
@@ -199,24 +214,14 @@ extern "C" int asm_dense_small(const void* p, int ldp, const void* q, int ldq, i
   // than half-zeroed or clobbered
   ASM_REQUIRE(ldo <= cdiv(N, 32) * 32, "dense_small: row stride %d pads N=%d past its last 32-column tile (out must own whole rows "
               "with fewer than 32 pad columns)", ldo, N);
-  ASM_REQUIRE(aligned16(p) && aligned16(q) && aligned16(out) && (!addend || aligned16(addend)), "dense_small: unaligned pointer");
-  DenseArgs a;
-  a.p = (const bf16_t*)p; a.q = (const bf16_t*)q; a.out = out; a.addend = (const bf16_t*)addend;
-  a.ldp = ldp; a.ldq = ldq; a.ldo = ldo; a.M = M; a.N = N; a.K = K; a.out_f32 = out_f32 ? 1 : 0;
-  ASM_LAUNCH(dense_small_kernel, dim3(cdiv(N, 32), cdiv(M, 32)), dim3(256), 0, (hipStream_t)stream, a);
-  ASM_CHECK_LAUNCH("dense_small");
-  return ASM_OK;
+  ASM_REQUIRE(asm_aligned16(p) && asm_aligned16(q) && asm_aligned16(out) && asm_aligned16(addend), "dense_small: unaligned pointer");
+  return asm_dense_small_launch(p, ldp, q, ldq, M, N, K, out, ldo, out_f32 != 0, addend, (hipStream_t)stream);
 }
 
 extern "C" int asm_dense_small_wgrad(const void* x, int ldx, const void* dy, int ldy, int M, int Cin, int Cout, float* dw,
                                      int ldw, void* stream) {
   ASM_REQUIRE(x && dy && dw && M > 0 && Cin > 0 && Cout > 0, "dense_small_wgrad: bad arguments");
   ASM_REQUIRE(ldx >= Cin && ldy >= Cout && ldw >= Cin && ldw % 4 == 0, "dense_small_wgrad: bad row strides");
-  ASM_REQUIRE(aligned16(dw), "dense_small_wgrad: unaligned pointer");
-  DenseWgradArgs a;
-  a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.dw = dw; a.ldx = ldx; a.ldy = ldy; a.ldw = ldw;
-  a.M = M; a.Cin = Cin; a.Cout = Cout;
-  ASM_LAUNCH(dense_small_wgrad_kernel, dim3(cdiv(Cin, 32), cdiv(Cout, 32)), dim3(256), 0, (hipStream_t)stream, a);
-  ASM_CHECK_LAUNCH("dense_small_wgrad");
-  return ASM_OK;
+  ASM_REQUIRE(asm_aligned16(dw), "dense_small_wgrad: unaligned pointer");
+  return asm_dense_small_wgrad_launch(x, ldx, dy, ldy, M, Cin, Cout, dw, ldw, (hipStream_t)stream);
 }

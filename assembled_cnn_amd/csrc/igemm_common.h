@@ -4,6 +4,21 @@
 #pragma once
 #include "common.h"
 
+// ---- the [N,1,1,C] squeeze / excite / classifier layers (dense_small.hip) ----
+// Is d one?  A 1x1 image under a 1x1 filter with packed rows: the layer is a row-major product [N][C] x [K][C]^T.
+static inline bool asm_dense_shaped(const asm_conv_desc* d) {
+  return d->H == 1 && d->W == 1 && d->Ho == 1 && d->Wo == 1 && d->R == 1 && d->S == 1 && d->C % 8 == 0 &&
+         (d->x_img_pitch == 0 || d->x_img_pitch == d->C) && (d->x_row_pitch == 0 || d->x_row_pitch == d->C) &&
+         (d->x_pix_pitch == 0 || d->x_pix_pitch == d->C);
+}
+// The launches behind asm_dense_small / asm_dense_small_wgrad, arguments as theirs and NOT checked again: plan_conv
+// (conv_igemm.hip) and plan_wgrad (conv_wgrad.hip) pick them only where those checks hold.
+int asm_dense_small_launch(const void* p, int ldp, const void* q, int ldq, int M, int N, int K, void* out, int ldo, bool out_f32,
+                           const void* addend, hipStream_t st);
+int asm_dense_small_wgrad_launch(const void* x, int ldx, const void* dy, int ldy, int M, int Cin, int Cout, float* dw, int ldw,
+                                 hipStream_t st);
+static inline bool asm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
 namespace asm_igemm {
 
 struct IGemmArgs {
@@ -51,7 +66,7 @@ constexpr int STATS_BM = 128;  // rows per statistics partial (asm_conv2d_stats_
 
 // ---- the kernel a forward / input-gradient launch runs: plan_conv (conv_igemm.hip) decides, run_plan launches ----
 // kernel families, numbered as asm_debug_last_conv_kernel reports them
-enum ConvFamily { FAM_GENERAL = 0, FAM_GEMM1 = 1, FAM_IGEMM2 = 2, FAM_IGEMM3 = 3, FAM_HALO = 4, FAM_DGRAD_S2 = 5, FAM_IGEMM8 = 8 };
+enum ConvFamily { FAM_GENERAL = 0, FAM_GEMM1 = 1, FAM_IGEMM2 = 2, FAM_IGEMM3 = 3, FAM_HALO = 4, FAM_DGRAD_S2 = 5, FAM_DENSE = 6, FAM_IGEMM8 = 8 };
 // epilogue variant (igemm_epilogue's template flags): plain, addend-prefetching (PFA), pooled-gradient gather, statistics,
 // batch-norm backward sums (BNRED), f32 output
 enum ConvEpi { EPI_PLAIN, EPI_PFA, EPI_POOL, EPI_STATS, EPI_BNRED, EPI_F32 };

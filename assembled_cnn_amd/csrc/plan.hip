@@ -312,7 +312,7 @@ namespace {
 asm_tuning make_default_tuning() {
   asm_tuning t = {};
   t.igemm_mode = 0; t.igemm_tile = 0; t.igemm_pfa = -1; t.dgrad_parity = 2; t.wgrad_halo = 1; t.wgrad_big = -1; t.wgrad_splits = 0;
-  t.bn_rows = 1024; t.igemm3 = 3; t.gemm1 = -1; t.wgrad_ring = -1; t.igemm8 = 1;
+  t.bn_rows = 1024; t.igemm3 = 3; t.gemm1 = -1; t.wgrad_ring = -1; t.igemm8 = 1; t.dense_small = 1;
   return t;
 }
 asm_tuning g_tuning = make_default_tuning();
@@ -326,7 +326,7 @@ extern "C" int asm_set_tuning(const asm_tuning* t) {
   if (t && (t->bn_rows <= 0 || t->igemm_mode < 0 || t->igemm_mode > 1 || (t->igemm_tile != 0 && t->igemm_tile != 1 && t->igemm_tile != 3) ||
             t->igemm_pfa < -1 || t->igemm_pfa > 1 || t->dgrad_parity < 0 || t->dgrad_parity > 2 || t->wgrad_halo < 0 || t->wgrad_halo > 2 ||
             t->wgrad_big < -1 || t->wgrad_big > 1 || t->wgrad_splits < 0 || t->igemm3 < 0 || t->igemm3 > 3 || t->gemm1 < -2 ||
-            t->wgrad_ring < -1 || t->igemm8 < 0 || t->igemm8 > 2))
+            t->wgrad_ring < -1 || t->igemm8 < 0 || t->igemm8 > 2 || t->dense_small < 0 || t->dense_small > 1))
     ASM_FAIL(ASM_EINVAL, "asm_set_tuning: field out of range");
   g_tuning = t ? *t : make_default_tuning();
   return ASM_OK;

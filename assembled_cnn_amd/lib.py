@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('ASM_HIP_LIB') or os.path.join(HERE, 'libasm_hip.so')
 
 ASM_OK, ASM_EINVAL, ASM_ENOTSUP, ASM_EHIP = 0, -1, -2, -3
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class AsmError(RuntimeError):
@@ -106,14 +106,14 @@ class Tuning(C.Structure):
   """struct asm_tuning: the kernel-selection overrides (the library itself reads no environment variable)"""
   _fields_ = [(n, C.c_int32) for n in (
       'igemm_mode', 'igemm_tile', 'igemm_pfa', 'dgrad_parity', 'wgrad_halo', 'wgrad_big', 'wgrad_splits', 'bn_rows', 'igemm3',
-      'gemm1', 'wgrad_ring', 'igemm8')]
+      'gemm1', 'wgrad_ring', 'igemm8', 'dense_small')]
 
 
 # environment variable of the HOST -> asm_tuning field (same-box A/B runs, tests); unset = the library's default
 TUNING_ENV = {'ASM_IGEMM_MODE': 'igemm_mode', 'ASM_IGEMM_TILE': 'igemm_tile', 'ASM_IGEMM_PFA': 'igemm_pfa',
               'ASM_DGRAD_PARITY': 'dgrad_parity', 'ASM_WGRAD_HALO': 'wgrad_halo', 'ASM_WGRAD_BIG': 'wgrad_big',
               'ASM_WGRAD_SPLITS': 'wgrad_splits', 'ASM_BN_ROWS': 'bn_rows', 'ASM_IGEMM3': 'igemm3', 'ASM_GEMM1': 'gemm1',
-              'ASM_WGRAD_RING': 'wgrad_ring', 'ASM_IGEMM8': 'igemm8'}
+              'ASM_WGRAD_RING': 'wgrad_ring', 'ASM_IGEMM8': 'igemm8', 'ASM_DENSE_SMALL': 'dense_small'}
 
 
 def apply_env_tuning(lib) -> 'Tuning':
@@ -133,6 +133,7 @@ def apply_env_tuning(lib) -> 'Tuning':
 ASM_F32, ASM_BF16, ASM_F16 = 0, 1, 2
 ASM_DGRAD_MASKED, ASM_DGRAD_POOLED, ASM_DGRAD_BNRED = 1, 2, 4     # asm_conv2d_dgrad_kernel variants
 CONV_DGRAD_S2 = 5       # asm_conv2d_dgrad_kernel's number of the one-launch 3x3 / stride-2 input gradient
+CONV_DENSE = 6          # ... and of a [N,1,1,C] layer on csrc/dense_small.hip
 ASM_AA_SCONV, ASM_AA_PROJ = 1, 2
 POOL_TYPES = {'gap': 0, 'gem': 1, 'flatten': 2}
 (PLAN_CONV, PLAN_BN, PLAN_DENSE, PLAN_MAXPOOL, PLAN_AVGPOOL, PLAN_BLURPOOL, PLAN_GAP, PLAN_GEM, PLAN_FLATTEN, PLAN_SK_GAP,

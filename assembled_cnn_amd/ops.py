@@ -244,16 +244,6 @@ def _bn_ev(nbytes):
   return _TIMER.start_class('bn', nbytes) if (_TIMER is not None and _TIMER.classes) else None
 
 
-def dense_small_on() -> bool:
-  """ASM_DENSE_SMALL=0 keeps the [N,1,1,C] layers on the implicit-GEMM convolution (A/B runs, tests); cached until refresh_tuning()."""
-  return knob('ASM_DENSE_SMALL', '1') != '0'
-
-
-def _is_dense(d: ConvDesc) -> bool:
-  return (d.H == 1 and d.W == 1 and d.Ho == 1 and d.Wo == 1 and d.R == 1 and d.S == 1 and d.x_img_pitch in (0, d.C)
-          and d.x_row_pitch in (0, d.C) and d.x_pix_pitch in (0, d.C) and d.C % 8 == 0)
-
-
 def conv_fprop(d: ConvDesc, x: torch.Tensor, w: torch.Tensor, want_stats: bool = False
                ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
   """y [N,Ho,Wo,ldy] (bf16 or f32) and, if want_stats, the BN partials [blocks,2,K] (f32)."""
@@ -263,12 +253,7 @@ def conv_fprop(d: ConvDesc, x: torch.Tensor, w: torch.Tensor, want_stats: bool =
   if want_stats:
     stats = empty((L().asm_conv2d_stats_blocks(C.byref(d)), 2, d.K), F32, x)
   ev = _TIMER.start('fprop', d) if _TIMER is not None else None
-  if not want_stats and _is_dense(d) and d.C % 16 == 0 and dense_small_on():
-    # [N,1,1,C] squeeze / excite / classifier layer: row-major product, no implicit-GEMM machinery (csrc/dense_small.hip)
-    check(L().asm_dense_small(_ptr(x), d.C, _ptr(w), d.C, d.N, d.K, d.C, _ptr(y), ldy, 1 if d.out_f32 else 0, None,
-                              _stream()), 'dense_small')
-  else:
-    check(L().asm_conv2d_fprop(C.byref(d), _ptr(x), _ptr(w), _ptr(y), _ptr(stats), _stream()), 'conv2d_fprop')
+  check(L().asm_conv2d_fprop(C.byref(d), _ptr(x), _ptr(w), _ptr(y), _ptr(stats), _stream()), 'conv2d_fprop')
   if ev is not None:
     ev.record()
   return y, stats
@@ -300,7 +285,7 @@ def dgrad_pool_ok(d: ConvDesc) -> bool:
   """can asm_conv2d_dgrad_pooled take this layer?  ASM_POOL_FUSE=0: never"""
   # K % 32: the library also covers narrower reductions (K <= the tile's 32 / 64 channels), which have never been fused --
   # the host keeps the rule that held when the pooled epilogue was introduced
-  return (knob('ASM_POOL_FUSE', '1') != '0' and not _is_dense(d) and d.K % 32 == 0
+  return (knob('ASM_POOL_FUSE', '1') != '0' and d.K % 32 == 0
           and dgrad_kernel(d, _lib.ASM_DGRAD_POOLED) >= 0)
 
 
@@ -315,7 +300,7 @@ def dgrad_bnred_ok(d: ConvDesc) -> bool:
   library covers: the 1x1 stride-1 layers and the 3x3 stride-1 layers of its igemm8 / igemm3 kernels.  ASM_BN_RED=0: never;
   ASM_BN_RED=1x1: the 1x1 layers only (round 6 A/B)"""
   mode = knob('ASM_BN_RED', '1')
-  if mode == '0' or _is_dense(d) or (mode == '1x1' and d.R != 1):
+  if mode == '0' or (mode == '1x1' and d.R != 1):
     return False
   return dgrad_kernel(d, _lib.ASM_DGRAD_BNRED) >= 0
 
@@ -350,11 +335,7 @@ def conv_dgrad(d: ConvDesc, dy: torch.Tensor, wt: torch.Tensor, addend: Optional
     if ev is not None:
       ev.record()
     return dx
-  if addend_mask is None and _is_dense(d) and d.K % 16 == 0 and dense_small_on():
-    # dy [N][K] (row stride K: a padded Cout arrives as K = kpad), wt = CRSK copy [C][K]
-    check(L().asm_dense_small(_ptr(dy), d.K, _ptr(wt), d.K, d.N, d.C, d.K, _ptr(dx), d.C, 0, _ptr(addend), _stream()),
-          'dense_small')
-  elif addend_mask is not None:
+  if addend_mask is not None:
     check(L().asm_conv2d_dgrad_masked(C.byref(d), _ptr(dy), _ptr(wt), _ptr(addend), _ptr(addend_mask), _ptr(dx),
                                       _stream()), 'conv2d_dgrad_masked')
   else:
@@ -390,12 +371,6 @@ def conv_wgrad(d: ConvDesc, x: torch.Tensor, dy: torch.Tensor, dw: torch.Tensor)
   need = L().asm_conv2d_wgrad_workspace_bytes(C.byref(d))
   ws = _workspace(need, x)
   ev = _TIMER.start('wgrad', d) if _TIMER is not None else None
-  if _is_dense(d) and d.N <= 1024 and dense_small_on():     # [N,1,1,C] layer: dw = dy^T . x over a few hundred rows
-    check(L().asm_dense_small_wgrad(_ptr(x), d.C, _ptr(dy), d.ldy if d.ldy else d.K, d.N, d.C, d.K, _ptr(dw), d.C,
-                                    _stream()), 'dense_small_wgrad')
-    if ev is not None:
-      ev.record()
-    return
   check(L().asm_conv2d_wgrad(C.byref(d), _ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), need, _stream()), 'conv2d_wgrad')
   if ev is not None:
     ev.record()

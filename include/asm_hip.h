@@ -35,7 +35,7 @@ extern "C" {
 #define ASM_ENOTSUP (-2)
 #define ASM_EHIP (-3)
 
-#define ASM_ABI_VERSION 10
+#define ASM_ABI_VERSION 11
 
 const char* asm_last_error(void);
 int asm_abi_version(void);
@@ -111,6 +111,8 @@ typedef struct asm_tuning {
                               multi-phase 256 x 256 kernel (igemm8_kernel, csrc/conv_igemm8.hip; bit-identical to igemm2's
                               256 x 256 tile): 1 where the layer took the 256 x 256 tile, the ragged last round on the
                               128-row kernel (default); 2 wherever the shape allows, unsplit; 0 never                     */
+  int32_t dense_small;     /* the [N,1,1,C] squeeze / excite / classifier layers (forward, input and weight gradient) on the
+                              row-major products of csrc/dense_small.hip: 1 (default); 0: on the convolution kernels          */
 } asm_tuning;
 void asm_tuning_defaults(asm_tuning* t);
 int asm_set_tuning(const asm_tuning* t);
@@ -121,6 +123,10 @@ void asm_get_tuning(asm_tuning* t);
  * the 1x1 "fc" convs of sk_conv2d / se_block (nets/blocks.py:139-147,172-181), the embedding conv
  * (nets/resnet_model.py:576-580) and tf.layers.dense (nets/resnet_model.py:595-597; a 1x1 conv on a
  * 1x1 image).  No bias (use_bias=False everywhere on this path; dense bias is added by asm_bias_add).
+ * Those [N,1,1,C] layers (H = W = Ho = Wo = R = S = 1, packed x rows) run on the kernels of csrc/dense_small.hip unless
+ * asm_tuning.dense_small is 0: asm_conv2d_fprop without statistics and asm_conv2d_dgrad (with or without addend) where the
+ * reduction is a multiple of 16, the output row stride one asm_dense_small accepts and the operands 16-byte aligned;
+ * asm_conv2d_wgrad up to N = 1024, without a workspace.  Everything else about them stays on the convolution kernels.
  *
  * Geometry: input  x [N, H, W, C] with element pitches (img_pitch, row_pitch, pix_pitch) so that a
  * pre-padded or channel-padded buffer can be addressed (the 7x7x3 stem runs as R=7,S=1,C=32 over a
@@ -177,8 +183,8 @@ int asm_conv2d_dgrad_masked(const asm_conv_desc* d, const void* dy, const void* 
  * avgpool_bwd(pool_dy) -- the block input of a projection bottleneck is read by conv1 (1x1, stride 1) and by the shortcut's
  * average pool (nets/resnet_model.py:123-141); with the shortcut branch's backward run first, its pooled gradient
  * pool_dy [N][pool_Ho][pool_Wo][C] is gathered in conv1's epilogue instead of being scattered by asm_avgpool_bwd into
- * a full-resolution tensor that conv1's input gradient is then added to.  1x1 / stride 1 only (ASM_ENOTSUP otherwise);
- * pooling geometry and the count_valid divisor rule as asm_avgpool_bwd. */
+ * a full-resolution tensor that conv1's input gradient is then added to.  1x1 / stride 1 only, and never a [N,1,1,C] layer
+ * (ASM_ENOTSUP otherwise); pooling geometry and the count_valid divisor rule as asm_avgpool_bwd. */
 int asm_conv2d_dgrad_pooled(const asm_conv_desc* d, const void* dy, const void* wt, const void* addend,
                             const uint8_t* addend_mask, const void* pool_dy, int pool_k, int pool_stride, int pool_pad,
                             int pool_Ho, int pool_Wo, int count_valid, void* dx, void* stream);
@@ -192,7 +198,8 @@ int asm_conv2d_dgrad_pooled(const asm_conv_desc* d, const void* dy, const void* 
  * asm_bn_apply, or NULL: no ReLU) and emits partial [asm_conv2d_dgrad_bnred_blocks(d)][2][C] = per 128 rows (sum dz, sum dz * y)
  * of the bf16-ROUNDED dx; asm_bn_bwd_finalize_raw (below) takes these partials (asm_bn_partials_compact applies).
  * Coverage is whatever asm_conv2d_dgrad_bnred_blocks(d) > 0 reports (ASM_ENOTSUP otherwise): the 1x1 stride-1 convolutions and
- * those 3x3 stride-1 ones whose input gradient runs on a kernel with the sums in its epilogue, with C % 8 == 0 -- which 3x3
+ * those 3x3 stride-1 ones whose input gradient runs on a kernel with the sums in its epilogue, with C % 8 == 0, the [N,1,1,C]
+ * layers excepted (0 blocks, whatever asm_tuning.dense_small is) -- which 3x3
  * layers that is depends on the asm_tuning fields igemm_mode, igemm_tile, igemm3 and igemm8; no float atomics: fixed summation
  * order. */
 int asm_conv2d_dgrad_bnred_blocks(const asm_conv_desc* d);
@@ -201,17 +208,19 @@ int asm_conv2d_dgrad_bnred(const asm_conv_desc* d, const void* dy, const void* w
                            void* dx, void* stream);
 
 /* Which kernel family an input gradient of d would run, from the plan and without launching: 0 the general igemm_kernel,
- * 1 igemm1, 2 igemm2, 3 igemm3, 4 conv_halo, 5 dgrad_s2_kernel (the one-launch 3x3 / stride-2 form), 8 igemm8 -- for the parity
+ * 1 igemm1, 2 igemm2, 3 igemm3, 4 conv_halo, 5 dgrad_s2_kernel (the one-launch 3x3 / stride-2 form), 6 dense_small_kernel (a
+ * [N,1,1,C] layer, plain or with an unmasked addend), 8 igemm8 -- for the parity
  * classes of a stride-2 layer the family of the last class, i.e. what asm_debug_last_conv_kernel reports after the call.  variant: ASM_DGRAD_MASKED (asm_conv2d_dgrad_masked),
  * ASM_DGRAD_POOLED (asm_conv2d_dgrad_pooled), ASM_DGRAD_BNRED (asm_conv2d_dgrad_bnred, optionally with MASKED), 0
- * (asm_conv2d_dgrad).  Operands are taken to be 16-byte aligned.  ASM_ENOTSUP: that entry point does not cover the layer. */
+ * (asm_conv2d_dgrad).  Operands are taken to be 16-byte aligned.  ASM_ENOTSUP: that entry point does not cover the layer
+ * (for POOLED and BNRED that includes every [N,1,1,C] layer). */
 #define ASM_DGRAD_MASKED 1
 #define ASM_DGRAD_POOLED 2
 #define ASM_DGRAD_BNRED 4
 int asm_conv2d_dgrad_kernel(const asm_conv_desc* d, int variant);
 
 /* dw[k][r][s][c] (float32) = sum_{n,ho,wo} dy(n,ho,wo,k) * x(n, ho*stride+r-pad, wo*stride+s-pad, c).
- * Split-K over output pixels; `workspace` holds the per-split slabs. */
+ * Split-K over output pixels; `workspace` holds the per-split slabs (0 bytes where one launch writes dw itself). */
 size_t asm_conv2d_wgrad_workspace_bytes(const asm_conv_desc* d);
 int asm_conv2d_wgrad(const asm_conv_desc* d, const void* x, const void* dy, float* dw,
                      void* workspace, size_t workspace_bytes, void* stream);

@@ -23,12 +23,14 @@ int asm_conv2d_wgrad_naive(const asm_conv_desc* d, const void* x, const void* dy
 int asm_debug_tr_probe(void* out256_i16, void* stream);
 
 /* The weight-gradient plan asm_conv2d_wgrad would use for d (with the current ASM_WGRAD_* knobs):
- * plan = {dy-tile rows (32/64/128/256), column-tile width (128/256), tiles_n, tiles_c, pixel splits, pixels per split}. */
+ * plan = {dy-tile rows (32/64/128/256), column-tile width (128/256), tiles_n, tiles_c, pixel splits, pixels per split}.
+ * Column-tile width -1: the resident-halo form, {K, -1, 1, 1, workgroups per K slice (= slabs), pixels per workgroup};
+ * -2: the [N,1,1,C] layer on dense_small_wgrad_kernel, {K, -2, ceil(K/32), ceil(C/32), 1, N}. */
 int asm_conv2d_wgrad_plan(const asm_conv_desc* d, int32_t plan[6]);
 
 /* Kernel family of the calling thread's last asm_conv2d_fprop* / asm_conv2d_dgrad* launch: 0 igemm_kernel (general fallback),
  * 1 igemm1_kernel (1x1 ring GEMM), 2 igemm2_kernel, 3 igemm3_kernel (rows resident across the taps), 4 conv_halo_kernel,
- * 5 dgrad_s2_kernel, 8 igemm8_kernel (wave-staggered multi-phase loop); -1 before the first call. */
+ * 5 dgrad_s2_kernel, 6 dense_small_kernel (a [N,1,1,C] layer), 8 igemm8_kernel (wave-staggered multi-phase loop); -1 before the first call. */
 int asm_debug_last_conv_kernel(void);
 
 /* asm_retrieval_topk_wide with the same arguments and result, which also ADDS to three device counters (uint64, zeroed by the

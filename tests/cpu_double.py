@@ -226,10 +226,17 @@ class CpuDouble(object):
     return self.asm_conv2d_dgrad(d, dy, wt, addend, dx, stream, addend_mask)
 
   @staticmethod
-  def _bnred_covers(d):
-    """the layers asm_conv2d_dgrad_bnred covers on the GPU side, as far as a host test can tell: every 1x1 stride-1 layer, and the
-    3x3 stride-1 pad-1 layers with K % 64 == 0 and more than 64 input channels (igemm3 / igemm8 territory)"""
-    if d.stride != 1 or d.C % 8:
+  def _dense_shaped(d):
+    """asm_dense_shaped (csrc/igemm_common.h): a [N,1,1,C] layer"""
+    return (d.H == 1 and d.W == 1 and d.Ho == 1 and d.Wo == 1 and d.R == 1 and d.S == 1 and d.C % 8 == 0
+            and d.x_img_pitch in (0, d.C) and d.x_row_pitch in (0, d.C) and d.x_pix_pitch in (0, d.C))
+
+  @classmethod
+  def _bnred_covers(cls, d):
+    """the layers asm_conv2d_dgrad_bnred covers on the GPU side, as far as a host test can tell: every 1x1 stride-1 layer but the
+    [N,1,1,C] ones, and the 3x3 stride-1 pad-1 layers with K % 64 == 0 and more than 64 input channels (igemm3 / igemm8
+    territory)"""
+    if d.stride != 1 or d.C % 8 or cls._dense_shaped(d):
       return False
     if d.R == 1 and d.S == 1 and d.pad == 0:
       return True
@@ -240,17 +247,21 @@ class CpuDouble(object):
     return d.K % 64 == 0 and d.C > 64
 
   def asm_conv2d_dgrad_kernel(self, d, variant):
-    """the family the GPU plan would give, as far as a host test needs it (the double reads the two tuning variables itself):
-    -2 (ASM_ENOTSUP) where the entry point refuses, 5 for the one-launch 3x3 / stride-2 form, else igemm2 (2) or, with
-    ASM_IGEMM_MODE=1, the general kernel (0)"""
+    """the family the GPU plan would give, as far as a host test needs it (the double reads the three tuning variables itself):
+    -2 (ASM_ENOTSUP) where the entry point refuses -- the fused forms refuse every [N,1,1,C] layer --, 6 for such a layer on
+    dense_small (ASM_DENSE_SMALL != 0, no masked addend, K % 16 == 0), 5 for the one-launch 3x3 / stride-2 form, else igemm2 (2)
+    or, with ASM_IGEMM_MODE=1, the general kernel (0)"""
     d = _desc(d)
     mode = os.environ.get('ASM_IGEMM_MODE') or '0'
     parity = os.environ.get('ASM_DGRAD_PARITY') or '2'
     k1 = d.R == 1 and d.S == 1 and d.pad == 0
+    dense = self._dense_shaped(d)
     if variant & 2:       # pooled: the 1x1 stride-1 igemm2 path
-      return 2 if k1 and d.stride == 1 and d.C % 8 == 0 and mode == '0' and not variant & 4 else -2
+      return 2 if k1 and d.stride == 1 and d.C % 8 == 0 and mode == '0' and not variant & 4 and not dense else -2
     if variant & 4:       # batch-norm sums
       return 2 if self._bnred_covers(d) else -2
+    if dense and not variant & 1 and d.K % 16 == 0 and (os.environ.get('ASM_DENSE_SMALL') or '1') != '0':
+      return 6
     if variant & 1 and k1 and d.stride == 2 and parity != '0' and mode == '0':
       return -2
     if (parity == '2' and mode == '0' and d.R == 3 and d.S == 3 and d.stride == 2 and d.pad == 1 and d.C == 64 and d.K == 64

@@ -40,6 +40,19 @@ def test_struct_layout_matches_header():
   assert ctypes.sizeof(ConvDesc) == 72
 
 
+def test_tuning_struct_has_one_environment_name_per_field():
+  """struct asm_tuning: 13 int32, every one reachable from exactly one ASM_* variable of the host"""
+  from assembled_cnn_amd.lib import TUNING_ENV, Tuning
+  fields = [n for n, _ in Tuning._fields_]
+  assert ctypes.sizeof(Tuning) == 13 * 4 and len(fields) == 13
+  assert fields[-1] == 'dense_small' and Tuning.dense_small.offset == 48
+  assert sorted(TUNING_ENV.values()) == sorted(fields)
+  hdr = open(os.path.join(ROOT, 'include', 'asm_hip.h')).read()
+  body = hdr[hdr.index('typedef struct asm_tuning {'):hdr.index('} asm_tuning;')]
+  assert re.findall(r'^  int32_t (\w+);', body, re.M) == fields, 'lib.Tuning and the header disagree'
+  assert '#define ASM_ABI_VERSION 11' in hdr
+
+
 def test_product_has_no_cpu_path():
   """ops must refuse CPU tensors when the real library is bound (no silent fallback)."""
   import torch

@@ -774,6 +774,35 @@ def test_dgrad_bnred_refuses_what_it_does_not_cover(hip_lib):
   assert ops.dgrad_bnred_ok(ops.make_conv_desc(2, 14, 14, 128, 256, 3, 3, 1))
 
 
+@pytest.mark.parametrize('knob', ['1', '0'])
+def test_fused_input_gradient_forms_never_take_a_dense_layer(hip_lib, knob, monkeypatch):
+  """asm_conv2d_dgrad_pooled / _bnred refuse every [N,1,1,C] layer, whatever asm_tuning.dense_small says"""
+  from assembled_cnn_amd import lib, ops
+  util.set_knob(monkeypatch, 'ASM_DENSE_SMALL', knob)
+  d = ops.make_conv_desc(33, 1, 1, 64, 128, 1, 1, 1)
+  assert ops.dgrad_kernel(d, lib.ASM_DGRAD_POOLED) < 0 and ops.dgrad_kernel(d, lib.ASM_DGRAD_BNRED) < 0
+  assert hip_lib.asm_conv2d_dgrad_bnred_blocks(C.byref(d)) == 0
+  assert not ops.dgrad_pool_ok(d) and not ops.dgrad_bnred_ok(d)
+  assert (ops.dgrad_kernel(d) == lib.CONV_DENSE) == (knob == '1')
+
+
+def test_weight_gradient_plan_of_a_dense_layer(hip_lib, monkeypatch):
+  """plan_wgrad's dense form ({K, -2, ceil(K/32), ceil(C/32), 1, N}, no workspace) up to 1024 rows with asm_tuning.dense_small
+  = 1; a wgrad_kernel plan (32-row dy tiles for K = 32, 128-wide column tiles) past that and with dense_small = 0.  Queries only."""
+  from assembled_cnn_amd import ops
+  plan = (C.c_int32 * 6)()
+
+  def query(n):
+    d = ops.make_conv_desc(n, 1, 1, 64, 32, 1, 1, 1)
+    assert hip_lib.asm_conv2d_wgrad_plan(C.byref(d), C.byref(plan)) == 0
+    return list(plan), hip_lib.asm_conv2d_wgrad_workspace_bytes(C.byref(d))
+
+  assert query(1024) == ([32, -2, 1, 2, 1, 1024], 0)
+  assert query(1025)[0][:4] == [32, 128, 1, 1]
+  util.set_knob(monkeypatch, 'ASM_DENSE_SMALL', '0')
+  assert query(1024)[0][:4] == [32, 128, 1, 1]
+
+
 @pytest.mark.parametrize('workload', ['assemble-r50', 'r50'])
 def test_dgrad_kernel_query_is_what_the_input_gradient_runs(hip_lib, workload):
   """asm_conv2d_dgrad_kernel answers from the plan, without launching: for every convolution of the workload (batch 2) and

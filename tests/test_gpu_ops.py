@@ -494,8 +494,10 @@ def test_dense_small_refuses_a_row_stride_it_cannot_zero(hip_lib):
 
 
 def test_dense_layers_route_through_dense_small_and_match_the_conv_kernels(hip_lib, monkeypatch):
-  """ops.conv_fprop / conv_dgrad of a [N,1,1,C] layer: the dense kernel == the implicit-GEMM convolution (A/B knob)"""
-  from assembled_cnn_amd import ops
+  """ops.conv_fprop / conv_dgrad of a [N,1,1,C] layer: the dense kernel == the implicit-GEMM convolution (A/B knob), and the
+  library's plan (asm_conv2d_dgrad_kernel) and its record of what ran (asm_debug_last_conv_kernel) name the dense family with
+  asm_tuning.dense_small = 1 and never with 0"""
+  from assembled_cnn_amd import lib, ops
   N_, Cn, K = 256, 128, 512
   x = _rand((N_, 1, 1, Cn), 1).cuda()
   w = _rand((K, 1, 1, Cn), 2, scale=Cn ** -0.5).cuda()
@@ -507,13 +509,134 @@ def test_dense_layers_route_through_dense_small_and_match_the_conv_kernels(hip_l
     util.set_knob(monkeypatch, 'ASM_DENSE_SMALL', knob)
     d = ops.make_conv_desc(N_, 1, 1, Cn, K, 1, 1, 1, out_f32=True)
     y, _ = ops.conv_fprop(d, x, w, False)
+    fams = [hip_lib.asm_debug_last_conv_kernel()]
     db = ops.make_conv_desc(N_, 1, 1, Cn, K, 1, 1, 1)
     yb, _ = ops.conv_fprop(db, x, w, False)
+    fams.append(hip_lib.asm_debug_last_conv_kernel())
     dx = ops.conv_dgrad(db, dy, wt)
+    fams += [hip_lib.asm_debug_last_conv_kernel(), ops.dgrad_kernel(db)]
+    assert all((f == lib.CONV_DENSE) == (knob == '1') for f in fams), (knob, fams)
     outs[knob] = (y.float().cpu(), yb.float().cpu(), dx.float().cpu())
   assert util.rel_l2(outs['1'][0], outs['0'][0]) <= 2e-6
   _close(outs['1'][1], outs['0'][1], name='dense fprop bf16')
   _close(outs['1'][2], outs['0'][2], name='dense dgrad')
+
+
+def _dense_operands(N_, Cn, K, seed=11):
+  """x [N,1,1,C], w [K,1,1,C], dy [N,1,1,K], wt [C,1,1,K] of a [N,1,1,C] layer (bf16, on the device)"""
+  from assembled_cnn_amd import ops
+  x = _rand((N_, 1, 1, Cn), seed).cuda()
+  w = _rand((K, 1, 1, Cn), seed + 1, scale=Cn ** -0.5).cuda()
+  dy = _rand((N_, 1, 1, K), seed + 2).cuda()
+  wt = torch.zeros((Cn, 1, 1, K), dtype=BF, device='cuda')
+  ops.filter_transpose(w, wt, K, 1, 1, Cn)
+  return x, w, dy, wt
+
+
+@pytest.mark.parametrize('N_,Cn,K', [(256, 128, 512),     # full tiles
+                                     (33, 48, 40),        # ragged rows and channel tile; a reduction of three 16-steps
+                                     (7, 16, 24)])        # a single 16-step
+def test_dense_layers_through_the_conv_entry_points_are_the_dense_small_launch_bit_for_bit(hip_lib, N_, Cn, K):
+  """asm_conv2d_fprop / _dgrad / _wgrad of a [N,1,1,C] layer plan onto dense_small.hip (plan_conv's FAM_DENSE, plan_wgrad's
+  dense form): the buffers they write, pad columns included, are those of a direct asm_dense_small[_wgrad] call with the
+  argument mapping of the plan -- the same launch, so torch.equal.  Cn is the reduction and K the output width throughout: the
+  input-gradient pair therefore runs the layer with the roles swapped (K input and Cn output channels of the forward layer),
+  which keeps the reduction a multiple of 16 as the kernel needs."""
+  from assembled_cnn_amd import lib, ops
+  from assembled_cnn_amd.ops import L, _ptr, _stream, check
+  x, w, dy, _ = _dense_operands(N_, Cn, K)
+  # forward, bf16
+  d = ops.make_conv_desc(N_, 1, 1, Cn, K, 1, 1, 1)
+  y, _ = ops.conv_fprop(d, x, w)
+  assert hip_lib.asm_debug_last_conv_kernel() == lib.CONV_DENSE
+  ref = torch.full((N_, 1, 1, K), 7.0, dtype=BF, device='cuda')
+  check(L().asm_dense_small(_ptr(x), Cn, _ptr(w), Cn, N_, K, Cn, _ptr(ref), K, 0, None, _stream()), 'dense_small')
+  assert torch.equal(y, ref)
+  # forward, f32 into padded rows (pad columns end inside the last 32-column tile)
+  ld = min(K + 8, -(-K // 32) * 32)
+  d = ops.make_conv_desc(N_, 1, 1, Cn, K, 1, 1, 1, ldy=ld, out_f32=True)
+  y, _ = ops.conv_fprop(d, x, w)
+  assert hip_lib.asm_debug_last_conv_kernel() == lib.CONV_DENSE
+  ref = torch.full((N_, 1, 1, ld), 7.0, dtype=torch.float32, device='cuda')
+  check(L().asm_dense_small(_ptr(x), Cn, _ptr(w), Cn, N_, K, Cn, _ptr(ref), ld, 1, None, _stream()), 'dense_small')
+  assert torch.equal(y, ref) and bool((y[..., K:] == 0).all())
+  # input gradient with and without an addend: dg [N][Cn] (the reduction), filter copy [K][Cn], result [N][K]
+  dd = ops.make_conv_desc(N_, 1, 1, K, Cn, 1, 1, 1)
+  dg = _rand((N_, 1, 1, Cn), 21).cuda()
+  wt = _rand((K, 1, 1, Cn), 22, scale=Cn ** -0.5).cuda()
+  for addend in (None, _rand((N_, 1, 1, K), 23).cuda()):
+    assert ops.dgrad_kernel(dd) == lib.CONV_DENSE
+    dx = ops.conv_dgrad(dd, dg, wt, addend)
+    assert hip_lib.asm_debug_last_conv_kernel() == lib.CONV_DENSE
+    ref = torch.full((N_, 1, 1, K), 7.0, dtype=BF, device='cuda')
+    check(L().asm_dense_small(_ptr(dg), Cn, _ptr(wt), Cn, N_, K, Cn, _ptr(ref), K, 0, _ptr(addend), _stream()), 'dense_small')
+    assert torch.equal(dx, ref)
+  # weight gradient
+  d = ops.make_conv_desc(N_, 1, 1, Cn, K, 1, 1, 1)
+  dw = torch.full((K, 1, 1, Cn), 3.0, device='cuda')
+  ops.conv_wgrad(d, x, dy, dw)
+  ref = torch.full((K, 1, 1, Cn), 5.0, device='cuda')
+  check(L().asm_dense_small_wgrad(_ptr(x), Cn, _ptr(dy), K, N_, Cn, K, _ptr(ref), Cn, _stream()), 'dense_small_wgrad')
+  assert torch.equal(dw, ref)
+
+
+def test_dense_layers_outside_dense_small_fall_back_to_the_conv_kernels(hip_lib):
+  """Each side condition of the dense plan (csrc/conv_igemm.hip: dense_covers) sends a [N,1,1,C] layer to the convolution
+  kernels, which still compute it: against the fp32 product, bf16 results to _close, f32 ones to 2e-6 relative L2."""
+  from assembled_cnn_amd import lib, ops
+  N_ = 33
+  last = hip_lib.asm_debug_last_conv_kernel
+
+  def product(a, b, n):      # [N][n] fp32 = a [N][r] . b [n][r]^T
+    return a.float().cpu().view(N_, -1) @ b.float().cpu().view(n, -1).t()
+
+  # a reduction that is no multiple of 16: forward C = 24 -> K = 40 ...
+  x, w, _, _ = _dense_operands(N_, 24, 40)
+  y, _ = ops.conv_fprop(ops.make_conv_desc(N_, 1, 1, 24, 40, 1, 1, 1), x, w)
+  assert last() != lib.CONV_DENSE
+  _close(y.view(N_, 40), product(x, w, 40), name='fprop, reduction 24')
+  # ... and the input gradient of the layer with the roles swapped (40 input channels, 24 output channels: reduction 24)
+  x, w, dy, wt = _dense_operands(N_, 40, 24)
+  dd = ops.make_conv_desc(N_, 1, 1, 40, 24, 1, 1, 1)
+  assert ops.dgrad_kernel(dd) not in (lib.CONV_DENSE, lib.ASM_ENOTSUP)
+  dx = ops.conv_dgrad(dd, dy, wt)
+  assert last() == ops.dgrad_kernel(dd)
+  _close(dx.view(N_, 40), product(dy, wt, 40), name='dgrad, reduction 24')
+
+  # fused statistics
+  x, w, dy, wt = _dense_operands(N_, 48, 40)
+  d = ops.make_conv_desc(N_, 1, 1, 48, 40, 1, 1, 1)
+  y, stats = ops.conv_fprop(d, x, w, want_stats=True)
+  assert last() != lib.CONV_DENSE and stats is not None
+  _close(y.view(N_, 40), product(x, w, 40), name='fprop with statistics')
+  assert torch.allclose(stats.sum(0)[0].cpu(), y.float().cpu().view(N_, 40).sum(0), rtol=1e-4, atol=1e-2)
+
+  # inference batch norm folded into the epilogue
+  scale = (torch.rand(40, generator=torch.Generator().manual_seed(5)) + 0.5).cuda()
+  shift = torch.randn(40, generator=torch.Generator().manual_seed(6)).cuda()
+  y = ops.conv_fprop_bn(d, x, w, scale, shift)
+  assert last() != lib.CONV_DENSE
+  _close(y.view(N_, 40), product(x, w, 40) * scale.cpu() + shift.cpu(), name='fprop_bn')
+
+  # a masked addend (40 input, 48 output channels: the reduction 48 alone would be dense_small's)
+  dd = ops.make_conv_desc(N_, 1, 1, 40, 48, 1, 1, 1)
+  x, w, dy, wt = _dense_operands(N_, 40, 48)
+  assert ops.dgrad_kernel(dd) == lib.CONV_DENSE
+  fam = ops.dgrad_kernel(dd, lib.ASM_DGRAD_MASKED)
+  assert fam >= 0 and fam != lib.CONV_DENSE
+  addend = _rand((N_, 1, 1, 40), 31).cuda()
+  mask = torch.randint(0, 256, (N_, 5), generator=torch.Generator().manual_seed(7), dtype=torch.uint8).cuda()
+  dx = ops.conv_dgrad(dd, dy, wt, addend, mask)
+  assert last() == fam
+  bits = ((mask.cpu().to(torch.int32)[:, :, None] >> torch.arange(8, dtype=torch.int32)) & 1).reshape(N_, 40).float()
+  _close(dx.view(N_, 40), product(dy, wt, 40) + addend.float().cpu().view(N_, 40) * bits, name='dgrad + masked addend')
+
+  # f32 rows wider than the last 32-column tile of K = 40 (asm_dense_small refuses such a stride: the plan does not pick it)
+  x, w, _, _ = _dense_operands(N_, 48, 40)
+  y, _ = ops.conv_fprop(ops.make_conv_desc(N_, 1, 1, 48, 40, 1, 1, 1, ldy=72, out_f32=True), x, w)
+  assert last() != lib.CONV_DENSE
+  r = util.rel_l2(y.view(N_, 72)[:, :40].cpu(), product(x, w, 40))
+  assert r <= 2e-6, r
 
 
 def test_sk_attention_path_fused_vs_unfused_whole_unit(hip_lib, monkeypatch):
