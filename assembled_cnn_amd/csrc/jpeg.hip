@@ -2,6 +2,8 @@
 //   jpeg_entropy_kernel  one 64-lane workgroup per image: Huffman tables -> LDS, coefficient region zeroed, then lane s
 //                        decodes restart intervals s, s + 64, ... (jpeg_entropy.h; an image without DRI is one interval,
 //                        so one lane works and the batch supplies the parallelism)
+//   jpeg_progressive_kernel  the entropy stage of progressive files (asm_jpeg_decode_progressive): the same workgroup
+//                        walks the image's scans in file order, tables rebuilt in LDS per scan, a barrier between scans
 //   jpeg_idct_kernel     one thread per 8x8 block: dequantise + jidctint.c's jpeg_idct_islow -> uint8 planes
 //   jpeg_colour_kernel   one thread per pixel: jdsample.c's fancy h2v1 / h2v2 upsampling + jdcolor.c's YCbCr -> RGB
 // Every index is checked against the image's own geometry and the sizes the caller passed; an image whose entropy decode
@@ -10,7 +12,7 @@
 #include "jpeg_entropy.h"
 
 static_assert(sizeof(asm_jpeg_desc) == 96 && sizeof(asm_jpeg_huff) == 272 && sizeof(asm_jpeg_tables) == 1600 &&
-                  sizeof(asm_jpeg_interval) == 32,
+                  sizeof(asm_jpeg_interval) == 32 && sizeof(asm_jpeg_scan) == 56,
               "JPEG ABI structs");
 
 namespace {
@@ -63,6 +65,69 @@ jpeg_entropy_kernel(const uint8_t* __restrict__ files, long long files_bytes, co
   __syncthreads();
   if (d.n_intervals != expect) return;
   const int err = jpeg_decode_lane(files, d, g, intervals, img, tab, zigzag, lane, 64, my_coefs);
+  if (err) atomicOr(&status[img], err);
+}
+
+// Progressive files: the scans of one image one after another.  One workgroup is one wave on one CU, so the barrier
+// between scans is all the ordering the coefficient traffic needs (a refinement scan reads what earlier scans stored).
+// Every loop bound around a barrier is uniform: the scan count and the table count come from rows all lanes read alike.
+// A lane that has seen an error stops decoding and keeps arriving at the barriers.
+__global__ void __launch_bounds__(64)
+jpeg_progressive_kernel(const uint8_t* __restrict__ files, long long files_bytes, const asm_jpeg_desc* __restrict__ descs,
+                        const asm_jpeg_scan* __restrict__ scans, int n_scans_total, const asm_jpeg_huff* __restrict__ huff,
+                        int n_huff, const asm_jpeg_interval* __restrict__ intervals, int n_intervals_total,
+                        long long total_blocks, long long dst_bytes, int16_t* __restrict__ coefs,
+                        int* __restrict__ status) {
+  __shared__ jpeg_dtab tab[3];       // DC-first scan: one per scan component; AC scan: [0]
+  __shared__ uint8_t zigzag[64];
+  __shared__ int failed;             // some lane has seen an error: the scans that follow are skipped
+  const int img = blockIdx.x, lane = threadIdx.x;
+  const asm_jpeg_desc d = descs[img];
+  jpeg_geom g;
+  const bool geom_ok = jpeg_make_geom(d, &g);
+  // first_interval / n_intervals name the image's rows of the scan table here
+  const int first_scan = d.first_interval, n_scans = d.n_intervals;
+  const bool ok = geom_ok && desc_fits(d, g, files_bytes, total_blocks, dst_bytes) && d.restart_interval == 0 &&
+                  (d.dcsel[0] | d.dcsel[1] | d.dcsel[2] | d.acsel[0] | d.acsel[1] | d.acsel[2]) == 0 && d.reserved == 0 &&
+                  first_scan >= 0 && n_scans >= 1 && n_scans <= 256 && first_scan <= n_scans_total - n_scans;
+  if (!ok) {       // uniform over the workgroup
+    if (lane == 0) status[img] = ASM_JPEG_EDESC;
+    return;
+  }
+  if (lane == 0) {
+    status[img] = 0;
+    failed = 0;
+  }
+  {
+    const uint8_t zz[64] = JPEG_ZIGZAG_INIT;
+    zigzag[lane] = zz[lane];
+  }
+  int16_t* my_coefs = coefs + d.coef_offset;
+  {
+    uint4* z = reinterpret_cast<uint4*>(my_coefs);
+    const long long n16 = g.n_coefs / 8;
+    for (long long i = lane; i < n16; i += 64) z[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  __syncthreads();
+  int err = 0;
+  for (int k = 0; k < n_scans; ++k) {
+    const asm_jpeg_scan sc = scans[first_scan + k];
+    const bool skip = failed != 0;       // written before the barrier that ended the previous scan: uniform
+    jpeg_scan_geom sg;
+    const int n_tab = jpeg_scan_tables(sc);
+    const int scan_err = skip ? 0 : jpeg_check_scan(d, g, sc, img, n_huff, n_intervals_total, &sg);
+    const bool run = !skip && scan_err == 0;      // uniform: every lane read the same rows
+    if (run && lane < n_tab) jpeg_dtab_prepare(huff[sc.huff[lane]], &tab[lane]);
+    __syncthreads();
+    if (run)
+      for (int t = 0; t < n_tab; ++t) jpeg_dtab_fill_look(&tab[t], lane, 64);
+    __syncthreads();
+    if (run && err == 0)
+      err = jpeg_prog_decode_lane(files, g, sc, sg, intervals, img, tab, zigzag, lane, 64, my_coefs);
+    err |= scan_err;
+    if (err) failed = 1;
+    __syncthreads();
+  }
   if (err) atomicOr(&status[img], err);
 }
 
@@ -245,6 +310,23 @@ extern "C" int asm_jpeg_decode_workspace_bytes(int64_t total_blocks, int64_t* by
   return ASM_OK;
 }
 
+// the inverse DCT and the colour launch for N rows whose coefficients are in place (both entry points end here)
+static int launch_pixel_stages(const asm_jpeg_desc* descs, const asm_jpeg_tables* tables, int N, int64_t files_bytes,
+                               int64_t total_blocks, int max_blocks, int max_pixels, uint8_t* dst, int64_t dst_bytes,
+                               const int32_t* status, const int16_t* coefs, uint8_t* planes, hipStream_t s) {
+  if (max_blocks > 0) {
+    ASM_LAUNCH(jpeg_idct_kernel, dim3((max_blocks + 63) / 64, N), dim3(64), 0, s, descs, tables, files_bytes,
+               total_blocks, dst_bytes, coefs, status, planes);
+    ASM_CHECK_LAUNCH("jpeg_decode (idct)");
+  }
+  if (max_pixels > 0) {
+    ASM_LAUNCH(jpeg_colour_kernel, dim3((max_pixels + 255) / 256, N), dim3(256), 0, s, descs, files_bytes, total_blocks,
+               dst_bytes, status, planes, dst);
+    ASM_CHECK_LAUNCH("jpeg_decode (colour)");
+  }
+  return ASM_OK;
+}
+
 extern "C" int asm_jpeg_decode(const uint8_t* files, int64_t files_bytes, const asm_jpeg_desc* descs,
                                const asm_jpeg_tables* tables, const asm_jpeg_interval* intervals, int N, int n_intervals,
                                int64_t total_blocks, int max_blocks, int max_pixels, uint8_t* dst, int64_t dst_bytes,
@@ -266,17 +348,38 @@ extern "C" int asm_jpeg_decode(const uint8_t* files, int64_t files_bytes, const 
                total_blocks, dst_bytes, coefs, status);
     ASM_CHECK_LAUNCH("jpeg_decode (entropy)");
   }
-  if (stages & 2) {
-    if (max_blocks > 0) {
-      ASM_LAUNCH(jpeg_idct_kernel, dim3((max_blocks + 63) / 64, N), dim3(64), 0, s, descs, tables, files_bytes,
-                 total_blocks, dst_bytes, coefs, status, planes);
-      ASM_CHECK_LAUNCH("jpeg_decode (idct)");
-    }
-    if (max_pixels > 0) {
-      ASM_LAUNCH(jpeg_colour_kernel, dim3((max_pixels + 255) / 256, N), dim3(256), 0, s, descs, files_bytes, total_blocks,
-                 dst_bytes, status, planes, dst);
-      ASM_CHECK_LAUNCH("jpeg_decode (colour)");
-    }
+  if (stages & 2)
+    return launch_pixel_stages(descs, tables, N, files_bytes, total_blocks, max_blocks, max_pixels, dst, dst_bytes, status,
+                               coefs, planes, s);
+  return ASM_OK;
+}
+
+extern "C" int asm_jpeg_decode_progressive(const uint8_t* files, int64_t files_bytes, const asm_jpeg_desc* descs,
+                                           const asm_jpeg_tables* tables, const asm_jpeg_scan* scans,
+                                           const asm_jpeg_huff* huff, const asm_jpeg_interval* intervals, int N, int n_scans,
+                                           int n_huff, int n_intervals, int64_t total_blocks, int max_blocks, int max_pixels,
+                                           uint8_t* dst, int64_t dst_bytes, int32_t* status, void* workspace,
+                                           int64_t workspace_bytes, int stages, void* stream) {
+  ASM_REQUIRE(N >= 0 && n_scans >= 0 && n_huff >= 0 && n_intervals >= 0 && files_bytes >= 0 && dst_bytes >= 0 &&
+                  total_blocks >= 0 && total_blocks < (1ll << 36) && max_blocks >= 0 && max_pixels >= 0,
+              "jpeg_decode_progressive: bad sizes");
+  ASM_REQUIRE(stages >= 1 && stages <= 3, "jpeg_decode_progressive: stages must be 1, 2 or 3");
+  ASM_REQUIRE(N <= 65535, "jpeg_decode_progressive: at most 65535 images per call");
+  ASM_REQUIRE(workspace_bytes >= total_blocks * 192, "jpeg_decode_progressive: workspace too small");
+  if (N == 0) return ASM_OK;
+  ASM_REQUIRE(files && descs && tables && scans && huff && intervals && dst && status && workspace,
+              "jpeg_decode_progressive: null pointer");
+  ASM_REQUIRE(((uintptr_t)workspace & 15) == 0, "jpeg_decode_progressive: workspace must be 16-byte aligned");
+  int16_t* coefs = (int16_t*)workspace;
+  uint8_t* planes = (uint8_t*)workspace + total_blocks * 128;
+  hipStream_t s = (hipStream_t)stream;
+  if (stages & 1) {
+    ASM_LAUNCH(jpeg_progressive_kernel, dim3(N), dim3(64), 0, s, files, files_bytes, descs, scans, n_scans, huff, n_huff,
+               intervals, n_intervals, total_blocks, dst_bytes, coefs, status);
+    ASM_CHECK_LAUNCH("jpeg_decode_progressive (entropy)");
   }
+  if (stages & 2)
+    return launch_pixel_stages(descs, tables, N, files_bytes, total_blocks, max_blocks, max_pixels, dst, dst_bytes, status,
+                               coefs, planes, s);
   return ASM_OK;
 }

@@ -1,6 +1,8 @@
 // Baseline JPEG entropy decode (ITU-T T.81 F.2.2) of one restart interval, as plain functions shared by the device
 // kernel (jpeg.hip) and a host program (tools/probes/jpeg_entropy_host.cpp, built with the address and undefined-behaviour
 // sanitizers): the same text is compiled for both, so what the host program proves about bounds holds for the kernel.
+// The second half of the file does the same for progressive files (T.81 annex G; jpeg_progressive_kernel and
+// tools/probes/jpeg_progressive_host.cpp).
 //
 // Rules: canonical codes of 1..16 bits; a 9-bit lookup, longer codes through maxcode / valoff; EXTEND;
 // one DC predictor per component, zero at the start of the interval; EOB and ZRL; FF 00 -> FF; pad bits ignored.
@@ -266,6 +268,275 @@ JPEG_HD int jpeg_decode_lane(const uint8_t* files, const asm_jpeg_desc& d, const
       continue;
     }
     err |= jpeg_decode_interval(files + iv.byte_begin, files + iv.byte_end, g, dc, ac, zigzag, first, count, coefs);
+  }
+  return err;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Progressive files (T.81 annex G, libjpeg's jdphuff.c): one scan carries a spectral band ss..se of some components at
+// successive-approximation position al.  The four kinds -- DC first, DC refinement, AC first, AC refinement -- below,
+// block by block; jpeg_prog_decode_interval walks one restart interval of one scan, jpeg_prog_decode_lane a lane's share
+// of a scan's intervals.  Same safety rules as above; the arithmetic is done in int and narrowed on store, negative
+// values are multiplied, never shifted.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// k raw bits (0..16), first bit first
+JPEG_HD int jpeg_receive_bits(jpeg_bits* b, int k, int* err) {
+  if (b->n < 32) jpeg_bits_fill(b);
+  b->n -= k;
+  if (b->n < b->pad) {
+    *err |= ASM_JPEG_EOVERRUN;
+    return 0;
+  }
+  return (int)((b->buf >> b->n) & ((1u << k) - 1u));
+}
+
+// a scan row as the decoder walks it: its MCU grid and what one MCU holds
+struct jpeg_scan_geom {
+  int ncomp;                 // components in the scan
+  int comp[3];               // their indices in the frame
+  int ch[3], cv[3];          // blocks per MCU of each, horizontally and vertically (1 x 1 for a scan of one component)
+  int mcus_x, n_mcus;        // MCUs per row, MCUs in the scan
+  int ss, se, ah, al;
+};
+
+// false: the scan row is not one this decoder handles (ASM_JPEG_EDESC)
+JPEG_HD bool jpeg_make_scan_geom(const asm_jpeg_desc& d, const jpeg_geom& g, const asm_jpeg_scan& sc, jpeg_scan_geom* s) {
+  if (sc.ncomp < 1 || sc.ncomp > g.ncomp) return false;
+  for (int i = 0; i < sc.ncomp; ++i) {
+    if (sc.comp[i] >= g.ncomp || (i > 0 && sc.comp[i] <= sc.comp[i - 1])) return false;
+  }
+  if (sc.ss == 0 ? sc.se != 0 : (sc.ncomp != 1 || sc.se < sc.ss || sc.se > 63)) return false;
+  if (sc.al > 13 || (sc.ah != 0 && sc.al != sc.ah - 1)) return false;
+  s->ncomp = sc.ncomp;
+  s->ss = sc.ss;
+  s->se = sc.se;
+  s->ah = sc.ah;
+  s->al = sc.al;
+  for (int i = 0; i < 3; ++i) {
+    const int c = i < sc.ncomp ? sc.comp[i] : 0;
+    s->comp[i] = c;
+    s->ch[i] = sc.ncomp > 1 ? g.ch[c] : 1;
+    s->cv[i] = sc.ncomp > 1 ? g.cv[c] : 1;
+  }
+  if (sc.ncomp > 1) {
+    s->mcus_x = g.mcus_x;
+    s->n_mcus = g.n_mcus;
+  } else {
+    // not interleaved: the component's true block grid, not the padded one
+    const int c = sc.comp[0];
+    const int hmax = g.ch[0], vmax = g.cv[0];
+    const int w = (d.width * g.ch[c] + hmax - 1) / hmax, h = (d.height * g.cv[c] + vmax - 1) / vmax;
+    s->mcus_x = (w + 7) / 8;
+    s->n_mcus = s->mcus_x * ((h + 7) / 8);
+  }
+  return true;
+}
+
+JPEG_HD int jpeg_scan_expected_intervals(const asm_jpeg_scan& sc, const jpeg_scan_geom& s) {
+  return sc.restart_interval > 0 ? (int)(((int64_t)s.n_mcus + sc.restart_interval - 1) / sc.restart_interval) : 1;
+}
+
+// Huffman tables the scan needs: one DC table per component for a DC-first scan, one AC table for an AC scan
+JPEG_HD int jpeg_scan_tables(const asm_jpeg_scan& sc) {
+  if (sc.ss > 0) return 1;
+  return sc.ah != 0 ? 0 : sc.ncomp < 1 ? 0 : sc.ncomp > 3 ? 3 : sc.ncomp;
+}
+
+// A scan row of image `img` against the image's descriptor and the table sizes of the call, before anything it points to
+// is read: 0 and *s filled, or ASM_JPEG_EDESC / ASM_JPEG_ERESTART.
+JPEG_HD int jpeg_check_scan(const asm_jpeg_desc& d, const jpeg_geom& g, const asm_jpeg_scan& sc, int img, int n_huff,
+                            int n_intervals_total, jpeg_scan_geom* s) {
+  if (sc.image != img || !jpeg_make_scan_geom(d, g, sc, s)) return ASM_JPEG_EDESC;
+  if (sc.restart_interval < 0 || sc.first_interval < 0 || sc.n_intervals < 1 ||
+      sc.first_interval > n_intervals_total - sc.n_intervals)
+    return ASM_JPEG_EDESC;
+  if (sc.byte_begin < d.scan_offset || sc.byte_end < sc.byte_begin || sc.byte_end > d.scan_offset + d.scan_bytes)
+    return ASM_JPEG_EDESC;
+  const int n_tab = jpeg_scan_tables(sc);
+  for (int i = 0; i < n_tab; ++i) {
+    if (sc.huff[i] < 0 || sc.huff[i] >= n_huff) return ASM_JPEG_EDESC;
+  }
+  return sc.n_intervals == jpeg_scan_expected_intervals(sc, *s) ? 0 : ASM_JPEG_ERESTART;
+}
+
+// DC first: pred += EXTEND; coef[0] = pred * 2^al
+JPEG_HD int jpeg_prog_dc_first(jpeg_bits* b, const jpeg_dtab* t, int al, int* pred, int16_t* out) {
+  int err = 0;
+  const int s = jpeg_decode_symbol(b, t, &err);
+  if (s < 0) return err;
+  if (s > 15) return ASM_JPEG_EBADCODE;
+  if (s) {
+    const int diff = jpeg_receive_extend(b, s, &err);
+    if (err) return err;
+    *pred = (int16_t)(*pred + diff);
+  }
+  out[0] = (int16_t)(*pred * (1 << al));
+  return 0;
+}
+
+// DC refinement: one raw bit per block
+JPEG_HD int jpeg_prog_dc_refine(jpeg_bits* b, int al, int16_t* out) {
+  int err = 0;
+  const int bit = jpeg_receive_bits(b, 1, &err);
+  if (err) return err;
+  if (bit) out[0] = (int16_t)(out[0] | (1 << al));
+  return 0;
+}
+
+// AC first: band ss..se of one block, with end-of-band runs over blocks
+JPEG_HD int jpeg_prog_ac_first(jpeg_bits* b, const jpeg_dtab* t, const uint8_t* zigzag, int ss, int se, int al, int* eobrun,
+                               int16_t* out) {
+  if (*eobrun > 0) {
+    --*eobrun;
+    return 0;
+  }
+  int err = 0;
+  for (int k = ss; k <= se;) {
+    const int rs = jpeg_decode_symbol(b, t, &err);
+    if (rs < 0) return err;
+    const int r = rs >> 4, s = rs & 15;
+    if (s != 0) {
+      k += r;
+      if (k > se) return ASM_JPEG_EBADCODE;
+      const int val = jpeg_receive_extend(b, s, &err);
+      if (err) return err;
+      out[zigzag[k]] = (int16_t)(val * (1 << al));
+      ++k;
+    } else if (r == 15) {
+      k += 16;
+    } else {
+      *eobrun = (1 << r) - 1;
+      if (r) *eobrun += jpeg_receive_bits(b, r, &err);
+      return err;
+    }
+  }
+  return 0;
+}
+
+// one correction bit for an already non-zero coefficient (T.81 G.1.2.3)
+JPEG_HD void jpeg_prog_correct(jpeg_bits* b, int p1, int16_t* cp, int* err) {
+  const int bit = jpeg_receive_bits(b, 1, err);
+  const int v = *cp;
+  if (bit && (v & p1) == 0) *cp = (int16_t)(v >= 0 ? v + p1 : v - p1);
+}
+
+// AC refinement: new coefficients of magnitude 2^al between correction bits for the ones already known
+JPEG_HD int jpeg_prog_ac_refine(jpeg_bits* b, const jpeg_dtab* t, const uint8_t* zigzag, int ss, int se, int al,
+                                int* eobrun, int16_t* out) {
+  const int p1 = 1 << al;
+  int err = 0;
+  int k = ss;
+  if (*eobrun == 0) {
+    while (k <= se) {
+      const int rs = jpeg_decode_symbol(b, t, &err);
+      if (rs < 0) return err;
+      int r = rs >> 4;
+      const int s = rs & 15;
+      int value = 0;
+      if (s != 0) {
+        if (s != 1) return ASM_JPEG_EBADCODE;
+        value = jpeg_receive_bits(b, 1, &err) ? p1 : -p1;
+        if (err) return err;
+      } else if (r != 15) {
+        *eobrun = 1 << r;
+        if (r) *eobrun += jpeg_receive_bits(b, r, &err);
+        if (err) return err;
+        break;
+      }
+      // past r still-zero coefficients, correcting the non-zero ones on the way
+      while (k <= se) {
+        int16_t* cp = out + zigzag[k];
+        if (*cp != 0) {
+          jpeg_prog_correct(b, p1, cp, &err);
+          if (err) return err;
+        } else if (--r < 0) {
+          break;
+        }
+        ++k;
+      }
+      if (value != 0) {
+        if (k > se) return ASM_JPEG_EBADCODE;
+        out[zigzag[k]] = (int16_t)value;
+      }
+      ++k;
+    }
+  }
+  if (*eobrun > 0) {
+    for (; k <= se; ++k) {
+      int16_t* cp = out + zigzag[k];
+      if (*cp != 0) {
+        jpeg_prog_correct(b, p1, cp, &err);
+        if (err) return err;
+      }
+    }
+    --*eobrun;
+  }
+  return 0;
+}
+
+// Decode MCUs [first_mcu, first_mcu + n_mcus) of one scan from the bytes [begin, end) into coefs (the image's own region
+// of g.n_coefs int16).  tab[i]: the table of scan component i (DC-first) or tab[0] (AC); unused for a DC refinement.
+JPEG_HD int jpeg_prog_decode_interval(const uint8_t* begin, const uint8_t* end, const jpeg_geom& g, const jpeg_scan_geom& s,
+                                      const jpeg_dtab* tab, const uint8_t* zigzag, int first_mcu, int n_mcus,
+                                      int16_t* coefs) {
+  if (first_mcu < 0 || n_mcus < 1 || first_mcu > s.n_mcus - n_mcus) return ASM_JPEG_EDESC;
+  jpeg_bits b;
+  jpeg_bits_init(&b, begin, end);
+  int pred[3] = {0, 0, 0};
+  int eobrun = 0;
+  int my = first_mcu / s.mcus_x, mx = first_mcu - my * s.mcus_x;
+  for (int m = 0; m < n_mcus; ++m) {
+    for (int i = 0; i < s.ncomp; ++i) {
+      const int c = s.comp[i];
+      for (int v = 0; v < s.cv[i]; ++v) {
+        for (int h = 0; h < s.ch[i]; ++h) {
+          const int bx = mx * s.ch[i] + h;
+          if (bx >= g.bw[c]) return ASM_JPEG_EDESC;
+          const int64_t blk = (int64_t)(my * s.cv[i] + v) * g.bw[c] + bx;
+          const int64_t at = g.base[c] + blk * 64;
+          const int64_t stop = c + 1 < g.ncomp ? g.base[c + 1] : g.n_coefs;
+          if (at < g.base[c] || at + 64 > stop) return ASM_JPEG_EDESC;
+          int16_t* out = coefs + at;
+          int err;
+          if (s.ss == 0)
+            err = s.ah == 0 ? jpeg_prog_dc_first(&b, &tab[i], s.al, &pred[i], out) : jpeg_prog_dc_refine(&b, s.al, out);
+          else
+            err = s.ah == 0 ? jpeg_prog_ac_first(&b, &tab[0], zigzag, s.ss, s.se, s.al, &eobrun, out)
+                            : jpeg_prog_ac_refine(&b, &tab[0], zigzag, s.ss, s.se, s.al, &eobrun, out);
+          if (err) return err;
+        }
+      }
+    }
+    if (++mx == s.mcus_x) {
+      mx = 0;
+      ++my;
+    }
+  }
+  return 0;
+}
+
+// What lane `lane` of `lanes` does for scan row `sc` of image `img`: its share (k = lane, lane + lanes, ...) of the scan's
+// rows of the interval table, each checked before a byte of it is read.  The caller has checked the scan row itself
+// (jpeg_make_scan_geom, byte range inside the image's, first_interval + n_intervals in range, interval count).
+JPEG_HD int jpeg_prog_decode_lane(const uint8_t* files, const jpeg_geom& g, const asm_jpeg_scan& sc, const jpeg_scan_geom& s,
+                                  const asm_jpeg_interval* intervals, int img, const jpeg_dtab* tab, const uint8_t* zigzag,
+                                  int lane, int lanes, int16_t* coefs) {
+  int err = 0;
+  for (int k = lane; k < sc.n_intervals && !err; k += lanes) {
+    const asm_jpeg_interval iv = intervals[sc.first_interval + k];
+    const int64_t first = sc.restart_interval > 0 ? (int64_t)k * sc.restart_interval : 0;
+    const int64_t left = s.n_mcus - first;
+    const int64_t count = sc.restart_interval > 0 ? (sc.restart_interval < left ? sc.restart_interval : left) : s.n_mcus;
+    const bool last = k == sc.n_intervals - 1;
+    if (iv.image != img || iv.byte_begin < sc.byte_begin || iv.byte_end < iv.byte_begin || iv.byte_end > sc.byte_end) {
+      err |= ASM_JPEG_EDESC;
+    } else if (iv.first_mcu != first || iv.n_mcus != count || iv.rst != (last ? -1 : (k & 7))) {
+      err |= ASM_JPEG_ERESTART;
+    } else {
+      err |= jpeg_prog_decode_interval(files + iv.byte_begin, files + iv.byte_end, g, s, tab, zigzag, (int)first, (int)count,
+                                       coefs);
+    }
   }
   return err;
 }

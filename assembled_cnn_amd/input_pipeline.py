@@ -176,7 +176,7 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
                      rng: Optional[np.random.Generator] = None, subtract_mean: bool = True,
                      windows: Optional[List[dict]] = None, autoaugment_type: Optional[str] = None,
                      augment: Optional[np.ndarray] = None, dct_method: str = '',
-                     jpeg_fallback=None) -> torch.Tensor:
+                     jpeg_fallback=None, jpeg_progressive: bool = False) -> torch.Tensor:
   """The imagenet* branches of data_util.preprocess_image for a batch of decoded images; float32 NHWC on `device`.
   `windows` overrides the sampled / computed windows (tests share them with the oracle).
   `autoaugment_type` ('imagenet' | 'good' | 'v0' | 'test'): in training mode the policy runs on the resized image, clipped
@@ -186,7 +186,8 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
   An entry of `images` that is bytes, a bytearray or a 1-D uint8 array is an encoded JPEG file: it is decoded on the device
   (`dct_method` '' or 'INTEGER_ACCURATE'; 'INTEGER_FAST' raises NotImplementedError), its size for the window arithmetic
   comes from its header, and a file of a kind the device does not decode goes through `jpeg_fallback(bytes) -> uint8
-  [H, W, 3]` (NotImplementedError without one).  A training crop is a window of the full decode."""
+  [H, W, 3]` (NotImplementedError without one).  A training crop is a window of the full decode.
+  `jpeg_progressive`: decode progressive files on the device as well (opt-in; they go to `jpeg_fallback` otherwise)."""
   if autoaugment_type is not None:
     _aa.check_policy_name(autoaugment_type)
   side, crop_type = output_size_and_crop_type(preprocessing_type, is_training, image_size)
@@ -194,7 +195,7 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
     _jpeg.check_dct_method(dct_method)
   # encoded files are decoded on the device into their slots of the packed buffer, decoded arrays (given, or returned by
   # the fallback) travel to theirs in one staged copy; one window and one descriptor per slot
-  pk = _jpeg.pack(images, jpeg_fallback)
+  pk = _jpeg.pack(images, jpeg_fallback, progressive=jpeg_progressive)
   if windows is None:
     if is_training:
       rng = rng if rng is not None else np.random.default_rng()

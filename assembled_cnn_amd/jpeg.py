@@ -2,7 +2,9 @@
 
 ``parse`` reads the marker segments of one file (ITU-T T.81 annex B): geometry, sampling, quantisation and Huffman tables,
 the byte range of the scan and of each restart interval, and whether the file is one the device path decodes.  ``pack``
-turns a batch of files into the tables ``asm_jpeg_decode`` reads, ``decode_batch`` runs it.  Everything a kernel could
+turns a batch of files into the tables ``asm_jpeg_decode`` reads, ``decode_batch`` runs it.  With ``progressive=True``
+(opt-in) a progressive file is read scan by scan and becomes a row of a second group of tables, the ones
+``asm_jpeg_decode_progressive`` reads.  Everything a kernel could
 trip over in a HEADER (truncated segments, table ids and sizes that disagree) is rejected here with ValueError; what can
 go wrong in the entropy-coded bytes is the kernel's to detect (per-image status, decode_packed raises ValueError).
 
@@ -23,12 +25,14 @@ ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 1
                    14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39,
                    46, 53, 60, 61, 54, 47, 55, 62, 63], dtype=np.int64)
 MAX_SIDE = 8192
+MAX_SCANS = 256         # of one progressive file: the device walks them one after another
 
 # the device tables, as numpy sees the structs of lib.py (include/asm_hip.h)
 DESC_DTYPE = np.dtype(lib.JpegDesc)
 HUFF_DTYPE = np.dtype(lib.JpegHuff)
 TABLES_DTYPE = np.dtype(lib.JpegTables)
 INTERVAL_DTYPE = np.dtype(lib.JpegInterval)
+SCAN_DTYPE = np.dtype(lib.JpegScan)
 
 
 def check_dct_method(dct_method: str):
@@ -55,11 +59,36 @@ def _as_array(data) -> np.ndarray:
   return np.frombuffer(bytes(data) if isinstance(data, memoryview) else data, dtype=np.uint8)
 
 
+class ScanInfo:
+  """One scan of a progressive file, as ``parse(..., progressive=True)`` found it."""
+  __slots__ = ('components', 'ss', 'se', 'ah', 'al', 'huffman', 'restart_interval', 'begin', 'end', 'intervals', 'rst')
+
+  def __init__(self):
+    self.components = []            # indices in frame order
+    self.ss = self.se = self.ah = self.al = 0
+    self.huffman = []               # per scan component: ((bits, vals) of its DC table, of its AC table) at this SOS, or None
+    self.restart_interval = 0       # DRI in force at this SOS, counting the scan's own MCUs
+    self.begin = self.end = 0       # entropy-coded bytes: data[begin:end]
+    self.intervals = np.zeros((0, 2), np.int64)
+    self.rst = np.zeros(0, np.int64)
+
+  def n_mcus(self, info) -> int:
+    """MCUs of the scan: the image's padded MCU grid for an interleaved scan, the component's TRUE block grid for a scan
+    of one component"""
+    if len(self.components) > 1:
+      return info.n_mcus
+    _, h, v, _ = info.components[self.components[0]]
+    if info.ncomp == 1:
+      h = v = 1
+    w, ht = -(-info.width * h // info.hs), -(-info.height * v // info.vs)
+    return -(-w // 8) * -(-ht // 8)
+
+
 class JpegInfo:
   """What ``parse`` found.  ``unsupported`` is None for a file the device decodes, else the reason it does not."""
   __slots__ = ('width', 'height', 'ncomp', 'precision', 'sof', 'components', 'scan_components', 'qtables', 'huffman',
                'restart_interval', 'hs', 'vs', 'mcus_x', 'mcus_y', 'scan_begin', 'scan_end', 'intervals', 'rst',
-               'unsupported')
+               'unsupported', 'scans')
 
   def __init__(self):
     self.width = self.height = self.ncomp = self.precision = 0
@@ -75,6 +104,12 @@ class JpegInfo:
     self.intervals = np.zeros((0, 2), np.int64)    # [begin, end) of every restart interval, markers excluded
     self.rst = np.zeros(0, np.int64)          # m of the RSTm after each interval but the last
     self.unsupported = None
+    self.scans = None               # [ScanInfo] in file order: a progressive file parsed with progressive=True
+
+  @property
+  def progressive(self) -> bool:
+    """a progressive file the device decodes (its row goes to asm_jpeg_decode_progressive)"""
+    return self.scans is not None and self.unsupported is None
 
   @property
   def n_mcus(self) -> int:
@@ -90,12 +125,40 @@ def _u16(a: np.ndarray, at: int) -> int:
   return (int(a[at]) << 8) | int(a[at + 1])
 
 
-def parse(data) -> JpegInfo:
+def _scan_extent(a: np.ndarray, at: int, marks):
+  """The entropy-coded bytes that start at a[at]: (end, intervals [k, 2], rst [k - 1], position of the marker that ends
+  them).  marks: the (FF positions followed by RSTm, by any other marker) of the whole file, found once.  The scan ends at
+  the first FF that is followed by neither 00 (a stuffed FF), FF (fill) nor RSTm."""
+  rst_ff, end_ff = marks
+  e = int(np.searchsorted(end_ff, at))
+  if e >= end_ff.size:
+    raise ValueError('JPEG ends without an EOI marker')
+  marker = end = int(end_ff[e])
+  while end > at and a[end - 1] == 0xFF:       # fill bytes in front of the marker
+    end -= 1
+  r = rst_ff[np.searchsorted(rst_ff, at):np.searchsorted(rst_ff, end)]
+  rst = a[r + 1].astype(np.int64) - 0xD0
+  begins = np.concatenate([[at], r + 2])
+  stops = np.concatenate([r, [end]])
+  return end, np.stack([begins, stops], axis=1).astype(np.int64), rst, marker
+
+
+def _markers(a: np.ndarray):
+  ff = np.flatnonzero(a[:-1] == 0xFF) if a.size > 1 else np.zeros(0, np.int64)
+  nxt = a[ff + 1]
+  is_rst = (nxt >= 0xD0) & (nxt <= 0xD7)
+  return ff[is_rst], ff[(nxt != 0) & (nxt != 0xFF) & ~is_rst]
+
+
+def parse(data, progressive: bool = False) -> JpegInfo:
   """Marker segments of one file.  Raises ValueError for a JPEG whose headers are malformed; a file of a kind the device
-  does not decode (and anything that is not JPEG at all) comes back with ``unsupported`` set."""
+  does not decode (and anything that is not JPEG at all) comes back with ``unsupported`` set.  progressive: read a
+  progressive (SOF2) file scan by scan into ``info.scans`` and classify it by the rules of DESIGN.md 1.2; without the
+  flag such a file is unsupported, and any other file is read the same either way."""
   a = _as_array(data)
   n = a.size
   info = JpegInfo()
+  marks = None
 
   def unsupported(why):
     if info.unsupported is None:
@@ -129,9 +192,11 @@ def parse(data) -> JpegInfo:
       raise ValueError('segment FF %02X is truncated' % m)
     seg = a[at + 2:at + seglen]
     at += seglen
-    if seen_sos:
+    if seen_sos and (info.scans is None or info.unsupported is not None):
       # anything but EOI after the first scan: more scans (or tables for them), DNL
       return unsupported('DNL marker' if m == 0xDC else 'several scans')
+    if seen_sos and m == 0xDB:
+      return unsupported('quantisation tables redefined between scans')
     if m == 0xDB:                         # DQT
       p = 0
       while p < seg.size:
@@ -187,7 +252,10 @@ def parse(data) -> JpegInfo:
       if len(set(c[0] for c in info.components)) != info.ncomp:
         raise ValueError('SOF: duplicate component id')
       if m == 0xC2:
-        unsupported('progressive (SOF2)')
+        if progressive:
+          info.scans = []
+        else:
+          unsupported('progressive (SOF2)')
       elif m not in (0xC0, 0xC1):
         unsupported('arithmetic coding' if m >= 0xC9 else 'lossless / hierarchical frame (SOF%d)' % (m - 0xC0))
       if info.precision != 8:
@@ -209,31 +277,30 @@ def parse(data) -> JpegInfo:
         raise ValueError('SOS: component count and segment size disagree')
       ns = int(seg[0])
       ids = [c[0] for c in info.components]
+      named = []
       for k in range(ns):
         cs, t = int(seg[1 + 2 * k]), int(seg[2 + 2 * k])
         if cs not in ids or (t >> 4) > 3 or (t & 15) > 3:
           raise ValueError('SOS: unknown component / bad table id')
-        info.scan_components.append((cs, t >> 4, t & 15))
+        named.append((cs, t >> 4, t & 15))
+      if marks is None:
+        marks = _markers(a)
+      end, intervals, rst, marker = _scan_extent(a, at, marks)
+      if not seen_sos:
+        info.scan_components = named
+        info.scan_begin, info.scan_end, info.intervals, info.rst = at, end, intervals, rst
       seen_sos = True
-      info.scan_begin = at
-      # the scan ends at the first FF that is followed by neither 00 (a stuffed FF), FF (fill) nor RSTm
-      body = a[at:]
-      ff = np.flatnonzero(body[:-1] == 0xFF) if body.size > 1 else np.zeros(0, np.int64)
-      nxt = body[ff + 1]
-      is_rst = (nxt >= 0xD0) & (nxt <= 0xD7)
-      ends = ff[(nxt != 0) & (nxt != 0xFF) & ~is_rst]
-      if ends.size == 0:
-        raise ValueError('JPEG ends without an EOI marker')
-      end = int(ends[0])
-      while end > 0 and body[end - 1] == 0xFF:       # fill bytes in front of the marker
-        end -= 1
-      info.scan_end = at + end
-      r = ff[is_rst & (ff < end)]
-      info.rst = (body[r + 1].astype(np.int64) - 0xD0)
-      begins = np.concatenate([[0], r + 2]) + at
-      stops = np.concatenate([r, [end]]) + at
-      info.intervals = np.stack([begins, stops], axis=1).astype(np.int64)
-      at = int(ends[0]) + at
+      if info.scans is not None and info.unsupported is None:
+        if len(info.scans) == MAX_SCANS:
+          return unsupported('more than %d scans' % MAX_SCANS)
+        sc = ScanInfo()
+        sc.components = [ids.index(cs) for cs, _, _ in named]
+        sc.ss, sc.se, sc.ah, sc.al = int(seg[-3]), int(seg[-2]), int(seg[-1]) >> 4, int(seg[-1]) & 15
+        sc.huffman = [(info.huffman.get((0, td)), info.huffman.get((1, ta))) for _, td, ta in named]
+        sc.restart_interval = info.restart_interval
+        sc.begin, sc.end, sc.intervals, sc.rst = at, end, intervals, rst
+        info.scans.append(sc)
+      at = marker
     # APPn, COM and the reserved markers carry nothing the decode needs
 
   if not seen_sos:
@@ -249,10 +316,11 @@ def parse(data) -> JpegInfo:
     return unsupported('4 components / CMYK')
   if info.ncomp not in (1, 3):
     return unsupported('%d components' % info.ncomp)
-  if len(info.scan_components) != info.ncomp:
-    return unsupported('several scans')
-  if [s[0] for s in info.scan_components] != [c[0] for c in info.components]:
-    return unsupported('scan components out of frame order')
+  if info.scans is None:
+    if len(info.scan_components) != info.ncomp:
+      return unsupported('several scans')
+    if [s[0] for s in info.scan_components] != [c[0] for c in info.components]:
+      return unsupported('scan components out of frame order')
   if info.ncomp == 3:
     if adobe_transform is not None and adobe_transform != 1:
       return unsupported('Adobe marker with transform %d' % adobe_transform)
@@ -265,14 +333,51 @@ def parse(data) -> JpegInfo:
   for (_, _, _, tq) in info.components:
     if tq not in info.qtables:
       raise ValueError('quantisation table %d is not defined' % tq)
+  info.mcus_x = -(-info.width // (8 * info.hs))
+  info.mcus_y = -(-info.height // (8 * info.vs))
+  if info.scans is not None:
+    why = _check_progression(info)
+    return unsupported(why) if why else info
   for (_, td, ta) in info.scan_components:
     if (0, td) not in info.huffman or (1, ta) not in info.huffman:
       raise ValueError('Huffman table %d/%d is not defined' % (td, ta))
   if len(set(s[1] for s in info.scan_components)) > 2 or len(set(s[2] for s in info.scan_components)) > 2:
     return unsupported('more than two DC or AC Huffman tables')
-  info.mcus_x = -(-info.width // (8 * info.hs))
-  info.mcus_y = -(-info.height // (8 * info.vs))
   return info
+
+
+def _check_progression(info: JpegInfo) -> Optional[str]:
+  """The scan script of a progressive file (T.81 G.1.1, libjpeg's jdphuff.c start_pass): None if the device decodes it,
+  else why not.  Where libjpeg warns and carries on, this refuses.  Raises ValueError for a Huffman table a scan needs
+  and the file never defined."""
+  coef_bits = np.full((info.ncomp, 64), -1, np.int64)
+  for k, sc in enumerate(info.scans):
+    nc = len(sc.components)
+    if sc.ss == 0:
+      if sc.se != 0:
+        return 'progressive scan %d mixes DC and AC coefficients (Ss 0, Se %d)' % (k, sc.se)
+      if any(b <= a for a, b in zip(sc.components, sc.components[1:])):
+        return 'progressive scan %d: components out of frame order' % k
+    else:
+      if nc != 1:
+        return 'progressive AC scan %d names %d components' % (k, nc)
+      if not sc.ss <= sc.se <= 63:
+        return 'progressive scan %d: bad spectral band %d..%d' % (k, sc.ss, sc.se)
+    if sc.al > 13 or (sc.ah != 0 and sc.al != sc.ah - 1):
+      return 'progressive scan %d: bad successive approximation Ah %d, Al %d' % (k, sc.ah, sc.al)
+    for c in sc.components:
+      if sc.ss > 0 and coef_bits[c, 0] < 0:
+        return 'progressive AC scan %d before the DC scan of its component' % k
+      band = coef_bits[c, sc.ss:sc.se + 1]
+      if np.any(np.where(band < 0, 0, band) != sc.ah):
+        return 'progressive scan %d: refinement out of sequence (Ah %d)' % (k, sc.ah)
+      band[:] = sc.al
+    for (dc, ac) in sc.huffman:
+      if (sc.ss == 0 and sc.ah == 0 and dc is None) or (sc.ss > 0 and ac is None):
+        raise ValueError('Huffman table of progressive scan %d is not defined' % k)
+  if np.any(coef_bits != 0):
+    return 'progressive file with incomplete scans'
+  return None
 
 
 class Packed:
@@ -291,6 +396,16 @@ class Packed:
     self.total_blocks = self.max_blocks = self.max_pixels = 0
     self.dev_index = []             # batch index of each device row
     self.fallback = {}              # batch index -> decoded uint8 [H, W, 3]
+    # the progressive rows (pack(..., progressive=True)), tables of their own for asm_jpeg_decode_progressive; the fields
+    # above describe the sequential rows alone
+    self.prog_index = []            # batch index of each progressive row
+    self.prog_files = np.zeros(16, np.uint8)
+    self.prog_descs = np.zeros(0, DESC_DTYPE)
+    self.prog_tables = np.zeros(0, TABLES_DTYPE)
+    self.prog_scans = np.zeros(0, SCAN_DTYPE)
+    self.prog_huff = np.zeros(0, HUFF_DTYPE)
+    self.prog_intervals = np.zeros(0, INTERVAL_DTYPE)
+    self.prog_total_blocks = self.prog_max_blocks = self.prog_max_pixels = 0
 
 
 def _check_decoded(arr, k) -> np.ndarray:
@@ -300,14 +415,90 @@ def _check_decoded(arr, k) -> np.ndarray:
   return arr
 
 
-def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[List[JpegInfo]] = None) -> Packed:
+def _interval_rows(image, intervals, rst, restart_interval, n_mcus, byte_shift) -> np.ndarray:
+  """asm_jpeg_interval rows of one scan: interval k holds MCUs [k * restart_interval, ...) of the scan's n_mcus"""
+  iv = np.zeros(len(intervals), INTERVAL_DTYPE)
+  idx = np.arange(len(iv), dtype=np.int64)
+  iv['image'] = image
+  iv['first_mcu'] = np.minimum(idx * restart_interval, 2 ** 31 - 1) if restart_interval else 0
+  iv['n_mcus'] = np.clip(n_mcus - idx * restart_interval, -2 ** 31, restart_interval) if restart_interval else n_mcus
+  iv['rst'] = np.concatenate([rst, [-1]])
+  iv['byte_begin'] = intervals[:, 0] + byte_shift
+  iv['byte_end'] = intervals[:, 1] + byte_shift
+  return iv
+
+
+def _pack_progressive(pk: Packed, infos, arrays):
+  """The progressive rows' tables: per image one descriptor (its first_interval / n_intervals name its rows of the scan
+  table), per scan one row, one pool entry per Huffman table a scan reads, and the scans' interval rows."""
+  nd = len(pk.prog_index)
+  pk.prog_descs = np.zeros(nd, DESC_DTYPE)
+  pk.prog_tables = np.zeros(nd, TABLES_DTYPE)
+  bytes_at, blocks_at, n_scans, n_iv = 0, 0, 0, 0
+  chunks, scan_rows, huffs, iv_rows = [], [], [], []
+  for row, k in enumerate(pk.prog_index):
+    info, a = infos[k], arrays[k]
+    first, last = info.scans[0].begin, info.scans[-1].end
+    body = a[first:last]        # every scan of the image, the marker segments between them included
+    chunks.append((bytes_at, body))
+    shift = bytes_at - first
+    d = pk.prog_descs[row]
+    d['scan_offset'], d['scan_bytes'] = bytes_at, body.size
+    d['coef_offset'] = d['plane_offset'] = blocks_at * 64
+    d['dst_offset'] = pk.offsets[k]
+    d['width'], d['height'], d['ncomp'] = info.width, info.height, info.ncomp
+    d['hs'], d['vs'], d['mcus_x'], d['mcus_y'] = info.hs, info.vs, info.mcus_x, info.mcus_y
+    d['first_interval'], d['n_intervals'] = n_scans, len(info.scans)
+    for c, (_, _, _, tq) in enumerate(info.components):
+      d['qsel'][c] = tq
+    for tq, q in info.qtables.items():
+      pk.prog_tables[row]['quant'][tq] = q
+    rows = np.zeros(len(info.scans), SCAN_DTYPE)
+    for j, sc in enumerate(info.scans):
+      r = rows[j]
+      r['image'], r['ncomp'] = row, len(sc.components)
+      r['comp'][:len(sc.components)] = sc.components
+      r['ss'], r['se'], r['ah'], r['al'] = sc.ss, sc.se, sc.ah, sc.al
+      r['huff'] = -1
+      for i, (dc, ac) in enumerate(sc.huffman):
+        table = ac if sc.ss > 0 else dc if sc.ah == 0 else None
+        if table is not None:
+          h = np.zeros((), HUFF_DTYPE)
+          h['bits'] = table[0]
+          h['vals'][:table[1].size] = table[1]
+          r['huff'][i] = len(huffs)
+          huffs.append(h)
+      r['restart_interval'] = sc.restart_interval
+      r['first_interval'], r['n_intervals'] = n_iv, len(sc.intervals)
+      r['byte_begin'], r['byte_end'] = sc.begin + shift, sc.end + shift
+      iv_rows.append(_interval_rows(row, sc.intervals, sc.rst, sc.restart_interval, sc.n_mcus(info), shift))
+      n_iv += len(sc.intervals)
+    scan_rows.append(rows)
+    n_scans += len(rows)
+    bytes_at += (body.size + 15) // 16 * 16
+    blocks_at += info.n_blocks
+    pk.prog_max_blocks = max(pk.prog_max_blocks, info.n_blocks)
+    pk.prog_max_pixels = max(pk.prog_max_pixels, info.width * info.height)
+  pk.prog_files = np.zeros(max(bytes_at, 16), np.uint8)
+  for o, body in chunks:
+    pk.prog_files[o:o + body.size] = body
+  pk.prog_scans = np.concatenate(scan_rows) if scan_rows else np.zeros(0, SCAN_DTYPE)
+  pk.prog_huff = np.array(huffs, HUFF_DTYPE) if huffs else np.zeros(0, HUFF_DTYPE)
+  pk.prog_intervals = np.concatenate(iv_rows) if iv_rows else np.zeros(0, INTERVAL_DTYPE)
+  pk.prog_total_blocks = blocks_at
+
+
+def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[List[JpegInfo]] = None,
+         progressive: bool = False) -> Packed:
   """Batch of entries -> the tables of asm_jpeg_decode (numpy, host).  An entry is an encoded file or an already decoded
   uint8 [H, W, 3] array (which only gets a slot in the output).  Files of an unsupported kind go through ``fallback(bytes)
-  -> uint8 [H, W, 3]``; without one the call raises NotImplementedError naming the reason and the index."""
+  -> uint8 [H, W, 3]``; without one the call raises NotImplementedError naming the reason and the index.
+  progressive: progressive files the device decodes become rows of a second group (the prog_* fields, the tables of
+  asm_jpeg_decode_progressive); `infos`, when given, must then have been parsed with the flag too."""
   pk = Packed()
   n = len(files)
   if infos is None:
-    infos = [parse(f) if is_encoded(f) else None for f in files]
+    infos = [parse(f, progressive) if is_encoded(f) else None for f in files]
   arrays = [None] * n
   for k, (f, info) in enumerate(zip(files, infos)):
     if info is None:
@@ -319,15 +510,16 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
       pk.fallback[k] = _check_decoded(fallback(bytes(f) if not isinstance(f, np.ndarray) else f.tobytes()), k)
     else:
       arrays[k] = _as_array(f)
-      pk.dev_index.append(k)
+      (pk.prog_index if info.progressive else pk.dev_index).append(k)
   nd = len(pk.dev_index)
   pk.descs = np.zeros(nd, DESC_DTYPE)
   pk.tables = np.zeros(nd, TABLES_DTYPE)
-  # output slots, 16-byte aligned (the src layout of asm_resize_crop_flip): the device-decoded entries first, then the
-  # already decoded ones back to back, so that those travel in one host-to-device copy
+  # output slots, 16-byte aligned (the src layout of asm_resize_crop_flip): the device-decoded entries first (sequential
+  # rows, then progressive rows), then the already decoded ones back to back, so that those travel in one host-to-device
+  # copy
   pk.sizes = [(infos[k].height, infos[k].width) if k not in pk.fallback else pk.fallback[k].shape[:2] for k in range(n)]
   hosted = sorted(pk.fallback)
-  pk.offsets, total = slot_layout([h * w * 3 for h, w in pk.sizes], pk.dev_index + hosted)
+  pk.offsets, total = slot_layout([h * w * 3 for h, w in pk.sizes], pk.dev_index + pk.prog_index + hosted)
   pk.host_begin = int(pk.offsets[hosted[0]]) if hosted else total
   pk.total_bytes = max(total, 16)
   scan_at, blocks_at, rows = 0, 0, []
@@ -360,15 +552,7 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
         bits, vals = info.huffman[(cls, th)]
         t[name][slot]['bits'] = bits
         t[name][slot]['vals'][:vals.size] = vals
-    iv = np.zeros(len(info.intervals), INTERVAL_DTYPE)
-    ri, total = info.restart_interval, info.n_mcus
-    idx = np.arange(len(iv), dtype=np.int64)
-    iv['image'] = row
-    iv['first_mcu'] = np.minimum(idx * ri, 2 ** 31 - 1) if ri else 0
-    iv['n_mcus'] = np.clip(total - idx * ri, -2 ** 31, ri) if ri else total
-    iv['rst'] = np.concatenate([info.rst, [-1]])
-    iv['byte_begin'] = info.intervals[:, 0] - info.scan_begin + scan_at
-    iv['byte_end'] = info.intervals[:, 1] - info.scan_begin + scan_at
+    iv = _interval_rows(row, info.intervals, info.rst, info.restart_interval, info.n_mcus, scan_at - info.scan_begin)
     rows.append(iv)
     scan_at += (scan.size + 15) // 16 * 16
     blocks_at += info.n_blocks
@@ -379,38 +563,59 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
     pk.files[o:o + scan.size] = scan
   pk.intervals = np.concatenate(rows) if rows else np.zeros(0, INTERVAL_DTYPE)
   pk.total_blocks = blocks_at
+  if pk.prog_index:
+    _pack_progressive(pk, infos, arrays)
   return pk
+
+
+def _raise_corrupt(status_rows):
+  """status_rows: (batch index, status word) of every device row, on the host"""
+  bad = sorted((k, st) for k, st in status_rows if st)
+  if bad:
+    raise ValueError('jpeg_decode: corrupt entropy-coded data in entries %s (status %s)' % (
+        [k for k, _ in bad], [st for _, st in bad]))
 
 
 def decode_packed(pk: Packed, device, stages: int = 3, check: bool = True, return_workspace: bool = False):
   """Run the device decode of a packed batch and copy the already decoded entries into their slots (one staged copy).
-  Returns (uint8 device buffer of pk.total_bytes, int32 status per device row), plus ops.jpeg_decode's workspace
-  (raw coefficients first) when return_workspace.  check: wait for the decode, return the status on the host and raise
-  ValueError naming the entries whose entropy-coded data is corrupt."""
+  Returns (uint8 device buffer of pk.total_bytes, int32 status per device row: the sequential rows, then the progressive
+  ones), plus ops.jpeg_decode's workspace (raw coefficients first) when return_workspace -- and, for a batch with
+  progressive rows, ops.jpeg_decode_progressive's as a fourth value.  check: wait for the decode, return the status on
+  the host and raise ValueError naming the entries whose entropy-coded data is corrupt.
+  The two groups are launched one after the other (three launches each) and write disjoint slots of the buffer."""
   dev = torch.device(device)
   dst = torch.empty(pk.total_bytes, dtype=torch.uint8, device=dev)
-  status = ws = None
+  status = ws = prog_status = prog_ws = None
   if pk.dev_index:
     status, ws = ops.jpeg_decode(*(upload_table(t, dev) for t in (pk.files, pk.descs, pk.tables, pk.intervals)),
                                  len(pk.dev_index), len(pk.intervals), pk.total_blocks, pk.max_blocks, pk.max_pixels, dst,
                                  stages=stages)
-    if check:
-      status = status.cpu()
-      bad = torch.nonzero(status).reshape(-1).tolist()
-      if bad:
-        raise ValueError('jpeg_decode: corrupt entropy-coded data in entries %s (status %s)' % (
-            [pk.dev_index[b] for b in bad], [int(status[b]) for b in bad]))
+  if pk.prog_index:
+    if return_workspace and ws is not None:
+      ws = ws.clone()       # both calls use the stream's one scratch buffer
+    tabs = (pk.prog_files, pk.prog_descs, pk.prog_tables, pk.prog_scans, pk.prog_huff, pk.prog_intervals)
+    prog_status, prog_ws = ops.jpeg_decode_progressive(
+        *(upload_table(t, dev) for t in tabs), len(pk.prog_index), len(pk.prog_scans), len(pk.prog_huff),
+        len(pk.prog_intervals), pk.prog_total_blocks, pk.prog_max_blocks, pk.prog_max_pixels, dst, stages=stages)
+    status = prog_status if status is None else torch.cat([status, prog_status])
+  if check and status is not None:
+    status = status.cpu()
+    _raise_corrupt(zip(pk.dev_index + pk.prog_index, status.tolist()))
   if pk.fallback:
     keys = sorted(pk.fallback)
     stage_into(dst[pk.host_begin:], [pk.fallback[k] for k in keys], [pk.offsets[k] - pk.host_begin for k in keys])
-  return (dst, status, ws) if return_workspace else (dst, status)
+  if not return_workspace:
+    return dst, status
+  return (dst, status, ws, prog_ws) if pk.prog_index else (dst, status, ws)
 
 
-def decode_batch(files: Sequence, device, fallback: Optional[Callable] = None, dct_method: str = ''):
+def decode_batch(files: Sequence, device, fallback: Optional[Callable] = None, dct_method: str = '',
+                 progressive: bool = False):
   """Encoded files -> (packed uint8 device buffer, byte offsets, [(height, width)]): image k is
   buffer[offsets[k] : offsets[k] + 3 * h * w] viewed as [h, w, 3].  Raises ValueError naming the files whose
-  entropy-coded data is corrupt, NotImplementedError for an unsupported kind without ``fallback``."""
+  entropy-coded data is corrupt, NotImplementedError for an unsupported kind without ``fallback``.
+  progressive: decode progressive files on the device too (they need no fallback then)."""
   check_dct_method(dct_method)
-  pk = pack(files, fallback)
+  pk = pack(files, fallback, progressive=progressive)
   dst = decode_packed(pk, device)[0]
   return dst, pk.offsets, pk.sizes

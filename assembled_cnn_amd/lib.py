@@ -66,7 +66,15 @@ class JpegInterval(C.Structure):
               ('byte_begin', C.c_int64), ('byte_end', C.c_int64)]
 
 
+class JpegScan(C.Structure):
+  """struct asm_jpeg_scan"""
+  _fields_ = [('image', C.c_int32), ('ncomp', C.c_int32), ('comp', C.c_uint8 * 4), ('ss', C.c_uint8), ('se', C.c_uint8),
+              ('ah', C.c_uint8), ('al', C.c_uint8), ('huff', C.c_int32 * 3), ('restart_interval', C.c_int32),
+              ('first_interval', C.c_int32), ('n_intervals', C.c_int32), ('byte_begin', C.c_int64), ('byte_end', C.c_int64)]
+
+
 assert (C.sizeof(JpegDesc), C.sizeof(JpegHuff), C.sizeof(JpegTables), C.sizeof(JpegInterval)) == (96, 272, 1600, 32)
+assert C.sizeof(JpegScan) == 56
 JPEG_EBADCODE, JPEG_EOVERRUN, JPEG_ERESTART, JPEG_EDESC = 1, 2, 4, 8      # asm_jpeg_decode's status bits
 
 
@@ -256,6 +264,8 @@ SIGNATURES = {
     'asm_autoaugment': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, C.c_int64, _P]),
     'asm_jpeg_decode_workspace_bytes': (_I, [C.c_int64, C.POINTER(C.c_int64)]),
     'asm_jpeg_decode': (_I, [_P, C.c_int64, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _P, C.c_int64, _P, _P, C.c_int64, _I, _P]),
+    'asm_jpeg_decode_progressive': (_I, [_P, C.c_int64, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, _I, _I, _P, C.c_int64, _P,
+                                         _P, C.c_int64, _I, _P]),
     'asm_model_plan': (_I, [C.POINTER(ModelCfg), _I, _I, _I, C.POINTER(PlanEntry), _I, C.POINTER(PlanSummary)]),
 }
 

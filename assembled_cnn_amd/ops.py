@@ -981,6 +981,28 @@ def jpeg_decode(files_u8, descs_dev, tables_dev, intervals_dev, n, n_intervals, 
   return status, ws
 
 
+def jpeg_decode_progressive(files_u8, descs_dev, tables_dev, scans_dev, huff_dev, intervals_dev, n, n_scans, n_huff,
+                            n_intervals, total_blocks, max_blocks, max_pixels, dst, stages=3):
+  """asm_jpeg_decode_progressive for the progressive rows packed by jpeg.pack(progressive=True): as jpeg_decode, with
+  n_scans struct asm_jpeg_scan and a pool of n_huff struct asm_jpeg_huff beside the descriptors.  Same return values."""
+  if (descs_dev.numel() != C.sizeof(_lib.JpegDesc) * n or tables_dev.numel() != C.sizeof(_lib.JpegTables) * n or
+      scans_dev.numel() != C.sizeof(_lib.JpegScan) * n_scans or huff_dev.numel() != C.sizeof(_lib.JpegHuff) * n_huff or
+      intervals_dev.numel() != C.sizeof(_lib.JpegInterval) * n_intervals):
+    raise ValueError('jpeg_decode_progressive: table sizes do not match n = %d, n_scans = %d, n_huff = %d, n_intervals = %d'
+                     % (n, n_scans, n_huff, n_intervals))
+  status = torch.empty((max(n, 1),), dtype=torch.int32, device=dst.device)[:n]
+  if n == 0:
+    return status, None
+  need = C.c_int64(0)
+  check(L().asm_jpeg_decode_workspace_bytes(total_blocks, C.byref(need)), 'jpeg_decode_workspace_bytes')
+  ws = _workspace(max(need.value, 16), dst)
+  check(L().asm_jpeg_decode_progressive(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev), _ptr(scans_dev),
+                                        _ptr(huff_dev), _ptr(intervals_dev), n, n_scans, n_huff, n_intervals, total_blocks,
+                                        max_blocks, max_pixels, _ptr(dst), dst.numel(), _ptr(status), _ptr(ws), ws.numel(),
+                                        stages, _stream()), 'jpeg_decode_progressive')
+  return status, ws
+
+
 # ---------------------------------------------------------------------------------------------------
 # retrieval evaluation (metric/recall_metric.py)
 # ---------------------------------------------------------------------------------------------------

@@ -35,6 +35,8 @@ extern "C" {
 #define ASM_ENOTSUP (-2)
 #define ASM_EHIP (-3)
 
+/* Changes when an existing struct or signature changes.  Additions keep it: asm_jpeg_decode_progressive and
+ * asm_jpeg_scan came in under 11. */
 #define ASM_ABI_VERSION 11
 
 const char* asm_last_error(void);
@@ -677,6 +679,42 @@ int asm_jpeg_decode(const uint8_t* files, int64_t files_bytes, const asm_jpeg_de
                     const asm_jpeg_interval* intervals, int N, int n_intervals, int64_t total_blocks, int max_blocks,
                     int max_pixels, uint8_t* dst, int64_t dst_bytes, int32_t* status, void* workspace,
                     int64_t workspace_bytes, int stages, void* stream);
+
+/* Progressive files (SOF2; T.81 annex G, libjpeg's jdphuff.c): a second entropy stage in front of the same pixel stages.
+ * One 64-lane workgroup per image zeroes the image's coefficients and walks its scans IN FILE ORDER (a refinement scan
+ * reads what earlier scans wrote); per scan it builds that scan's Huffman tables in LDS and lane s decodes the scan's
+ * restart intervals s, s + 64, ...  Then asm_jpeg_decode's inverse DCT and colour launches run for these rows.  Same
+ * `stages`, same `status` contract, same workspace (asm_jpeg_decode_workspace_bytes) as asm_jpeg_decode.
+ *   files      every image's bytes from its first scan's entropy-coded data to the end of its last scan's
+ *   descs      N asm_jpeg_desc: geometry, offsets and qsel as for asm_jpeg_decode; scan_offset / scan_bytes cover all
+ *              scans of the image; first_interval / n_intervals name rows of the SCAN table here (the image's scans in
+ *              file order, 1..256 of them); restart_interval, dcsel, acsel and reserved are not used and must be zero
+ *   tables     N asm_jpeg_tables; only quant is read
+ *   scans      n_scans rows; huff: n_huff tables the scan rows point into; intervals: n_intervals rows, those of a scan
+ *              at [first_interval, first_interval + n_intervals) in restart order, `image` the row of descs, first_mcu /
+ *              n_mcus counting the SCAN's own MCUs, rst restarting at 0 in every scan
+ * A scan of several components walks the image's padded MCU grid as the sequential decoder does; a scan of ONE component
+ * is not interleaved: its MCU is one block and it walks that component's TRUE block grid, ceil(ceil(width * h / hmax) /
+ * 8) by ceil(ceil(height * v / vmax) / 8), in raster order (storage keeps the padded row pitch; padded blocks no scan
+ * visits stay zero).  Every index of every row is checked on the device against the sizes passed here: a violation is
+ * ASM_JPEG_EDESC, an interval count other than ceil(scan MCUs / restart_interval) (1 without DRI) ASM_JPEG_ERESTART.
+ * The host (jpeg.parse) has checked that the scans' progression is legal and complete; the device does not depend on it. */
+typedef struct asm_jpeg_scan {
+  int32_t image;                           /* row of descs                                                         */
+  int32_t ncomp;                           /* components in the scan: 1..3 for a DC scan, 1 for an AC scan         */
+  uint8_t comp[4];                         /* their indices in the frame, increasing; unused entries 0             */
+  uint8_t ss, se, ah, al;                  /* spectral band ss..se (0..0: DC), successive approximation high / low */
+  int32_t huff[3];                         /* per scan component: row of huff (DC-first scan: its DC table; AC     */
+                                           /* scan: [0] its AC table); -1 where the scan needs none                */
+  int32_t restart_interval;                /* the scan's MCUs per interval (DRI at its SOS); 0 = one interval      */
+  int32_t first_interval, n_intervals;     /* rows of the interval table                                           */
+  int64_t byte_begin, byte_end;            /* the scan's entropy-coded bytes in files, inside the image's range    */
+} asm_jpeg_scan;                           /* 56 bytes */
+int asm_jpeg_decode_progressive(const uint8_t* files, int64_t files_bytes, const asm_jpeg_desc* descs,
+                                const asm_jpeg_tables* tables, const asm_jpeg_scan* scans, const asm_jpeg_huff* huff,
+                                const asm_jpeg_interval* intervals, int N, int n_scans, int n_huff, int n_intervals,
+                                int64_t total_blocks, int max_blocks, int max_pixels, uint8_t* dst, int64_t dst_bytes,
+                                int32_t* status, void* workspace, int64_t workspace_bytes, int stages, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Flag surface and topology planner.  asm_model_cfg carries the flags of nets/hparams_config.py:30-292 (+

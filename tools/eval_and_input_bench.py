@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput of the rows either side of the training step: the GPU input-pipeline tail (resize/crop/flip/mean-sub
 kernel), the device JPEG decoder in front of it, and evaluation-mode inference with the on-device metrics (BASELINE
-configs 1 and 3-eval).  `--only jpeg` runs the JPEG leg alone."""
+configs 1 and 3-eval).  `--only jpeg` runs the JPEG leg alone, `--only jpeg_progressive` the progressive-file leg."""
 import os, sys, time
 import numpy as np
 import torch
@@ -83,8 +83,83 @@ def jpeg_leg(n=256):
   print('decoded arrays today: pack_batch + H2D %.2f ms per batch of %d (%.1f MB)' % (best, n, sum(a.size for a in arrays) / 1e6))
 
 
-if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] == 'jpeg':
-  jpeg_leg()
+def jpeg_progressive_leg(n=256):
+  """The images of jpeg_leg saved twice, progressive and baseline.  Progressive files on the device (opt-in): the entropy
+  stage (the file's scans one after another, one lane per file without restart markers), the pixel stages, the whole
+  decode_batch(progressive=True).  Beside it, in the same run: what happens to those files without the flag (Pillow on 16
+  threads as the fallback, then pack_batch + H2D of the decoded arrays) and the sequential device decode of the same
+  images."""
+  import concurrent.futures, io
+  from PIL import Image
+  from assembled_cnn_amd import jpeg
+  rng = np.random.default_rng(1)
+  prog, base = [], []
+  for _ in range(n):
+    w, h = int(rng.integers(440, 561)), int(rng.integers(330, 421))
+    low = Image.fromarray(rng.integers(0, 256, size=(h // 24 + 2, w // 24 + 2, 3), dtype=np.uint8)).resize((w, h), Image.BICUBIC)
+    arr = np.clip(np.asarray(low).astype(np.float32) + rng.normal(0, 9, size=(h, w, 3)), 0, 255).astype(np.uint8)
+    for files, kw in ((prog, dict(progressive=True)), (base, {})):
+      b = io.BytesIO()
+      Image.fromarray(arr).save(b, 'JPEG', quality=90, subsampling=2, **kw)
+      files.append(b.getvalue())
+  scans = [len(jpeg.parse(f, progressive=True).scans) for f in prog]
+  print('jpeg progressive: %d files, the images of the jpeg leg; mean %.1f KB progressive (%d..%d scans), %.1f KB baseline'
+        % (n, sum(map(len, prog)) / n / 1e3, min(scans), max(scans), sum(map(len, base)) / n / 1e3))
+  pk = jpeg.pack(prog, progressive=True)
+  assert len(pk.prog_index) == n
+  up = [staging.upload_table(t, 'cuda') for t in (pk.prog_files, pk.prog_descs, pk.prog_tables, pk.prog_scans, pk.prog_huff,
+                                                  pk.prog_intervals)]
+  dst = torch.empty(pk.total_bytes, dtype=torch.uint8, device='cuda')
+  run = lambda stages: ops.jpeg_decode_progressive(*up, n, len(pk.prog_scans), len(pk.prog_huff), len(pk.prog_intervals),
+                                                   pk.prog_total_blocks, pk.prog_max_blocks, pk.prog_max_pixels, dst,
+                                                   stages=stages)
+  assert not run(3)[0].any()
+  ms_e, ms_p = ev(lambda: run(1), iters=3), ev(lambda: run(2), iters=10)
+  got = dst.cpu().numpy()
+
+  def whole(files, **kw):
+    runs = []
+    for _ in range(3):
+      t0 = time.time(); jpeg.decode_batch(files, 'cuda', **kw); torch.cuda.synchronize(); runs.append(1e3 * (time.time() - t0))
+    return runs
+
+  w_prog = whole(prog, progressive=True)
+  t0 = time.time(); jpeg.pack(prog, progressive=True); ms_host = 1e3 * (time.time() - t0)
+  print('progressive entropy stage : %8.2f ms per batch of %d (%6.0f img/s); 3 timed launches' % (ms_e, n, n / ms_e * 1e3))
+  print('progressive pixel stages  : %8.2f ms per batch of %d (%6.0f img/s); 10 timed launches' % (ms_p, n, n / ms_p * 1e3))
+  print('progressive decode_batch  : %8.2f ms per batch of %d (%6.0f img/s), host parse + pack %.1f ms of it; runs %s'
+        % (min(w_prog), n, n / min(w_prog) * 1e3, ms_host, ' '.join('%.1f' % w for w in w_prog)))
+  # without the flag: the fallback decodes on the host, the arrays travel
+  dec = lambda f: np.asarray(Image.open(io.BytesIO(f)).convert('RGB'))
+  with concurrent.futures.ThreadPoolExecutor(16) as ex:
+    list(ex.map(dec, prog[:32]))
+    pil = []
+    for _ in range(3):
+      t0 = time.time(); arrays = list(ex.map(dec, prog)); pil.append(1e3 * (time.time() - t0))
+  assert all(np.array_equal(got[int(o):int(o) + a.size].reshape(a.shape), a) for o, a in zip(pk.offsets, arrays)), 'device != Pillow'
+  print('jpeg progressive: the device output equals Pillow\'s on all %d files' % n)
+  wins = [P.eval_window(a.shape[0], a.shape[1], 224, 224) for a in arrays]
+  h2d = []
+  for _ in range(3):
+    t0 = time.time(); buf, table = P.pack_batch(arrays, wins, 224, 224, pin=True); buf.cuda(); table.cuda(); torch.cuda.synchronize()
+    h2d.append(1e3 * (time.time() - t0))
+  print('without the flag          : Pillow, 16 threads %8.2f ms (%6.0f img/s; runs %s) + pack_batch + H2D %.2f ms = %.2f ms per batch of %d'
+        % (min(pil), n / min(pil) * 1e3, ' '.join('%.1f' % w for w in pil), min(h2d), min(pil) + min(h2d), n))
+  # the same images as baseline files on the device
+  pb = jpeg.pack(base)
+  ub = [staging.upload_table(t, 'cuda') for t in (pb.files, pb.descs, pb.tables, pb.intervals)]
+  runb = lambda stages: ops.jpeg_decode(*ub, n, len(pb.intervals), pb.total_blocks, pb.max_blocks, pb.max_pixels, dst, stages=stages)
+  assert not runb(3)[0].any()
+  ms_be, ms_bp = ev(lambda: runb(1), iters=3), ev(lambda: runb(2), iters=10)
+  w_base = whole(base)
+  print('sequential, same images   : entropy %.2f ms, pixel stages %.2f ms, decode_batch %.2f ms per batch of %d (runs %s)'
+        % (ms_be, ms_bp, min(w_base), n, ' '.join('%.1f' % w for w in w_base)))
+  print('progressive / sequential entropy stage: %.2f x; entropy share of the progressive device time: %.1f %%'
+        % (ms_e / ms_be, 100 * ms_e / (ms_e + ms_p)))
+
+
+if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] in ('jpeg', 'jpeg_progressive'):
+  jpeg_progressive_leg() if sys.argv[sys.argv.index('--only') + 1] == 'jpeg_progressive' else jpeg_leg()
   sys.exit(0)
 
 rng = np.random.default_rng(0)
