@@ -2,6 +2,9 @@
 //   jpeg_entropy_kernel  one 64-lane workgroup per image: Huffman tables -> LDS, coefficient region zeroed, then lane s
 //                        decodes restart intervals s, s + 64, ... (jpeg_entropy.h; an image without DRI is one interval,
 //                        so one lane works and the batch supplies the parallelism)
+//   jpeg_entropy_parallel_kernel  the same stage for asm_jpeg_decode_parallel: one 256-lane workgroup per image decodes
+//                        every interval in segments, all lanes at once, to the same coefficients and status
+//                        (jpeg_parallel.h)
 //   jpeg_progressive_kernel  the entropy stage of progressive files (asm_jpeg_decode_progressive): the same workgroup
 //                        walks the image's scans in file order, tables rebuilt in LDS per scan, a barrier between scans
 //   jpeg_idct_kernel     one thread per 8x8 block: dequantise + jidctint.c's jpeg_idct_islow -> uint8 planes
@@ -12,7 +15,7 @@
 #include "jpeg_entropy.h"
 
 static_assert(sizeof(asm_jpeg_desc) == 96 && sizeof(asm_jpeg_huff) == 272 && sizeof(asm_jpeg_tables) == 1600 &&
-                  sizeof(asm_jpeg_interval) == 32 && sizeof(asm_jpeg_scan) == 56,
+                  sizeof(asm_jpeg_interval) == 32 && sizeof(asm_jpeg_scan) == 56 && sizeof(jpeg_seg) == 32,
               "JPEG ABI structs");
 
 namespace {
@@ -66,6 +69,93 @@ jpeg_entropy_kernel(const uint8_t* __restrict__ files, long long files_bytes, co
   if (d.n_intervals != expect) return;
   const int err = jpeg_decode_lane(files, d, g, intervals, img, tab, zigzag, lane, 64, my_coefs);
   if (err) atomicOr(&status[img], err);
+}
+
+// One scan on many lanes (jpeg_parallel.h): one 256-lane workgroup per image, the image's segments shared out lane,
+// lane + 256, ...  Every branch around a barrier is uniform: it depends on the descriptor, on the segment count read
+// alike by all lanes, or on a __syncthreads_or.  The state rows live in global memory (an 8192 x 8192 image has more
+// segments than LDS holds); the barriers order the workgroup's own traffic to them.
+#define JPEG_PAR_LANES 256
+__global__ void __launch_bounds__(JPEG_PAR_LANES)
+jpeg_entropy_parallel_kernel(const uint8_t* __restrict__ files, long long files_bytes, const asm_jpeg_desc* __restrict__ descs,
+                             const asm_jpeg_tables* __restrict__ tables, const asm_jpeg_interval* __restrict__ intervals,
+                             int n_intervals_total, const int32_t* __restrict__ seg_first, long long total_segments,
+                             int segment_bytes, jpeg_seg* __restrict__ segs, long long total_blocks, long long dst_bytes,
+                             int16_t* __restrict__ coefs, int* __restrict__ status, int32_t* __restrict__ info) {
+  __shared__ jpeg_dtab tab[4];       // dc 0, dc 1, ac 0, ac 1
+  __shared__ uint8_t zigzag[64];
+  __shared__ int32_t chain_sum[JPEG_PAR_LANES];
+  __shared__ uint32_t dc_sum[3 * JPEG_PAR_LANES];
+  __shared__ uint8_t run_flags[JPEG_PAR_LANES];
+  const int img = blockIdx.x, lane = threadIdx.x;
+  if (info && lane < 2) info[2 * img + lane] = 0;
+  jpeg_par_ctx c;
+  c.d = descs[img];
+  const asm_jpeg_desc& d = c.d;
+  const bool geom_ok = jpeg_make_geom(d, &c.g);
+  const int expect = geom_ok ? jpeg_expected_intervals(d, c.g) : 0;
+  const bool ok = geom_ok && desc_fits(d, c.g, files_bytes, total_blocks, dst_bytes) && d.restart_interval >= 0 &&
+                  d.first_interval >= 0 && d.n_intervals >= 1 && d.first_interval <= n_intervals_total - d.n_intervals;
+  if (!ok) {       // uniform over the workgroup
+    if (lane == 0) status[img] = ASM_JPEG_EDESC;
+    return;
+  }
+  if (lane == 0) status[img] = d.n_intervals == expect ? 0 : ASM_JPEG_ERESTART;
+  if (lane < 64) {
+    const uint8_t zz[64] = JPEG_ZIGZAG_INIT;
+    zigzag[lane] = zz[lane];
+  }
+  const asm_jpeg_tables& tb = tables[img];
+  if (lane < 4) jpeg_dtab_prepare(lane < 2 ? tb.dc[lane] : tb.ac[lane - 2], &tab[lane]);
+  int16_t* my_coefs = coefs + d.coef_offset;
+  {
+    uint4* z = reinterpret_cast<uint4*>(my_coefs);
+    const long long n16 = c.g.n_coefs / 8;
+    for (long long i = lane; i < n16; i += JPEG_PAR_LANES) z[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
+  __syncthreads();
+  for (int t = 0; t < 4; ++t) jpeg_dtab_fill_look(&tab[t], lane, JPEG_PAR_LANES);
+  if (d.n_intervals != expect) return;       // uniform
+  c.files = files;
+  c.bpm = d.ncomp == 1 ? 1 : d.hs * d.vs + 2;
+  c.intervals = intervals + d.first_interval;
+  c.seg_first = seg_first + d.first_interval;
+  c.img = img;
+  c.segment_bytes = segment_bytes;
+  c.tab = tab;
+  c.zigzag = zigzag;
+  c.coefs = my_coefs;
+  c.segs = nullptr;
+  c.n_segs = 0;
+  if (__syncthreads_or(jpeg_par_check_table(c, total_segments, lane, JPEG_PAR_LANES) ? 1 : 0)) {
+    if (lane == 0) atomicOr(&status[img], ASM_JPEG_EDESC);
+    return;
+  }
+  c.segs = segs + c.seg_first[0];
+  c.n_segs = jpeg_par_segments(c);
+  int err = jpeg_par_init(c, lane, JPEG_PAR_LANES);
+  __syncthreads();
+  // the fixed point: the truth advances at least one segment per round, so n_segs + 1 rounds always suffice
+  int rounds = 0;
+  for (int more = 1; more && rounds <= c.n_segs; ++rounds) {
+    jpeg_par_decode(c, lane, JPEG_PAR_LANES);
+    __syncthreads();
+    more = __syncthreads_or(jpeg_par_publish(c, lane, JPEG_PAR_LANES) ? 1 : 0);
+  }
+  jpeg_par_chain_sum(c, lane, JPEG_PAR_LANES, chain_sum, run_flags);
+  __syncthreads();
+  jpeg_par_chain_apply(c, lane, JPEG_PAR_LANES, chain_sum, run_flags);
+  __syncthreads();
+  err |= jpeg_par_write(c, lane, JPEG_PAR_LANES);
+  __syncthreads();
+  jpeg_par_dc_sum(c, lane, JPEG_PAR_LANES, dc_sum, run_flags);
+  __syncthreads();
+  jpeg_par_dc_apply(c, lane, JPEG_PAR_LANES, dc_sum, run_flags);
+  if (err) atomicOr(&status[img], err);
+  if (info && lane == 0) {
+    info[2 * img] = c.n_segs;
+    info[2 * img + 1] = rounds;
+  }
 }
 
 // Progressive files: the scans of one image one after another.  One workgroup is one wave on one CU, so the barrier
@@ -347,6 +437,50 @@ extern "C" int asm_jpeg_decode(const uint8_t* files, int64_t files_bytes, const 
     ASM_LAUNCH(jpeg_entropy_kernel, dim3(N), dim3(64), 0, s, files, files_bytes, descs, tables, intervals, n_intervals,
                total_blocks, dst_bytes, coefs, status);
     ASM_CHECK_LAUNCH("jpeg_decode (entropy)");
+  }
+  if (stages & 2)
+    return launch_pixel_stages(descs, tables, N, files_bytes, total_blocks, max_blocks, max_pixels, dst, dst_bytes, status,
+                               coefs, planes, s);
+  return ASM_OK;
+}
+
+extern "C" int asm_jpeg_decode_parallel_workspace_bytes(int64_t total_blocks, int64_t total_segments, int64_t* bytes) {
+  ASM_REQUIRE(bytes && total_blocks >= 0 && total_blocks < (1ll << 36) && total_segments >= 0 &&
+                  total_segments < (1ll << 30),
+              "jpeg_decode_parallel_workspace_bytes: bad sizes");
+  *bytes = total_blocks * (64 * 2 + 64) + total_segments * (int64_t)sizeof(jpeg_seg);
+  return ASM_OK;
+}
+
+extern "C" int asm_jpeg_decode_parallel(const uint8_t* files, int64_t files_bytes, const asm_jpeg_desc* descs,
+                                        const asm_jpeg_tables* tables, const asm_jpeg_interval* intervals,
+                                        const int32_t* segment_first, int N, int n_intervals, int64_t total_segments,
+                                        int segment_bytes, int64_t total_blocks, int max_blocks, int max_pixels,
+                                        uint8_t* dst, int64_t dst_bytes, int32_t* status, int32_t* info, void* workspace,
+                                        int64_t workspace_bytes, int stages, void* stream) {
+  ASM_REQUIRE(N >= 0 && n_intervals >= 0 && files_bytes >= 0 && files_bytes < (1ll << 40) && dst_bytes >= 0 &&
+                  total_blocks >= 0 && total_blocks < (1ll << 36) && max_blocks >= 0 && max_pixels >= 0 &&
+                  total_segments >= 0 && total_segments < (1ll << 30),
+              "jpeg_decode_parallel: bad sizes");
+  ASM_REQUIRE(segment_bytes >= 16 && segment_bytes <= 65536 && segment_bytes % 16 == 0,
+              "jpeg_decode_parallel: segment_bytes must be a multiple of 16 in 16..65536");
+  ASM_REQUIRE(stages >= 1 && stages <= 3, "jpeg_decode_parallel: stages must be 1, 2 or 3");
+  ASM_REQUIRE(N <= 65535, "jpeg_decode_parallel: at most 65535 images per call");
+  ASM_REQUIRE(workspace_bytes >= total_blocks * 192 + total_segments * (int64_t)sizeof(jpeg_seg),
+              "jpeg_decode_parallel: workspace too small");
+  if (N == 0) return ASM_OK;
+  ASM_REQUIRE(files && descs && tables && intervals && segment_first && dst && status && workspace,
+              "jpeg_decode_parallel: null pointer");
+  ASM_REQUIRE(((uintptr_t)workspace & 15) == 0, "jpeg_decode_parallel: workspace must be 16-byte aligned");
+  int16_t* coefs = (int16_t*)workspace;
+  uint8_t* planes = (uint8_t*)workspace + total_blocks * 128;
+  jpeg_seg* segs = (jpeg_seg*)((uint8_t*)workspace + total_blocks * 192);      // 16-byte aligned: 192 = 12 * 16
+  hipStream_t s = (hipStream_t)stream;
+  if (stages & 1) {
+    ASM_LAUNCH(jpeg_entropy_parallel_kernel, dim3(N), dim3(JPEG_PAR_LANES), 0, s, files, files_bytes, descs, tables,
+               intervals, n_intervals, segment_first, total_segments, segment_bytes, segs, total_blocks, dst_bytes, coefs,
+               status, info);
+    ASM_CHECK_LAUNCH("jpeg_decode_parallel (entropy)");
   }
   if (stages & 2)
     return launch_pixel_stages(descs, tables, N, files_bytes, total_blocks, max_blocks, max_pixels, dst, dst_bytes, status,

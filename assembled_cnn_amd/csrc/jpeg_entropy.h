@@ -272,6 +272,9 @@ JPEG_HD int jpeg_decode_lane(const uint8_t* files, const asm_jpeg_desc& d, const
   return err;
 }
 
+// one scan on many lanes: the segment-parallel form of jpeg_decode_lane (asm_jpeg_decode_parallel)
+#include "jpeg_parallel.h"
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Progressive files (T.81 annex G, libjpeg's jdphuff.c): one scan carries a spectral band ss..se of some components at
 // successive-approximation position al.  The four kinds -- DC first, DC refinement, AC first, AC refinement -- below,

@@ -176,7 +176,8 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
                      rng: Optional[np.random.Generator] = None, subtract_mean: bool = True,
                      windows: Optional[List[dict]] = None, autoaugment_type: Optional[str] = None,
                      augment: Optional[np.ndarray] = None, dct_method: str = '',
-                     jpeg_fallback=None, jpeg_progressive: bool = False) -> torch.Tensor:
+                     jpeg_fallback=None, jpeg_progressive: bool = False,
+                     jpeg_entropy: str = 'sequential') -> torch.Tensor:
   """The imagenet* branches of data_util.preprocess_image for a batch of decoded images; float32 NHWC on `device`.
   `windows` overrides the sampled / computed windows (tests share them with the oracle).
   `autoaugment_type` ('imagenet' | 'good' | 'v0' | 'test'): in training mode the policy runs on the resized image, clipped
@@ -187,7 +188,11 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
   (`dct_method` '' or 'INTEGER_ACCURATE'; 'INTEGER_FAST' raises NotImplementedError), its size for the window arithmetic
   comes from its header, and a file of a kind the device does not decode goes through `jpeg_fallback(bytes) -> uint8
   [H, W, 3]` (NotImplementedError without one).  A training crop is a window of the full decode.
-  `jpeg_progressive`: decode progressive files on the device as well (opt-in; they go to `jpeg_fallback` otherwise)."""
+  `jpeg_progressive`: decode progressive files on the device as well (opt-in; they go to `jpeg_fallback` otherwise).
+  `jpeg_entropy`: 'parallel' decodes each sequential file's scan on all lanes of a workgroup (opt-in, jpeg.py; the same
+  pixels)."""
+  if jpeg_entropy not in _jpeg.ENTROPY_MODES:
+    raise ValueError('jpeg_entropy must be one of %s, got %r' % (_jpeg.ENTROPY_MODES, jpeg_entropy))
   if autoaugment_type is not None:
     _aa.check_policy_name(autoaugment_type)
   side, crop_type = output_size_and_crop_type(preprocessing_type, is_training, image_size)
@@ -195,7 +200,8 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
     _jpeg.check_dct_method(dct_method)
   # encoded files are decoded on the device into their slots of the packed buffer, decoded arrays (given, or returned by
   # the fallback) travel to theirs in one staged copy; one window and one descriptor per slot
-  pk = _jpeg.pack(images, jpeg_fallback, progressive=jpeg_progressive)
+  pk = _jpeg.pack(images, jpeg_fallback, progressive=jpeg_progressive,
+                  segment_bytes=_jpeg.DEFAULT_SEGMENT_BYTES if jpeg_entropy == 'parallel' else None)
   if windows is None:
     if is_training:
       rng = rng if rng is not None else np.random.default_rng()
@@ -208,6 +214,6 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
   desc = np.zeros(n, dtype=_DESC_DTYPE)
   _fill_table(desc, pk.offsets, pk.sizes, windows, side, side)
   dev = torch.device(device)
-  bd = _jpeg.decode_packed(pk, dev)[0]
+  bd = _jpeg.decode_packed(pk, dev, entropy=jpeg_entropy)[0]
   return _augment_tail(bd, staging.upload_table(desc, dev), n, side, is_training, dev, rng, subtract_mean,
                        autoaugment_type, augment)

@@ -26,6 +26,10 @@ ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 1
                    46, 53, 60, 61, 54, 47, 55, 62, 63], dtype=np.int64)
 MAX_SIDE = 8192
 MAX_SCANS = 256         # of one progressive file: the device walks them one after another
+ENTROPY_MODES = ('sequential', 'parallel')
+# raw file bytes per segment of the segment-parallel entropy stage (entropy='parallel'); the best of the sweep in
+# profiles/jpeg_decode.md
+DEFAULT_SEGMENT_BYTES = 128
 
 # the device tables, as numpy sees the structs of lib.py (include/asm_hip.h)
 DESC_DTYPE = np.dtype(lib.JpegDesc)
@@ -394,6 +398,10 @@ class Packed:
     self.total_bytes = 16
     self.host_begin = 0             # the slots of the already decoded entries are [host_begin, total_bytes)
     self.total_blocks = self.max_blocks = self.max_pixels = 0
+    # pack(..., segment_bytes=...): asm_jpeg_decode_parallel's table, one entry per row of `intervals`
+    self.segment_bytes = None
+    self.segment_first = np.zeros(0, np.int32)
+    self.total_segments = 0
     self.dev_index = []             # batch index of each device row
     self.fallback = {}              # batch index -> decoded uint8 [H, W, 3]
     # the progressive rows (pack(..., progressive=True)), tables of their own for asm_jpeg_decode_progressive; the fields
@@ -488,14 +496,35 @@ def _pack_progressive(pk: Packed, infos, arrays):
   pk.prog_total_blocks = blocks_at
 
 
+def check_segment_bytes(segment_bytes: int) -> int:
+  if int(segment_bytes) != segment_bytes or not 16 <= segment_bytes <= 65536 or segment_bytes % 16:
+    raise ValueError('segment_bytes must be a multiple of 16 in 16..65536, got %r' % (segment_bytes,))
+  return int(segment_bytes)
+
+
+def segment_table(intervals: np.ndarray, segment_bytes: int):
+  """(int32 first segment of every interval row, total segments): an interval of b bytes has max(1, ceil(b /
+  segment_bytes)) segments and the rows follow each other without a gap (include/asm_hip.h, asm_jpeg_decode_parallel)"""
+  size = intervals['byte_end'].astype(np.int64) - intervals['byte_begin']
+  counts = np.maximum(-(-size // segment_bytes), 1)
+  ends = np.cumsum(counts)
+  total = int(ends[-1]) if len(ends) else 0
+  if total >= 2 ** 30:
+    raise ValueError('segment_bytes = %d gives %d segments, more than one call takes' % (segment_bytes, total))
+  return (ends - counts).astype(np.int32), total
+
+
 def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[List[JpegInfo]] = None,
-         progressive: bool = False) -> Packed:
+         progressive: bool = False, segment_bytes: Optional[int] = None) -> Packed:
   """Batch of entries -> the tables of asm_jpeg_decode (numpy, host).  An entry is an encoded file or an already decoded
   uint8 [H, W, 3] array (which only gets a slot in the output).  Files of an unsupported kind go through ``fallback(bytes)
   -> uint8 [H, W, 3]``; without one the call raises NotImplementedError naming the reason and the index.
   progressive: progressive files the device decodes become rows of a second group (the prog_* fields, the tables of
-  asm_jpeg_decode_progressive); `infos`, when given, must then have been parsed with the flag too."""
+  asm_jpeg_decode_progressive); `infos`, when given, must then have been parsed with the flag too.
+  segment_bytes: also fill the segment table of asm_jpeg_decode_parallel for the sequential rows (entropy='parallel')."""
   pk = Packed()
+  if segment_bytes is not None:
+    pk.segment_bytes = check_segment_bytes(segment_bytes)
   n = len(files)
   if infos is None:
     infos = [parse(f, progressive) if is_encoded(f) else None for f in files]
@@ -563,6 +592,8 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
     pk.files[o:o + scan.size] = scan
   pk.intervals = np.concatenate(rows) if rows else np.zeros(0, INTERVAL_DTYPE)
   pk.total_blocks = blocks_at
+  if pk.segment_bytes is not None:
+    pk.segment_first, pk.total_segments = segment_table(pk.intervals, pk.segment_bytes)
   if pk.prog_index:
     _pack_progressive(pk, infos, arrays)
   return pk
@@ -576,17 +607,32 @@ def _raise_corrupt(status_rows):
         [k for k, _ in bad], [st for _, st in bad]))
 
 
-def decode_packed(pk: Packed, device, stages: int = 3, check: bool = True, return_workspace: bool = False):
+def decode_packed(pk: Packed, device, stages: int = 3, check: bool = True, return_workspace: bool = False,
+                  entropy: str = 'sequential', return_info: bool = False):
   """Run the device decode of a packed batch and copy the already decoded entries into their slots (one staged copy).
   Returns (uint8 device buffer of pk.total_bytes, int32 status per device row: the sequential rows, then the progressive
   ones), plus ops.jpeg_decode's workspace (raw coefficients first) when return_workspace -- and, for a batch with
   progressive rows, ops.jpeg_decode_progressive's as a fourth value.  check: wait for the decode, return the status on
   the host and raise ValueError naming the entries whose entropy-coded data is corrupt.
-  The two groups are launched one after the other (three launches each) and write disjoint slots of the buffer."""
+  The two groups are launched one after the other (three launches each) and write disjoint slots of the buffer.
+  entropy: 'parallel' decodes the sequential rows with asm_jpeg_decode_parallel (the pack must have been made with
+  segment_bytes); every result is the same.  return_info (parallel only): append the int32 [rows, 2] device tensor of
+  segments and rounds per sequential row."""
+  if entropy not in ENTROPY_MODES:
+    raise ValueError('entropy must be one of %s, got %r' % (ENTROPY_MODES, entropy))
+  if entropy == 'parallel' and pk.segment_bytes is None:
+    raise ValueError("entropy='parallel' needs a batch packed with segment_bytes")
+  if return_info and entropy != 'parallel':
+    raise ValueError("return_info needs entropy='parallel'")
   dev = torch.device(device)
   dst = torch.empty(pk.total_bytes, dtype=torch.uint8, device=dev)
-  status = ws = prog_status = prog_ws = None
-  if pk.dev_index:
+  status = ws = prog_status = prog_ws = info = None
+  if pk.dev_index and entropy == 'parallel':
+    tabs = (pk.files, pk.descs, pk.tables, pk.intervals, pk.segment_first)
+    status, ws, info = ops.jpeg_decode_parallel(*(upload_table(t, dev) for t in tabs), len(pk.dev_index), len(pk.intervals),
+                                                pk.total_segments, pk.segment_bytes, pk.total_blocks, pk.max_blocks,
+                                                pk.max_pixels, dst, stages=stages, info=True)
+  elif pk.dev_index:
     status, ws = ops.jpeg_decode(*(upload_table(t, dev) for t in (pk.files, pk.descs, pk.tables, pk.intervals)),
                                  len(pk.dev_index), len(pk.intervals), pk.total_blocks, pk.max_blocks, pk.max_pixels, dst,
                                  stages=stages)
@@ -604,18 +650,27 @@ def decode_packed(pk: Packed, device, stages: int = 3, check: bool = True, retur
   if pk.fallback:
     keys = sorted(pk.fallback)
     stage_into(dst[pk.host_begin:], [pk.fallback[k] for k in keys], [pk.offsets[k] - pk.host_begin for k in keys])
-  if not return_workspace:
-    return dst, status
-  return (dst, status, ws, prog_ws) if pk.prog_index else (dst, status, ws)
+  out = (dst, status)
+  if return_workspace:
+    out += (ws, prog_ws) if pk.prog_index else (ws,)
+  return out + (info,) if return_info else out
 
 
 def decode_batch(files: Sequence, device, fallback: Optional[Callable] = None, dct_method: str = '',
-                 progressive: bool = False):
+                 progressive: bool = False, entropy: str = 'sequential', segment_bytes: Optional[int] = None):
   """Encoded files -> (packed uint8 device buffer, byte offsets, [(height, width)]): image k is
   buffer[offsets[k] : offsets[k] + 3 * h * w] viewed as [h, w, 3].  Raises ValueError naming the files whose
   entropy-coded data is corrupt, NotImplementedError for an unsupported kind without ``fallback``.
-  progressive: decode progressive files on the device too (they need no fallback then)."""
+  progressive: decode progressive files on the device too (they need no fallback then).
+  entropy: 'parallel' decodes each sequential file's scan on all lanes of a workgroup, in segments of segment_bytes
+  (default DEFAULT_SEGMENT_BYTES); the pixels are the same."""
   check_dct_method(dct_method)
-  pk = pack(files, fallback, progressive=progressive)
-  dst = decode_packed(pk, device)[0]
+  if entropy not in ENTROPY_MODES:
+    raise ValueError('entropy must be one of %s, got %r' % (ENTROPY_MODES, entropy))
+  if entropy == 'parallel':
+    segment_bytes = DEFAULT_SEGMENT_BYTES if segment_bytes is None else segment_bytes
+  elif segment_bytes is not None:
+    raise ValueError("segment_bytes needs entropy='parallel'")
+  pk = pack(files, fallback, progressive=progressive, segment_bytes=segment_bytes)
+  dst = decode_packed(pk, device, entropy=entropy)[0]
   return dst, pk.offsets, pk.sizes

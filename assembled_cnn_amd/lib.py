@@ -264,6 +264,9 @@ SIGNATURES = {
     'asm_autoaugment': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, C.c_int64, _P]),
     'asm_jpeg_decode_workspace_bytes': (_I, [C.c_int64, C.POINTER(C.c_int64)]),
     'asm_jpeg_decode': (_I, [_P, C.c_int64, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _P, C.c_int64, _P, _P, C.c_int64, _I, _P]),
+    'asm_jpeg_decode_parallel_workspace_bytes': (_I, [C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    'asm_jpeg_decode_parallel': (_I, [_P, C.c_int64, _P, _P, _P, _P, _I, _I, C.c_int64, _I, C.c_int64, _I, _I, _P, C.c_int64, _P,
+                                      _P, _P, C.c_int64, _I, _P]),
     'asm_jpeg_decode_progressive': (_I, [_P, C.c_int64, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, _I, _I, _P, C.c_int64, _P,
                                          _P, C.c_int64, _I, _P]),
     'asm_model_plan': (_I, [C.POINTER(ModelCfg), _I, _I, _I, C.POINTER(PlanEntry), _I, C.POINTER(PlanSummary)]),

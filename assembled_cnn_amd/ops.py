@@ -981,6 +981,28 @@ def jpeg_decode(files_u8, descs_dev, tables_dev, intervals_dev, n, n_intervals, 
   return status, ws
 
 
+def jpeg_decode_parallel(files_u8, descs_dev, tables_dev, intervals_dev, segment_first_dev, n, n_intervals, total_segments,
+                         segment_bytes, total_blocks, max_blocks, max_pixels, dst, stages=3, info=False):
+  """asm_jpeg_decode_parallel for a batch packed by jpeg.pack(segment_bytes=...): jpeg_decode's tables plus the int32
+  device table of each interval's first segment.  Same return values as jpeg_decode (the workspace's state rows follow
+  the planes), plus, with info, an int32 [n, 2] device tensor: segments and rounds per image."""
+  if (descs_dev.numel() != C.sizeof(_lib.JpegDesc) * n or tables_dev.numel() != C.sizeof(_lib.JpegTables) * n or
+      intervals_dev.numel() != C.sizeof(_lib.JpegInterval) * n_intervals or
+      segment_first_dev.numel() * segment_first_dev.element_size() != 4 * n_intervals):
+    raise ValueError('jpeg_decode_parallel: table sizes do not match n = %d, n_intervals = %d' % (n, n_intervals))
+  status = torch.empty((max(n, 1),), dtype=torch.int32, device=dst.device)[:n]
+  info_dev = torch.zeros((max(n, 1), 2), dtype=torch.int32, device=dst.device)[:n] if info else None
+  need = C.c_int64(0)
+  check(L().asm_jpeg_decode_parallel_workspace_bytes(total_blocks, total_segments, C.byref(need)),
+        'jpeg_decode_parallel_workspace_bytes')
+  ws = _workspace(max(need.value, 16), dst) if n else None
+  check(L().asm_jpeg_decode_parallel(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev), _ptr(intervals_dev),
+                                     _ptr(segment_first_dev), n, n_intervals, total_segments, segment_bytes, total_blocks,
+                                     max_blocks, max_pixels, _ptr(dst), dst.numel(), _ptr(status),
+                                     _ptr(info_dev), _ptr(ws), need.value, stages, _stream()), 'jpeg_decode_parallel')
+  return (status, ws, info_dev) if info else (status, ws)
+
+
 def jpeg_decode_progressive(files_u8, descs_dev, tables_dev, scans_dev, huff_dev, intervals_dev, n, n_scans, n_huff,
                             n_intervals, total_blocks, max_blocks, max_pixels, dst, stages=3):
   """asm_jpeg_decode_progressive for the progressive rows packed by jpeg.pack(progressive=True): as jpeg_decode, with

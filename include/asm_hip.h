@@ -35,8 +35,8 @@ extern "C" {
 #define ASM_ENOTSUP (-2)
 #define ASM_EHIP (-3)
 
-/* Changes when an existing struct or signature changes.  Additions keep it: asm_jpeg_decode_progressive and
- * asm_jpeg_scan came in under 11. */
+/* Changes when an existing struct or signature changes.  Additions keep it: asm_jpeg_decode_progressive,
+ * asm_jpeg_scan and asm_jpeg_decode_parallel came in under 11. */
 #define ASM_ABI_VERSION 11
 
 const char* asm_last_error(void);
@@ -679,6 +679,34 @@ int asm_jpeg_decode(const uint8_t* files, int64_t files_bytes, const asm_jpeg_de
                     const asm_jpeg_interval* intervals, int N, int n_intervals, int64_t total_blocks, int max_blocks,
                     int max_pixels, uint8_t* dst, int64_t dst_bytes, int32_t* status, void* workspace,
                     int64_t workspace_bytes, int stages, void* stream);
+
+/* One scan on many lanes: a second entropy stage for the same rows as asm_jpeg_decode (sequential SOF0 / SOF1 files), in
+ * front of the same pixel stages.  Every restart interval is cut into segments of `segment_bytes` raw (stuffed) file
+ * bytes -- the last segment of an interval takes the remainder, an interval no longer than one segment is one segment --
+ * and one 256-lane workgroup per image decodes all segments at once: from guessed states first, in rounds, until no
+ * segment's exit state changes the next one's entry (Huffman codes resynchronise by themselves), then once more from the
+ * proven states to store the coefficients; DC values are a per-component prefix sum.  DESIGN.md 1.2 has the rules.
+ * For every input it leaves the status word asm_jpeg_decode leaves, and where that is 0 the same coefficients and pixels.
+ *   files .. intervals, N, n_intervals, total_blocks .. status, stages: as for asm_jpeg_decode (files_bytes < 2^40)
+ *   segment_bytes  a multiple of 16 in 16..65536
+ *   segment_first  int32 [n_intervals], one entry per row of `intervals`: the index in the state region of that
+ *              interval's first segment.  Interval r owns the rows [segment_first[r], segment_first[r] + n_r) with
+ *              n_r = max(1, ceil((byte_end - byte_begin) / segment_bytes)); the intervals of one image follow each other
+ *              without a gap (segment_first[r + 1] == segment_first[r] + n_r), no two images share a row, and every
+ *              row lies in [0, total_segments), total_segments < 2^30.  A table that breaks the first or the last rule
+ *              gives the image ASM_JPEG_EDESC.  Images that share rows overwrite each other's states and may decode
+ *              wrongly (any status, any coefficients), but the device treats the state rows as untrusted data: whatever
+ *              they hold, no table index leaves the image's own rows and no byte is read outside a checked interval.
+ *   info       optional int32 [N][2], written by the call: segments of the image, rounds its workgroup ran (0, 0 for
+ *              a refused descriptor); may be null
+ *   workspace  asm_jpeg_decode_parallel_workspace_bytes(total_blocks, total_segments): asm_jpeg_decode's coefficients
+ *              and planes, then total_segments state rows of 32 bytes */
+int asm_jpeg_decode_parallel_workspace_bytes(int64_t total_blocks, int64_t total_segments, int64_t* bytes);
+int asm_jpeg_decode_parallel(const uint8_t* files, int64_t files_bytes, const asm_jpeg_desc* descs,
+                             const asm_jpeg_tables* tables, const asm_jpeg_interval* intervals, const int32_t* segment_first,
+                             int N, int n_intervals, int64_t total_segments, int segment_bytes, int64_t total_blocks,
+                             int max_blocks, int max_pixels, uint8_t* dst, int64_t dst_bytes, int32_t* status, int32_t* info,
+                             void* workspace, int64_t workspace_bytes, int stages, void* stream);
 
 /* Progressive files (SOF2; T.81 annex G, libjpeg's jdphuff.c): a second entropy stage in front of the same pixel stages.
  * One 64-lane workgroup per image zeroes the image's coefficients and walks its scans IN FILE ORDER (a refinement scan

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Throughput of the rows either side of the training step: the GPU input-pipeline tail (resize/crop/flip/mean-sub
 kernel), the device JPEG decoder in front of it, and evaluation-mode inference with the on-device metrics (BASELINE
-configs 1 and 3-eval).  `--only jpeg` runs the JPEG leg alone, `--only jpeg_progressive` the progressive-file leg."""
+configs 1 and 3-eval).  `--only jpeg` runs the JPEG leg alone, `--only jpeg_progressive` the progressive-file leg,
+`--only jpeg_parallel` the sequential entropy stage against the segment-parallel one."""
 import os, sys, time
 import numpy as np
 import torch
@@ -20,6 +21,21 @@ def ev(fn, iters=10):
   return a.elapsed_time(b) / iters
 
 
+def photographic_files(n, rng):
+  """n files of about 500 x 375, 4:2:0, quality 90, no restart markers: smooth random fields + sigma-9 noise"""
+  import io
+  from PIL import Image
+  files = []
+  for _ in range(n):
+    w, h = int(rng.integers(440, 561)), int(rng.integers(330, 421))
+    low = Image.fromarray(rng.integers(0, 256, size=(h // 24 + 2, w // 24 + 2, 3), dtype=np.uint8)).resize((w, h), Image.BICUBIC)
+    arr = np.clip(np.asarray(low).astype(np.float32) + rng.normal(0, 9, size=(h, w, 3)), 0, 255).astype(np.uint8)
+    b = io.BytesIO()
+    Image.fromarray(arr).save(b, 'JPEG', quality=90, subsampling=2)
+    files.append(b.getvalue())
+  return files
+
+
 def jpeg_leg(n=256):
   """Device JPEG decode of n files of about 500 x 375, 4:2:0, quality 90, no restart markers: the entropy stage, the pixel
   stages, the whole decode_batch (host parse and packing included), the same files through Pillow on 16 threads, and what
@@ -32,14 +48,7 @@ def jpeg_leg(n=256):
   except ImportError:
     Image = None
   if Image is not None:
-    files = []
-    for _ in range(n):
-      w, h = int(rng.integers(440, 561)), int(rng.integers(330, 421))
-      low = Image.fromarray(rng.integers(0, 256, size=(h // 24 + 2, w // 24 + 2, 3), dtype=np.uint8)).resize((w, h), Image.BICUBIC)
-      arr = np.clip(np.asarray(low).astype(np.float32) + rng.normal(0, 9, size=(h, w, 3)), 0, 255).astype(np.uint8)
-      b = io.BytesIO()
-      Image.fromarray(arr).save(b, 'JPEG', quality=90, subsampling=2)
-      files.append(b.getvalue())
+    files = photographic_files(n, rng)
     source = 'generated with Pillow: smooth fields + sigma-9 noise, 440..560 x 330..420, 4:2:0, quality 90'
   else:
     fx = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden', 'jpeg_fixtures.npz'))
@@ -81,6 +90,86 @@ def jpeg_leg(n=256):
     t0 = time.time(); buf, table = P.pack_batch(arrays, wins, 224, 224, pin=True); buf.cuda(); table.cuda(); torch.cuda.synchronize()
     best = min(best, 1e3 * (time.time() - t0))
   print('decoded arrays today: pack_batch + H2D %.2f ms per batch of %d (%.1f MB)' % (best, n, sum(a.size for a in arrays) / 1e6))
+
+
+def jpeg_parallel_leg(n=256):
+  """The sequential entropy stage (one lane per restart interval) against the segment-parallel one (asm_jpeg_decode_parallel,
+  one scan on all lanes of a workgroup) on the files of jpeg_leg, in one run: the two alternating, three runs each, entropy
+  stage alone and whole decode_batch; the segment_bytes sweep with mean and max rounds; both at 1024 files per call; and a
+  batch of white-noise files, which do not resynchronise.  Ends with the bar: the slowest parallel entropy run beats the
+  fastest sequential one on the photographic batch."""
+  import io
+  from PIL import Image
+  from assembled_cnn_amd import jpeg
+  many = photographic_files(4 * n, np.random.default_rng(1))       # the first n are jpeg_leg's files
+  rng = np.random.default_rng(2)
+  noise = []
+  for _ in range(n):
+    b = io.BytesIO()
+    Image.fromarray(rng.integers(0, 256, size=(192, 256, 3), dtype=np.uint8)).save(b, 'JPEG', quality=100, subsampling=0)
+    noise.append(b.getvalue())
+
+  def stage(files, segment_bytes):
+    """(run(stages) for the batch, its pack, its output buffer); segment_bytes None: the sequential stage"""
+    pk = jpeg.pack(files, segment_bytes=segment_bytes)
+    tabs = [staging.upload_table(t, 'cuda') for t in (pk.files, pk.descs, pk.tables, pk.intervals)]
+    dst = torch.empty(pk.total_bytes, dtype=torch.uint8, device='cuda')
+    sizes = (pk.total_blocks, pk.max_blocks, pk.max_pixels, dst)
+    if segment_bytes is None:
+      return (lambda stages: ops.jpeg_decode(*tabs, len(files), len(pk.intervals), *sizes, stages=stages)), pk, dst
+    sf = staging.upload_table(pk.segment_first, 'cuda')
+    return (lambda stages: ops.jpeg_decode_parallel(*tabs, sf, len(files), len(pk.intervals), pk.total_segments, segment_bytes,
+                                                    *sizes, stages=stages, info=True)), pk, dst
+
+  def entropy_runs(files, segment_bytes, what):
+    seq, _, dst_s = stage(files, None)
+    par, _, dst_p = stage(files, segment_bytes)
+    assert not seq(3)[0].any() and not par(3)[0].any()
+    torch.cuda.synchronize()
+    assert torch.equal(dst_s, dst_p), 'the parallel stage differs from the sequential one'
+    info = par(1)[2].cpu().numpy()
+    ms_s, ms_p = [], []
+    for _ in range(3):       # alternating
+      ms_s.append(ev(lambda: seq(1), iters=3))
+      ms_p.append(ev(lambda: par(1), iters=3))
+    k = len(files)
+    print('%s, %d files (mean %.1f KB), entropy stage alone, ms per batch, three alternating runs:' % (what, k, sum(map(len, files)) / k / 1e3))
+    print('  sequential                 : %s  (best %6.0f img/s)' % (' '.join('%8.2f' % m for m in ms_s), k / min(ms_s) * 1e3))
+    print('  parallel, segment_bytes %3d: %s  (worst %6.0f img/s); %.0f segments per file, rounds mean %.1f max %d'
+          % (segment_bytes, ' '.join('%8.2f' % m for m in ms_p), k / max(ms_p) * 1e3, info[:, 0].mean(), info[:, 1].mean(),
+             info[:, 1].max()))
+    print('  slowest parallel / fastest sequential: %.3f (sequential is %.1f x the parallel time)'
+          % (max(ms_p) / min(ms_s), min(ms_s) / max(ms_p)))
+    return ms_s, ms_p
+
+  files = many[:n]
+  default = jpeg.DEFAULT_SEGMENT_BYTES
+  print('jpeg parallel: segment_bytes sweep, %d photographic files, entropy stage alone' % n)
+  for sb in (32, 64, 128, 256, 512, 1024):
+    par, _, _ = stage(files, sb)
+    assert not par(3)[0].any()
+    info = par(1)[2].cpu().numpy()
+    print('  segment_bytes %4d: %8.2f ms per batch; %6.0f segments per file, rounds mean %.1f max %d'
+          % (sb, ev(lambda: par(1), iters=3), info[:, 0].mean(), info[:, 1].mean(), info[:, 1].max()))
+  ms_s, ms_p = entropy_runs(files, default, 'photographic')
+  whole_s, whole_p = [], []
+  for _ in range(3):
+    t0 = time.time(); jpeg.decode_batch(files, 'cuda'); torch.cuda.synchronize(); whole_s.append(1e3 * (time.time() - t0))
+    t0 = time.time(); jpeg.decode_batch(files, 'cuda', entropy='parallel'); torch.cuda.synchronize()
+    whole_p.append(1e3 * (time.time() - t0))
+  print('whole decode_batch, %d files, ms per batch, three alternating runs:' % n)
+  print('  sequential: %s  (best %6.0f img/s)' % (' '.join('%8.2f' % m for m in whole_s), n / min(whole_s) * 1e3))
+  print('  parallel  : %s  (best %6.0f img/s)' % (' '.join('%8.2f' % m for m in whole_p), n / min(whole_p) * 1e3))
+  dec = lambda f: np.asarray(Image.open(io.BytesIO(f)).convert('RGB'))
+  import concurrent.futures
+  with concurrent.futures.ThreadPoolExecutor(16) as ex:
+    list(ex.map(dec, files[:32]))
+    t0 = time.time(); list(ex.map(dec, files)); ms_pil = 1e3 * (time.time() - t0)
+  print('Pillow, 16 threads : %8.2f ms per batch of %d (%6.0f img/s)' % (ms_pil, n, n / ms_pil * 1e3))
+  entropy_runs(many, default, 'photographic')
+  entropy_runs(noise, default, 'white noise 256 x 192, 4:4:4, quality 100')
+  assert max(ms_p) < min(ms_s), 'the bar: the slowest parallel entropy run must beat the fastest sequential one'
+  print('jpeg parallel: bar met, slowest parallel %.2f ms < fastest sequential %.2f ms' % (max(ms_p), min(ms_s)))
 
 
 def jpeg_progressive_leg(n=256):
@@ -158,8 +247,9 @@ def jpeg_progressive_leg(n=256):
         % (ms_e / ms_be, 100 * ms_e / (ms_e + ms_p)))
 
 
-if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] in ('jpeg', 'jpeg_progressive'):
-  jpeg_progressive_leg() if sys.argv[sys.argv.index('--only') + 1] == 'jpeg_progressive' else jpeg_leg()
+if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] in ('jpeg', 'jpeg_progressive', 'jpeg_parallel'):
+  {'jpeg': jpeg_leg, 'jpeg_progressive': jpeg_progressive_leg, 'jpeg_parallel': jpeg_parallel_leg}[
+      sys.argv[sys.argv.index('--only') + 1]]()
   sys.exit(0)
 
 rng = np.random.default_rng(0)
