@@ -9,6 +9,8 @@
 //                        walks the image's scans in file order, tables rebuilt in LDS per scan, a barrier between scans
 //   jpeg_idct_kernel     one thread per 8x8 block: dequantise + jidctint.c's jpeg_idct_islow -> uint8 planes
 //   jpeg_colour_kernel   one thread per pixel: jdsample.c's fancy h2v1 / h2v2 upsampling + jdcolor.c's YCbCr -> RGB
+// The entropy kernels open with the same text: jpeg_image_begin, jpeg_image_clear and (sequential, parallel)
+// jpeg_baseline_tables; the three entry points share jpeg_call_begin / jpeg_call_finish around their own launch.
 // Every index is checked against the image's own geometry and the sizes the caller passed; an image whose entropy decode
 // failed (status != 0) gets zeros (a refused descriptor too, as long as its slot in dst fits on its own).
 #include "common.h"
@@ -31,6 +33,41 @@ __device__ __forceinline__ bool desc_fits(const asm_jpeg_desc& d, const jpeg_geo
          d.acsel[0] < 2 && d.acsel[1] < 2 && d.acsel[2] < 2;
 }
 
+// What every entropy kernel does first: the image's descriptor, its geometry, and whether its regions fit this call.
+// Uniform over the workgroup; writes nothing and contains no barrier.  The kernel ANDs its own conditions to the result
+// and, on false, leaves with the one write a refused descriptor gets: status[img] = ASM_JPEG_EDESC from lane 0.
+__device__ __forceinline__ bool jpeg_image_begin(const asm_jpeg_desc* __restrict__ descs, int img, long long files_bytes,
+                                                 long long total_blocks, long long dst_bytes, asm_jpeg_desc* d, jpeg_geom* g) {
+  *d = descs[img];
+  return jpeg_make_geom(*d, g) && desc_fits(*d, *g, files_bytes, total_blocks, dst_bytes);
+}
+
+// What follows acceptance: the zig-zag table into LDS and the image's coefficients zeroed (64 coefficients = 128 bytes
+// per block, 16 bytes per store), by `lanes` lanes.  Contains no barrier: the caller's next one publishes both.
+__device__ __forceinline__ void jpeg_image_clear(const jpeg_geom& g, uint8_t* zigzag, int16_t* my_coefs, int lane, int lanes) {
+  if (lane < 64) {
+    const uint8_t zz[64] = JPEG_ZIGZAG_INIT;
+    zigzag[lane] = zz[lane];
+  }
+  uint4* z = reinterpret_cast<uint4*>(my_coefs);
+  const long long n16 = g.n_coefs / 8;
+  for (long long i = lane; i < n16; i += lanes) z[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// The sequential and the parallel kernel after that: status[img] = 0, or ASM_JPEG_ERESTART for an interval count that is
+// not the geometry's; the four tables built by lanes 0..3 and their look-ups filled by all lanes.  Contains ONE barrier,
+// between the two, which also publishes jpeg_image_clear's stores; the look-ups are published by the caller's next
+// barrier.  false (uniform): the count is wrong and the kernel returns -- after that barrier of its own, if it has one.
+__device__ __forceinline__ bool jpeg_baseline_tables(const asm_jpeg_desc& d, const jpeg_geom& g, const asm_jpeg_tables& tb,
+                                                     jpeg_dtab* tab, int* status_word, int lane, int lanes) {
+  const bool counted = d.n_intervals == jpeg_expected_intervals(d.restart_interval, g.n_mcus);
+  if (lane == 0) *status_word = counted ? 0 : ASM_JPEG_ERESTART;
+  if (lane < 4) jpeg_dtab_prepare(lane < 2 ? tb.dc[lane] : tb.ac[lane - 2], &tab[lane]);
+  __syncthreads();
+  for (int t = 0; t < 4; ++t) jpeg_dtab_fill_look(&tab[t], lane, lanes);
+  return counted;
+}
+
 __global__ void __launch_bounds__(64)
 jpeg_entropy_kernel(const uint8_t* __restrict__ files, long long files_bytes, const asm_jpeg_desc* __restrict__ descs,
                     const asm_jpeg_tables* __restrict__ tables, const asm_jpeg_interval* __restrict__ intervals,
@@ -39,34 +76,19 @@ jpeg_entropy_kernel(const uint8_t* __restrict__ files, long long files_bytes, co
   __shared__ jpeg_dtab tab[4];       // dc 0, dc 1, ac 0, ac 1
   __shared__ uint8_t zigzag[64];
   const int img = blockIdx.x, lane = threadIdx.x;
-  const asm_jpeg_desc d = descs[img];
+  asm_jpeg_desc d;
   jpeg_geom g;
-  const bool geom_ok = jpeg_make_geom(d, &g);
-  const int expect = geom_ok ? jpeg_expected_intervals(d, g) : 0;
-  const bool ok = geom_ok && desc_fits(d, g, files_bytes, total_blocks, dst_bytes) && d.restart_interval >= 0 &&
+  const bool ok = jpeg_image_begin(descs, img, files_bytes, total_blocks, dst_bytes, &d, &g) && d.restart_interval >= 0 &&
                   d.first_interval >= 0 && d.n_intervals >= 1 && d.first_interval <= n_intervals_total - d.n_intervals;
   if (!ok) {       // uniform over the workgroup
     if (lane == 0) status[img] = ASM_JPEG_EDESC;
     return;
   }
-  if (lane == 0) status[img] = d.n_intervals == expect ? 0 : ASM_JPEG_ERESTART;
-  {
-    const uint8_t zz[64] = JPEG_ZIGZAG_INIT;
-    zigzag[lane] = zz[lane];
-  }
-  const asm_jpeg_tables& tb = tables[img];
-  if (lane < 4) jpeg_dtab_prepare(lane < 2 ? tb.dc[lane] : tb.ac[lane - 2], &tab[lane]);
-  // zero the image's coefficients: 64 coefficients = 128 bytes per block, 16 bytes per store
   int16_t* my_coefs = coefs + d.coef_offset;
-  {
-    uint4* z = reinterpret_cast<uint4*>(my_coefs);
-    const long long n16 = g.n_coefs / 8;
-    for (long long i = lane; i < n16; i += 64) z[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
+  jpeg_image_clear(g, zigzag, my_coefs, lane, 64);
+  const bool counted = jpeg_baseline_tables(d, g, tables[img], tab, &status[img], lane, 64);
   __syncthreads();
-  for (int t = 0; t < 4; ++t) jpeg_dtab_fill_look(&tab[t], lane, 64);
-  __syncthreads();
-  if (d.n_intervals != expect) return;
+  if (!counted) return;
   const int err = jpeg_decode_lane(files, d, g, intervals, img, tab, zigzag, lane, 64, my_coefs);
   if (err) atomicOr(&status[img], err);
 }
@@ -90,43 +112,19 @@ jpeg_entropy_parallel_kernel(const uint8_t* __restrict__ files, long long files_
   const int img = blockIdx.x, lane = threadIdx.x;
   if (info && lane < 2) info[2 * img + lane] = 0;
   jpeg_par_ctx c;
-  c.d = descs[img];
   const asm_jpeg_desc& d = c.d;
-  const bool geom_ok = jpeg_make_geom(d, &c.g);
-  const int expect = geom_ok ? jpeg_expected_intervals(d, c.g) : 0;
-  const bool ok = geom_ok && desc_fits(d, c.g, files_bytes, total_blocks, dst_bytes) && d.restart_interval >= 0 &&
+  const bool ok = jpeg_image_begin(descs, img, files_bytes, total_blocks, dst_bytes, &c.d, &c.g) && d.restart_interval >= 0 &&
                   d.first_interval >= 0 && d.n_intervals >= 1 && d.first_interval <= n_intervals_total - d.n_intervals;
   if (!ok) {       // uniform over the workgroup
     if (lane == 0) status[img] = ASM_JPEG_EDESC;
     return;
   }
-  if (lane == 0) status[img] = d.n_intervals == expect ? 0 : ASM_JPEG_ERESTART;
-  if (lane < 64) {
-    const uint8_t zz[64] = JPEG_ZIGZAG_INIT;
-    zigzag[lane] = zz[lane];
-  }
-  const asm_jpeg_tables& tb = tables[img];
-  if (lane < 4) jpeg_dtab_prepare(lane < 2 ? tb.dc[lane] : tb.ac[lane - 2], &tab[lane]);
   int16_t* my_coefs = coefs + d.coef_offset;
-  {
-    uint4* z = reinterpret_cast<uint4*>(my_coefs);
-    const long long n16 = c.g.n_coefs / 8;
-    for (long long i = lane; i < n16; i += JPEG_PAR_LANES) z[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
-  __syncthreads();
-  for (int t = 0; t < 4; ++t) jpeg_dtab_fill_look(&tab[t], lane, JPEG_PAR_LANES);
-  if (d.n_intervals != expect) return;       // uniform
-  c.files = files;
-  c.bpm = d.ncomp == 1 ? 1 : d.hs * d.vs + 2;
-  c.intervals = intervals + d.first_interval;
-  c.seg_first = seg_first + d.first_interval;
-  c.img = img;
-  c.segment_bytes = segment_bytes;
-  c.tab = tab;
-  c.zigzag = zigzag;
-  c.coefs = my_coefs;
-  c.segs = nullptr;
-  c.n_segs = 0;
+  jpeg_image_clear(c.g, zigzag, my_coefs, lane, JPEG_PAR_LANES);
+  // the look-ups are published by the barrier of the table check below
+  if (!jpeg_baseline_tables(d, c.g, tables[img], tab, &status[img], lane, JPEG_PAR_LANES)) return;
+  jpeg_par_ctx_fill(&c, files, intervals + d.first_interval, seg_first + d.first_interval, img, segment_bytes, tab, zigzag,
+                    my_coefs);
   if (__syncthreads_or(jpeg_par_check_table(c, total_segments, lane, JPEG_PAR_LANES) ? 1 : 0)) {
     if (lane == 0) atomicOr(&status[img], ASM_JPEG_EDESC);
     return;
@@ -172,12 +170,12 @@ jpeg_progressive_kernel(const uint8_t* __restrict__ files, long long files_bytes
   __shared__ uint8_t zigzag[64];
   __shared__ int failed;             // some lane has seen an error: the scans that follow are skipped
   const int img = blockIdx.x, lane = threadIdx.x;
-  const asm_jpeg_desc d = descs[img];
+  asm_jpeg_desc d;
   jpeg_geom g;
-  const bool geom_ok = jpeg_make_geom(d, &g);
+  const bool fits = jpeg_image_begin(descs, img, files_bytes, total_blocks, dst_bytes, &d, &g);
   // first_interval / n_intervals name the image's rows of the scan table here
   const int first_scan = d.first_interval, n_scans = d.n_intervals;
-  const bool ok = geom_ok && desc_fits(d, g, files_bytes, total_blocks, dst_bytes) && d.restart_interval == 0 &&
+  const bool ok = fits && d.restart_interval == 0 &&
                   (d.dcsel[0] | d.dcsel[1] | d.dcsel[2] | d.acsel[0] | d.acsel[1] | d.acsel[2]) == 0 && d.reserved == 0 &&
                   first_scan >= 0 && n_scans >= 1 && n_scans <= 256 && first_scan <= n_scans_total - n_scans;
   if (!ok) {       // uniform over the workgroup
@@ -188,16 +186,8 @@ jpeg_progressive_kernel(const uint8_t* __restrict__ files, long long files_bytes
     status[img] = 0;
     failed = 0;
   }
-  {
-    const uint8_t zz[64] = JPEG_ZIGZAG_INIT;
-    zigzag[lane] = zz[lane];
-  }
   int16_t* my_coefs = coefs + d.coef_offset;
-  {
-    uint4* z = reinterpret_cast<uint4*>(my_coefs);
-    const long long n16 = g.n_coefs / 8;
-    for (long long i = lane; i < n16; i += 64) z[i] = make_uint4(0u, 0u, 0u, 0u);
-  }
+  jpeg_image_clear(g, zigzag, my_coefs, lane, 64);
   __syncthreads();
   int err = 0;
   for (int k = 0; k < n_scans; ++k) {
@@ -394,13 +384,28 @@ jpeg_colour_kernel(const asm_jpeg_desc* __restrict__ descs, long long files_byte
 
 }  // namespace
 
+// workspace of a call: int16 coefficients, then uint8 planes, per 8x8 block (both multiples of 16 bytes)
+#define JPEG_COEF_BYTES_PER_BLOCK 128
+#define JPEG_PLANE_BYTES_PER_BLOCK 64
+static int64_t jpeg_workspace_bytes(int64_t total_blocks) {
+  return total_blocks * (JPEG_COEF_BYTES_PER_BLOCK + JPEG_PLANE_BYTES_PER_BLOCK);
+}
+
 extern "C" int asm_jpeg_decode_workspace_bytes(int64_t total_blocks, int64_t* bytes) {
   ASM_REQUIRE(bytes && total_blocks >= 0 && total_blocks < (1ll << 36), "jpeg_decode_workspace_bytes: bad sizes");
-  *bytes = total_blocks * (64 * 2 + 64);
+  *bytes = jpeg_workspace_bytes(total_blocks);
   return ASM_OK;
 }
 
-// the inverse DCT and the colour launch for N rows whose coefficients are in place (both entry points end here)
+extern "C" int asm_jpeg_decode_parallel_workspace_bytes(int64_t total_blocks, int64_t total_segments, int64_t* bytes) {
+  ASM_REQUIRE(bytes && total_blocks >= 0 && total_blocks < (1ll << 36) && total_segments >= 0 &&
+                  total_segments < (1ll << 30),
+              "jpeg_decode_parallel_workspace_bytes: bad sizes");
+  *bytes = jpeg_workspace_bytes(total_blocks) + total_segments * (int64_t)sizeof(jpeg_seg);
+  return ASM_OK;
+}
+
+// the inverse DCT and the colour launch for N rows whose coefficients are in place (every entry point ends here)
 static int launch_pixel_stages(const asm_jpeg_desc* descs, const asm_jpeg_tables* tables, int N, int64_t files_bytes,
                                int64_t total_blocks, int max_blocks, int max_pixels, uint8_t* dst, int64_t dst_bytes,
                                const int32_t* status, const int16_t* coefs, uint8_t* planes, hipStream_t s) {
@@ -417,39 +422,64 @@ static int launch_pixel_stages(const asm_jpeg_desc* descs, const asm_jpeg_tables
   return ASM_OK;
 }
 
+// The arguments the three entry points have in common, and what jpeg_call_begin carves from the workspace.
+struct jpeg_call {
+  const uint8_t* files;
+  const asm_jpeg_desc* descs;
+  const asm_jpeg_tables* tables;
+  uint8_t* dst;
+  int32_t* status;
+  void* workspace;
+  int64_t files_bytes, dst_bytes, total_blocks, workspace_bytes;
+  int N, max_blocks, max_pixels, stages;
+  hipStream_t s;
+  int16_t* coefs;       // workspace
+  uint8_t* planes;      // workspace + total_blocks * JPEG_COEF_BYTES_PER_BLOCK
+};
+
+// What the entry points check alike, in their order: sizes (own_sizes_ok: the entry point's own counts), own_error (null,
+// or what is wrong with an argument only this entry point has), stages, N, the workspace (own_bytes: what the entry point
+// keeps behind coefficients and planes); nothing more for N == 0; then the pointers (own_pointers: the entry point's own
+// tables) and the alignment.  `name` keeps every message the entry point's.
+static int jpeg_call_begin(const char* name, jpeg_call* c, bool own_sizes_ok, const char* own_error, bool own_pointers,
+                           int64_t own_bytes) {
+  ASM_REQUIRE(c->N >= 0 && c->files_bytes >= 0 && c->dst_bytes >= 0 && c->total_blocks >= 0 && c->total_blocks < (1ll << 36) &&
+                  c->max_blocks >= 0 && c->max_pixels >= 0 && own_sizes_ok,
+              "%s: bad sizes", name);
+  ASM_REQUIRE(!own_error, "%s: %s", name, own_error);
+  ASM_REQUIRE(c->stages >= 1 && c->stages <= 3, "%s: stages must be 1, 2 or 3", name);
+  ASM_REQUIRE(c->N <= 65535, "%s: at most 65535 images per call", name);
+  ASM_REQUIRE(c->workspace_bytes >= jpeg_workspace_bytes(c->total_blocks) + own_bytes, "%s: workspace too small", name);
+  if (c->N == 0) return ASM_OK;
+  ASM_REQUIRE(c->files && c->descs && c->tables && own_pointers && c->dst && c->status && c->workspace, "%s: null pointer",
+              name);
+  ASM_REQUIRE(((uintptr_t)c->workspace & 15) == 0, "%s: workspace must be 16-byte aligned", name);
+  c->coefs = (int16_t*)c->workspace;
+  c->planes = (uint8_t*)c->workspace + c->total_blocks * JPEG_COEF_BYTES_PER_BLOCK;
+  return ASM_OK;
+}
+
+// after the entry point's own entropy launch
+static int jpeg_call_finish(const jpeg_call& c) {
+  if (!(c.stages & 2)) return ASM_OK;
+  return launch_pixel_stages(c.descs, c.tables, c.N, c.files_bytes, c.total_blocks, c.max_blocks, c.max_pixels, c.dst,
+                             c.dst_bytes, c.status, c.coefs, c.planes, c.s);
+}
+
 extern "C" int asm_jpeg_decode(const uint8_t* files, int64_t files_bytes, const asm_jpeg_desc* descs,
                                const asm_jpeg_tables* tables, const asm_jpeg_interval* intervals, int N, int n_intervals,
                                int64_t total_blocks, int max_blocks, int max_pixels, uint8_t* dst, int64_t dst_bytes,
                                int32_t* status, void* workspace, int64_t workspace_bytes, int stages, void* stream) {
-  ASM_REQUIRE(N >= 0 && n_intervals >= 0 && files_bytes >= 0 && dst_bytes >= 0 && total_blocks >= 0 &&
-                  total_blocks < (1ll << 36) && max_blocks >= 0 && max_pixels >= 0,
-              "jpeg_decode: bad sizes");
-  ASM_REQUIRE(stages >= 1 && stages <= 3, "jpeg_decode: stages must be 1, 2 or 3");
-  ASM_REQUIRE(N <= 65535, "jpeg_decode: at most 65535 images per call");
-  ASM_REQUIRE(workspace_bytes >= total_blocks * 192, "jpeg_decode: workspace too small");
-  if (N == 0) return ASM_OK;
-  ASM_REQUIRE(files && descs && tables && intervals && dst && status && workspace, "jpeg_decode: null pointer");
-  ASM_REQUIRE(((uintptr_t)workspace & 15) == 0, "jpeg_decode: workspace must be 16-byte aligned");
-  int16_t* coefs = (int16_t*)workspace;
-  uint8_t* planes = (uint8_t*)workspace + total_blocks * 128;
-  hipStream_t s = (hipStream_t)stream;
+  jpeg_call c = {files, descs, tables, dst, status, workspace, files_bytes, dst_bytes, total_blocks, workspace_bytes,
+                 N, max_blocks, max_pixels, stages, (hipStream_t)stream, nullptr, nullptr};
+  const int rc = jpeg_call_begin("jpeg_decode", &c, n_intervals >= 0, nullptr, intervals != nullptr, 0);
+  if (rc != ASM_OK || N == 0) return rc;
   if (stages & 1) {
-    ASM_LAUNCH(jpeg_entropy_kernel, dim3(N), dim3(64), 0, s, files, files_bytes, descs, tables, intervals, n_intervals,
-               total_blocks, dst_bytes, coefs, status);
+    ASM_LAUNCH(jpeg_entropy_kernel, dim3(N), dim3(64), 0, c.s, files, files_bytes, descs, tables, intervals, n_intervals,
+               total_blocks, dst_bytes, c.coefs, status);
     ASM_CHECK_LAUNCH("jpeg_decode (entropy)");
   }
-  if (stages & 2)
-    return launch_pixel_stages(descs, tables, N, files_bytes, total_blocks, max_blocks, max_pixels, dst, dst_bytes, status,
-                               coefs, planes, s);
-  return ASM_OK;
-}
-
-extern "C" int asm_jpeg_decode_parallel_workspace_bytes(int64_t total_blocks, int64_t total_segments, int64_t* bytes) {
-  ASM_REQUIRE(bytes && total_blocks >= 0 && total_blocks < (1ll << 36) && total_segments >= 0 &&
-                  total_segments < (1ll << 30),
-              "jpeg_decode_parallel_workspace_bytes: bad sizes");
-  *bytes = total_blocks * (64 * 2 + 64) + total_segments * (int64_t)sizeof(jpeg_seg);
-  return ASM_OK;
+  return jpeg_call_finish(c);
 }
 
 extern "C" int asm_jpeg_decode_parallel(const uint8_t* files, int64_t files_bytes, const asm_jpeg_desc* descs,
@@ -458,34 +488,24 @@ extern "C" int asm_jpeg_decode_parallel(const uint8_t* files, int64_t files_byte
                                         int segment_bytes, int64_t total_blocks, int max_blocks, int max_pixels,
                                         uint8_t* dst, int64_t dst_bytes, int32_t* status, int32_t* info, void* workspace,
                                         int64_t workspace_bytes, int stages, void* stream) {
-  ASM_REQUIRE(N >= 0 && n_intervals >= 0 && files_bytes >= 0 && files_bytes < (1ll << 40) && dst_bytes >= 0 &&
-                  total_blocks >= 0 && total_blocks < (1ll << 36) && max_blocks >= 0 && max_pixels >= 0 &&
-                  total_segments >= 0 && total_segments < (1ll << 30),
-              "jpeg_decode_parallel: bad sizes");
-  ASM_REQUIRE(segment_bytes >= 16 && segment_bytes <= 65536 && segment_bytes % 16 == 0,
-              "jpeg_decode_parallel: segment_bytes must be a multiple of 16 in 16..65536");
-  ASM_REQUIRE(stages >= 1 && stages <= 3, "jpeg_decode_parallel: stages must be 1, 2 or 3");
-  ASM_REQUIRE(N <= 65535, "jpeg_decode_parallel: at most 65535 images per call");
-  ASM_REQUIRE(workspace_bytes >= total_blocks * 192 + total_segments * (int64_t)sizeof(jpeg_seg),
-              "jpeg_decode_parallel: workspace too small");
-  if (N == 0) return ASM_OK;
-  ASM_REQUIRE(files && descs && tables && intervals && segment_first && dst && status && workspace,
-              "jpeg_decode_parallel: null pointer");
-  ASM_REQUIRE(((uintptr_t)workspace & 15) == 0, "jpeg_decode_parallel: workspace must be 16-byte aligned");
-  int16_t* coefs = (int16_t*)workspace;
-  uint8_t* planes = (uint8_t*)workspace + total_blocks * 128;
-  jpeg_seg* segs = (jpeg_seg*)((uint8_t*)workspace + total_blocks * 192);      // 16-byte aligned: 192 = 12 * 16
-  hipStream_t s = (hipStream_t)stream;
+  jpeg_call c = {files, descs, tables, dst, status, workspace, files_bytes, dst_bytes, total_blocks, workspace_bytes,
+                 N, max_blocks, max_pixels, stages, (hipStream_t)stream, nullptr, nullptr};
+  const bool segment_ok = segment_bytes >= 16 && segment_bytes <= 65536 && segment_bytes % 16 == 0;
+  const int rc = jpeg_call_begin(
+      "jpeg_decode_parallel", &c,
+      n_intervals >= 0 && files_bytes < (1ll << 40) && total_segments >= 0 && total_segments < (1ll << 30),
+      segment_ok ? nullptr : "segment_bytes must be a multiple of 16 in 16..65536", intervals && segment_first,
+      total_segments * (int64_t)sizeof(jpeg_seg));
+  if (rc != ASM_OK || N == 0) return rc;
+  // the state rows follow the planes; 16-byte aligned: both per-block sizes are multiples of 16
+  jpeg_seg* segs = (jpeg_seg*)((uint8_t*)workspace + jpeg_workspace_bytes(total_blocks));
   if (stages & 1) {
-    ASM_LAUNCH(jpeg_entropy_parallel_kernel, dim3(N), dim3(JPEG_PAR_LANES), 0, s, files, files_bytes, descs, tables,
-               intervals, n_intervals, segment_first, total_segments, segment_bytes, segs, total_blocks, dst_bytes, coefs,
+    ASM_LAUNCH(jpeg_entropy_parallel_kernel, dim3(N), dim3(JPEG_PAR_LANES), 0, c.s, files, files_bytes, descs, tables,
+               intervals, n_intervals, segment_first, total_segments, segment_bytes, segs, total_blocks, dst_bytes, c.coefs,
                status, info);
     ASM_CHECK_LAUNCH("jpeg_decode_parallel (entropy)");
   }
-  if (stages & 2)
-    return launch_pixel_stages(descs, tables, N, files_bytes, total_blocks, max_blocks, max_pixels, dst, dst_bytes, status,
-                               coefs, planes, s);
-  return ASM_OK;
+  return jpeg_call_finish(c);
 }
 
 extern "C" int asm_jpeg_decode_progressive(const uint8_t* files, int64_t files_bytes, const asm_jpeg_desc* descs,
@@ -494,26 +514,15 @@ extern "C" int asm_jpeg_decode_progressive(const uint8_t* files, int64_t files_b
                                            int n_huff, int n_intervals, int64_t total_blocks, int max_blocks, int max_pixels,
                                            uint8_t* dst, int64_t dst_bytes, int32_t* status, void* workspace,
                                            int64_t workspace_bytes, int stages, void* stream) {
-  ASM_REQUIRE(N >= 0 && n_scans >= 0 && n_huff >= 0 && n_intervals >= 0 && files_bytes >= 0 && dst_bytes >= 0 &&
-                  total_blocks >= 0 && total_blocks < (1ll << 36) && max_blocks >= 0 && max_pixels >= 0,
-              "jpeg_decode_progressive: bad sizes");
-  ASM_REQUIRE(stages >= 1 && stages <= 3, "jpeg_decode_progressive: stages must be 1, 2 or 3");
-  ASM_REQUIRE(N <= 65535, "jpeg_decode_progressive: at most 65535 images per call");
-  ASM_REQUIRE(workspace_bytes >= total_blocks * 192, "jpeg_decode_progressive: workspace too small");
-  if (N == 0) return ASM_OK;
-  ASM_REQUIRE(files && descs && tables && scans && huff && intervals && dst && status && workspace,
-              "jpeg_decode_progressive: null pointer");
-  ASM_REQUIRE(((uintptr_t)workspace & 15) == 0, "jpeg_decode_progressive: workspace must be 16-byte aligned");
-  int16_t* coefs = (int16_t*)workspace;
-  uint8_t* planes = (uint8_t*)workspace + total_blocks * 128;
-  hipStream_t s = (hipStream_t)stream;
+  jpeg_call c = {files, descs, tables, dst, status, workspace, files_bytes, dst_bytes, total_blocks, workspace_bytes,
+                 N, max_blocks, max_pixels, stages, (hipStream_t)stream, nullptr, nullptr};
+  const int rc = jpeg_call_begin("jpeg_decode_progressive", &c, n_scans >= 0 && n_huff >= 0 && n_intervals >= 0, nullptr,
+                                 scans && huff && intervals, 0);
+  if (rc != ASM_OK || N == 0) return rc;
   if (stages & 1) {
-    ASM_LAUNCH(jpeg_progressive_kernel, dim3(N), dim3(64), 0, s, files, files_bytes, descs, scans, n_scans, huff, n_huff,
-               intervals, n_intervals, total_blocks, dst_bytes, coefs, status);
+    ASM_LAUNCH(jpeg_progressive_kernel, dim3(N), dim3(64), 0, c.s, files, files_bytes, descs, scans, n_scans, huff, n_huff,
+               intervals, n_intervals, total_blocks, dst_bytes, c.coefs, status);
     ASM_CHECK_LAUNCH("jpeg_decode_progressive (entropy)");
   }
-  if (stages & 2)
-    return launch_pixel_stages(descs, tables, N, files_bytes, total_blocks, max_blocks, max_pixels, dst, dst_bytes, status,
-                               coefs, planes, s);
-  return ASM_OK;
+  return jpeg_call_finish(c);
 }

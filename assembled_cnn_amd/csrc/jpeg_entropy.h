@@ -3,6 +3,8 @@
 // sanitizers): the same text is compiled for both, so what the host program proves about bounds holds for the kernel.
 // The second half of the file does the same for progressive files (T.81 annex G; jpeg_progressive_kernel and
 // tools/probes/jpeg_progressive_host.cpp).
+// What the sequential, the segment-parallel (jpeg_parallel.h) and the progressive decoder decide alike is one function
+// each: jpeg_check_interval (a row of the interval table) and jpeg_decode_dc_diff / jpeg_decode_ac_step (a baseline symbol).
 //
 // Rules: canonical codes of 1..16 bits; a 9-bit lookup, longer codes through maxcode / valoff; EXTEND;
 // one DC predictor per component, zero at the start of the interval; EOB and ZRL; FF 00 -> FF; pad bits ignored.
@@ -172,26 +174,83 @@ JPEG_HD int jpeg_decode_symbol(jpeg_bits* b, const jpeg_dtab* t, int* err) {
   return (int)(e & 255u);
 }
 
-// s bits (1..15; the caller filled at least 32 before the symbol) -> EXTEND(value, s) (T.81 F.2.2.1)
-JPEG_HD int jpeg_receive_extend(jpeg_bits* b, int s, int* err) {
-  b->n -= s;
+// k raw bits (0..16) of those already in buf, first bit first; 0 and *err set if one of them is a pad bit
+JPEG_HD int jpeg_take_bits(jpeg_bits* b, int k, int* err) {
+  b->n -= k;
   if (b->n < b->pad) {
     *err |= ASM_JPEG_EOVERRUN;
     return 0;
   }
-  const int v = (int)((b->buf >> b->n) & ((1u << s) - 1u));
+  return (int)((b->buf >> b->n) & ((1u << k) - 1u));
+}
+
+// s bits (1..15; the caller filled at least 32 before the symbol) -> EXTEND(value, s) (T.81 F.2.2.1); with *err set the
+// value means nothing and every caller drops it
+JPEG_HD int jpeg_receive_extend(jpeg_bits* b, int s, int* err) {
+  const int v = jpeg_take_bits(b, s, err);
   return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
 }
 
-// Decode MCUs [first_mcu, first_mcu + n_mcus) of one image from the bytes [begin, end) into coefs (the image's own region
-// of g.n_coefs int16, already zero).  dc[c] / ac[c]: the tables of component c.  Returns 0 or ASM_JPEG_E*.
+// The baseline symbol step of the sequential, the segment-parallel and (DC half) the progressive decoder: a DC symbol and
+// its EXTEND -> *diff (0 for the symbol 0).  Returns 0 or ASM_JPEG_E*.  What becomes of the predictor is the caller's business.
+JPEG_HD int jpeg_decode_dc_diff(jpeg_bits* b, const jpeg_dtab* t, int* diff) {
+  int err = 0;
+  *diff = 0;
+  const int s = jpeg_decode_symbol(b, t, &err);
+  if (s < 0) return err;
+  if (s > 15) return ASM_JPEG_EBADCODE;
+  if (s) *diff = jpeg_receive_extend(b, s, &err);
+  return err;
+}
+
+// One AC symbol at zig-zag index *k (1..63) of a block: ZRL moves *k on by sixteen, EOB sets it to 64, anything else skips
+// its run, stores EXTEND at the index it reaches (through `out` unless that is null: symbols only) and moves one past it.
+// Returns 0 or ASM_JPEG_E*; an index past 63 is ASM_JPEG_EBADCODE.
+JPEG_HD int jpeg_decode_ac_step(jpeg_bits* b, const jpeg_dtab* t, const uint8_t* zigzag, int* k, int16_t* out) {
+  int err = 0;
+  const int rs = jpeg_decode_symbol(b, t, &err);
+  if (rs < 0) return err;
+  const int run = rs >> 4, s = rs & 15;
+  if (s == 0) {
+    *k = run == 15 ? *k + 16 : 64;
+    return 0;
+  }
+  *k += run;
+  if (*k > 63) return ASM_JPEG_EBADCODE;
+  const int val = jpeg_receive_extend(b, s, &err);
+  if (err) return err;
+  if (out) out[zigzag[*k]] = (int16_t)val;
+  ++*k;
+  return 0;
+}
+
+// Row k of the n_intervals rows of one scan, before a byte of it is read: it must belong to image `img`, lie inside the
+// bytes [range_begin, range_end) (ASM_JPEG_EDESC), name the MCUs and the RSTm that k, restart_interval and the scan's
+// n_mcus_scan MCUs give it (ASM_JPEG_ERESTART), and those MCUs must exist (ASM_JPEG_EDESC) -- in this order.  0: the
+// interval decodes *n_mcus MCUs from *first_mcu.  The one check of the sequential, parallel and progressive decoders.
+JPEG_HD int jpeg_check_interval(const asm_jpeg_interval& iv, int k, int n_intervals, int img, int restart_interval,
+                                int n_mcus_scan, int64_t range_begin, int64_t range_end, int* first_mcu, int* n_mcus) {
+  const int64_t first = restart_interval > 0 ? (int64_t)k * restart_interval : 0;
+  const int64_t left = n_mcus_scan - first;
+  const int64_t count = restart_interval > 0 ? (restart_interval < left ? restart_interval : left) : n_mcus_scan;
+  const bool last = k == n_intervals - 1;
+  *first_mcu = *n_mcus = 0;
+  if (iv.image != img || iv.byte_begin < range_begin || iv.byte_end < iv.byte_begin || iv.byte_end > range_end)
+    return ASM_JPEG_EDESC;
+  if (iv.first_mcu != first || iv.n_mcus != count || iv.rst != (last ? -1 : (k & 7))) return ASM_JPEG_ERESTART;
+  if (first < 0 || count < 1 || first > n_mcus_scan - count) return ASM_JPEG_EDESC;
+  *first_mcu = (int)first;
+  *n_mcus = (int)count;
+  return 0;
+}
+
+// Decode MCUs [first_mcu, first_mcu + n_mcus) (jpeg_check_interval passed them) of one image from the bytes [begin, end)
+// into coefs (the image's own region of g.n_coefs int16, already zero).  dc[c] / ac[c]: component c's.  Returns 0 or ASM_JPEG_E*.
 JPEG_HD int jpeg_decode_interval(const uint8_t* begin, const uint8_t* end, const jpeg_geom& g, const jpeg_dtab* const* dc,
                                  const jpeg_dtab* const* ac, const uint8_t* zigzag, int first_mcu, int n_mcus,
                                  int16_t* coefs) {
-  if (first_mcu < 0 || n_mcus < 1 || first_mcu > g.n_mcus - n_mcus) return ASM_JPEG_EDESC;
   jpeg_bits b;
   jpeg_bits_init(&b, begin, end);
-  int err = 0;
   int pred[3] = {0, 0, 0};
   int my = first_mcu / g.mcus_x, mx = first_mcu - my * g.mcus_x;
   for (int m = 0; m < n_mcus; ++m) {
@@ -200,32 +259,16 @@ JPEG_HD int jpeg_decode_interval(const uint8_t* begin, const uint8_t* end, const
         for (int h = 0; h < g.ch[c]; ++h) {
           const int64_t blk = (int64_t)(my * g.cv[c] + v) * g.bw[c] + (mx * g.ch[c] + h);
           const int64_t at = g.base[c] + blk * 64;
-          if (at < 0 || at + 64 > g.n_coefs) return err | ASM_JPEG_EDESC;
+          if (at < 0 || at + 64 > g.n_coefs) return ASM_JPEG_EDESC;
           int16_t* out = coefs + at;
-          int s = jpeg_decode_symbol(&b, dc[c], &err);
-          if (s < 0) return err;
-          if (s > 15) return err | ASM_JPEG_EBADCODE;
-          if (s) {
-            const int diff = jpeg_receive_extend(&b, s, &err);
-            if (err) return err;
-            pred[c] = (int16_t)(pred[c] + diff);
-          }
+          int diff;
+          int err = jpeg_decode_dc_diff(&b, dc[c], &diff);
+          if (err) return err;
+          pred[c] = (int16_t)(pred[c] + diff);      // a running predictor, stored when it is not the zero already there
           if (pred[c]) out[0] = (int16_t)pred[c];
-          for (int k = 1; k < 64; ++k) {
-            const int rs = jpeg_decode_symbol(&b, ac[c], &err);
-            if (rs < 0) return err;
-            const int r = rs >> 4;
-            s = rs & 15;
-            if (s == 0) {
-              if (r != 15) break;      // EOB
-              k += 15;                 // ZRL: sixteen zeros
-              continue;
-            }
-            k += r;
-            if (k > 63) return err | ASM_JPEG_EBADCODE;
-            const int val = jpeg_receive_extend(&b, s, &err);
+          for (int k = 1; k < 64;) {
+            err = jpeg_decode_ac_step(&b, ac[c], zigzag, &k, out);
             if (err) return err;
-            out[zigzag[k]] = (int16_t)val;
           }
         }
       }
@@ -238,9 +281,9 @@ JPEG_HD int jpeg_decode_interval(const uint8_t* begin, const uint8_t* end, const
   return 0;
 }
 
-// intervals a workgroup expects for the image: one without DRI, else one per restart_interval MCUs
-JPEG_HD int jpeg_expected_intervals(const asm_jpeg_desc& d, const jpeg_geom& g) {
-  return d.restart_interval > 0 ? (int)(((int64_t)g.n_mcus + d.restart_interval - 1) / d.restart_interval) : 1;
+// intervals a workgroup expects for a scan of n_mcus MCUs: one without DRI, else one per restart_interval MCUs
+JPEG_HD int jpeg_expected_intervals(int restart_interval, int n_mcus) {
+  return restart_interval > 0 ? (int)(((int64_t)n_mcus + restart_interval - 1) / restart_interval) : 1;
 }
 
 // What lane `lane` of `lanes` does for image `img`: its share (k = lane, lane + lanes, ...) of the image's rows of the
@@ -254,20 +297,12 @@ JPEG_HD int jpeg_decode_lane(const uint8_t* files, const asm_jpeg_desc& d, const
   int err = 0;
   for (int k = lane; k < d.n_intervals; k += lanes) {
     const asm_jpeg_interval iv = intervals[d.first_interval + k];
-    const int first = d.restart_interval > 0 ? k * d.restart_interval : 0;
-    const int left = g.n_mcus - first;
-    const int count = d.restart_interval > 0 ? (d.restart_interval < left ? d.restart_interval : left) : g.n_mcus;
-    const bool last = k == d.n_intervals - 1;
-    if (iv.image != img || iv.byte_begin < d.scan_offset || iv.byte_end < iv.byte_begin ||
-        iv.byte_end > d.scan_offset + d.scan_bytes) {
-      err |= ASM_JPEG_EDESC;
-      continue;
-    }
-    if (iv.first_mcu != first || iv.n_mcus != count || iv.rst != (last ? -1 : (k & 7))) {
-      err |= ASM_JPEG_ERESTART;
-      continue;
-    }
-    err |= jpeg_decode_interval(files + iv.byte_begin, files + iv.byte_end, g, dc, ac, zigzag, first, count, coefs);
+    int first, count;
+    // the row must lie in the descriptor's scan; a refused row is ORed in and the lane goes on to its next interval
+    const int row_err = jpeg_check_interval(iv, k, d.n_intervals, img, d.restart_interval, g.n_mcus, d.scan_offset,
+                                            d.scan_offset + d.scan_bytes, &first, &count);
+    err |= row_err ? row_err
+                   : jpeg_decode_interval(files + iv.byte_begin, files + iv.byte_end, g, dc, ac, zigzag, first, count, coefs);
   }
   return err;
 }
@@ -286,12 +321,7 @@ JPEG_HD int jpeg_decode_lane(const uint8_t* files, const asm_jpeg_desc& d, const
 // k raw bits (0..16), first bit first
 JPEG_HD int jpeg_receive_bits(jpeg_bits* b, int k, int* err) {
   if (b->n < 32) jpeg_bits_fill(b);
-  b->n -= k;
-  if (b->n < b->pad) {
-    *err |= ASM_JPEG_EOVERRUN;
-    return 0;
-  }
-  return (int)((b->buf >> b->n) & ((1u << k) - 1u));
+  return jpeg_take_bits(b, k, err);
 }
 
 // a scan row as the decoder walks it: its MCU grid and what one MCU holds
@@ -336,10 +366,6 @@ JPEG_HD bool jpeg_make_scan_geom(const asm_jpeg_desc& d, const jpeg_geom& g, con
   return true;
 }
 
-JPEG_HD int jpeg_scan_expected_intervals(const asm_jpeg_scan& sc, const jpeg_scan_geom& s) {
-  return sc.restart_interval > 0 ? (int)(((int64_t)s.n_mcus + sc.restart_interval - 1) / sc.restart_interval) : 1;
-}
-
 // Huffman tables the scan needs: one DC table per component for a DC-first scan, one AC table for an AC scan
 JPEG_HD int jpeg_scan_tables(const asm_jpeg_scan& sc) {
   if (sc.ss > 0) return 1;
@@ -360,20 +386,15 @@ JPEG_HD int jpeg_check_scan(const asm_jpeg_desc& d, const jpeg_geom& g, const as
   for (int i = 0; i < n_tab; ++i) {
     if (sc.huff[i] < 0 || sc.huff[i] >= n_huff) return ASM_JPEG_EDESC;
   }
-  return sc.n_intervals == jpeg_scan_expected_intervals(sc, *s) ? 0 : ASM_JPEG_ERESTART;
+  return sc.n_intervals == jpeg_expected_intervals(sc.restart_interval, s->n_mcus) ? 0 : ASM_JPEG_ERESTART;
 }
 
 // DC first: pred += EXTEND; coef[0] = pred * 2^al
 JPEG_HD int jpeg_prog_dc_first(jpeg_bits* b, const jpeg_dtab* t, int al, int* pred, int16_t* out) {
-  int err = 0;
-  const int s = jpeg_decode_symbol(b, t, &err);
-  if (s < 0) return err;
-  if (s > 15) return ASM_JPEG_EBADCODE;
-  if (s) {
-    const int diff = jpeg_receive_extend(b, s, &err);
-    if (err) return err;
-    *pred = (int16_t)(*pred + diff);
-  }
+  int diff;
+  const int err = jpeg_decode_dc_diff(b, t, &diff);
+  if (err) return err;
+  *pred = (int16_t)(*pred + diff);
   out[0] = (int16_t)(*pred * (1 << al));
   return 0;
 }
@@ -478,12 +499,11 @@ JPEG_HD int jpeg_prog_ac_refine(jpeg_bits* b, const jpeg_dtab* t, const uint8_t*
   return 0;
 }
 
-// Decode MCUs [first_mcu, first_mcu + n_mcus) of one scan from the bytes [begin, end) into coefs (the image's own region
-// of g.n_coefs int16).  tab[i]: the table of scan component i (DC-first) or tab[0] (AC); unused for a DC refinement.
+// Decode MCUs [first_mcu, first_mcu + n_mcus) (jpeg_check_interval passed them) of one scan from the bytes [begin, end)
+// into coefs (the image's g.n_coefs int16).  tab[i]: scan component i's table (DC-first) or tab[0] (AC); none for a DC refinement.
 JPEG_HD int jpeg_prog_decode_interval(const uint8_t* begin, const uint8_t* end, const jpeg_geom& g, const jpeg_scan_geom& s,
                                       const jpeg_dtab* tab, const uint8_t* zigzag, int first_mcu, int n_mcus,
                                       int16_t* coefs) {
-  if (first_mcu < 0 || n_mcus < 1 || first_mcu > s.n_mcus - n_mcus) return ASM_JPEG_EDESC;
   jpeg_bits b;
   jpeg_bits_init(&b, begin, end);
   int pred[3] = {0, 0, 0};
@@ -528,18 +548,11 @@ JPEG_HD int jpeg_prog_decode_lane(const uint8_t* files, const jpeg_geom& g, cons
   int err = 0;
   for (int k = lane; k < sc.n_intervals && !err; k += lanes) {
     const asm_jpeg_interval iv = intervals[sc.first_interval + k];
-    const int64_t first = sc.restart_interval > 0 ? (int64_t)k * sc.restart_interval : 0;
-    const int64_t left = s.n_mcus - first;
-    const int64_t count = sc.restart_interval > 0 ? (sc.restart_interval < left ? sc.restart_interval : left) : s.n_mcus;
-    const bool last = k == sc.n_intervals - 1;
-    if (iv.image != img || iv.byte_begin < sc.byte_begin || iv.byte_end < iv.byte_begin || iv.byte_end > sc.byte_end) {
-      err |= ASM_JPEG_EDESC;
-    } else if (iv.first_mcu != first || iv.n_mcus != count || iv.rst != (last ? -1 : (k & 7))) {
-      err |= ASM_JPEG_ERESTART;
-    } else {
-      err |= jpeg_prog_decode_interval(files + iv.byte_begin, files + iv.byte_end, g, s, tab, zigzag, (int)first, (int)count,
-                                       coefs);
-    }
+    int first, count;
+    // the row must lie in its scan row's bytes; the lane stops at its first error (the loop's condition)
+    err = jpeg_check_interval(iv, k, sc.n_intervals, img, sc.restart_interval, s.n_mcus, sc.byte_begin, sc.byte_end, &first,
+                              &count);
+    if (!err) err = jpeg_prog_decode_interval(files + iv.byte_begin, files + iv.byte_end, g, s, tab, zigzag, first, count, coefs);
   }
   return err;
 }

@@ -13,7 +13,8 @@
 //
 // Phases of one image (every lane-function is followed by a workgroup barrier):
 //   jpeg_par_check_table   the image's rows of the segment table against the sizes of the call
-//   jpeg_par_init          one state row per segment: the true entry for the first of an interval, a guess for the others
+//   jpeg_par_init          one state row per segment: the true entry for the first of an interval, a guess for the others;
+//                          the interval's row is judged by jpeg_check_interval, the sequential decoder's own check
 //   jpeg_par_decode /      a round: every segment whose entry changed is decoded from it, symbols only, up to the first
 //   jpeg_par_publish       symbol that starts at or after its end (exit state + blocks started); then every exit that is
 //                          no error and differs from the next entry replaces it.  Repeat until nothing was published.
@@ -22,6 +23,7 @@
 //   jpeg_par_write         every valid segment once more, storing AC coefficients and DC differences; only this ORs errors
 //   jpeg_par_dc_sum /      DC values: per-component prefix sums over contiguous MCU runs, restarted at interval starts
 //   jpeg_par_dc_apply
+// Symbols are decoded by jpeg_decode_dc_diff / jpeg_decode_ac_step, the sequential decoder's own step: the status words agree.
 // Safety: the rules of jpeg_entropy.h.  Bytes are read inside the interval's range only, every block ordinal becomes an
 // address through jpeg_par_block_at (checked against the geometry), every loop consumes a bit per iteration or ends.
 // The state rows are untrusted (jpeg_par_segment_range): whatever they hold, every table index is bounded by the
@@ -65,27 +67,27 @@ struct jpeg_par_ctx {
   int16_t* coefs;
 };
 
+// everything of the context but the descriptor and the geometry (filled first: bpm reads them) and the state rows, which
+// are set once jpeg_par_check_table has passed
+JPEG_HD void jpeg_par_ctx_fill(jpeg_par_ctx* c, const uint8_t* files, const asm_jpeg_interval* intervals, const int32_t* seg_first,
+                               int img, int segment_bytes, const jpeg_dtab* tab, const uint8_t* zigzag, int16_t* coefs) {
+  c->files = files;
+  c->bpm = c->d.ncomp == 1 ? 1 : c->d.hs * c->d.vs + 2;
+  c->intervals = intervals;
+  c->seg_first = seg_first;
+  c->img = img;
+  c->segment_bytes = segment_bytes;
+  c->tab = tab;
+  c->zigzag = zigzag;
+  c->coefs = coefs;
+  c->segs = nullptr;
+  c->n_segs = 0;
+}
+
 // segments of an interval row: ceil(bytes / segment_bytes), at least one
 JPEG_HD int64_t jpeg_par_interval_segments(const asm_jpeg_interval& iv, int segment_bytes) {
   const int64_t bytes = iv.byte_end - iv.byte_begin;
   return bytes > segment_bytes ? (bytes + segment_bytes - 1) / segment_bytes : 1;
-}
-
-// interval row k of the image against the descriptor, as jpeg_decode_lane checks it: 0 or ASM_JPEG_EDESC / ERESTART
-JPEG_HD int jpeg_par_check_interval(const jpeg_par_ctx& c, int k, const asm_jpeg_interval& iv, int* first_mcu, int* n_mcus) {
-  const asm_jpeg_desc& d = c.d;
-  const int first = d.restart_interval > 0 ? k * d.restart_interval : 0;
-  const int left = c.g.n_mcus - first;
-  const int count = d.restart_interval > 0 ? (d.restart_interval < left ? d.restart_interval : left) : c.g.n_mcus;
-  const bool last = k == d.n_intervals - 1;
-  *first_mcu = first;
-  *n_mcus = count;
-  if (iv.image != c.img || iv.byte_begin < d.scan_offset || iv.byte_end < iv.byte_begin ||
-      iv.byte_end > d.scan_offset + d.scan_bytes)
-    return ASM_JPEG_EDESC;
-  if (iv.first_mcu != first || iv.n_mcus != count || iv.rst != (last ? -1 : (k & 7))) return ASM_JPEG_ERESTART;
-  if (first < 0 || count < 1 || first > c.g.n_mcus - count) return ASM_JPEG_EDESC;
-  return 0;
 }
 
 // The image's rows of the segment table: row k names the first state row of interval k, the rows of one image follow
@@ -109,14 +111,16 @@ JPEG_HD int jpeg_par_segments(const jpeg_par_ctx& c) {
 // State row `row` (a copy) of segment s, judged before anything it names is used.  The state region is NOT trusted: a
 // segment table in which two images share rows lets another workgroup write into this image's rows at any time, so a
 // row's interval index, flags and states are data like the file's bytes.  false: the row names no interval of this
-// image, its interval's row of the interval table is refused (jpeg_par_check_interval), or s is no segment of that
+// image, its interval's row of the interval table is refused (jpeg_check_interval), or s is no segment of that
 // interval.  Else *iv is the checked interval row, [iv->byte_begin, *end) what the segment may cover (*end is the
 // segment's end, the interval's for its last segment, *last), *first_mcu / *n_mcus the interval's MCUs.
 JPEG_HD bool jpeg_par_segment_range(const jpeg_par_ctx& c, int s, const jpeg_seg& row, asm_jpeg_interval* iv, int64_t* end,
                                     bool* last, int* first_mcu, int* n_mcus) {
   if (row.interval < 0 || row.interval >= c.d.n_intervals) return false;
   *iv = c.intervals[row.interval];
-  if (jpeg_par_check_interval(c, row.interval, *iv, first_mcu, n_mcus)) return false;
+  if (jpeg_check_interval(*iv, row.interval, c.d.n_intervals, c.img, c.d.restart_interval, c.g.n_mcus, c.d.scan_offset,
+                          c.d.scan_offset + c.d.scan_bytes, first_mcu, n_mcus))
+    return false;
   const int64_t j = s - (int64_t)(c.seg_first[row.interval] - c.seg_first[0]);
   const int64_t n = jpeg_par_interval_segments(*iv, c.segment_bytes);
   if (j < 0 || j >= n) return false;
@@ -140,7 +144,9 @@ JPEG_HD int jpeg_par_init(const jpeg_par_ctx& c, int lane, int lanes) {
     const asm_jpeg_interval iv = c.intervals[lo];
     const int64_t j = want - c.seg_first[lo], n = jpeg_par_interval_segments(iv, c.segment_bytes);
     int first_mcu, n_mcus;
-    const int row_err = jpeg_par_check_interval(c, lo, iv, &first_mcu, &n_mcus);
+    // the row against the descriptor's scan, as jpeg_decode_lane judges it
+    const int row_err = jpeg_check_interval(iv, lo, c.d.n_intervals, c.img, c.d.restart_interval, c.g.n_mcus, c.d.scan_offset,
+                                            c.d.scan_offset + c.d.scan_bytes, &first_mcu, &n_mcus);
     jpeg_seg row;
     row.interval = lo;
     row.count = 0;
@@ -148,7 +154,7 @@ JPEG_HD int jpeg_par_init(const jpeg_par_ctx& c, int lane, int lanes) {
     row.exit = JPEG_SEG_NOEXIT;
     row.flags = (j == 0 ? JPEG_SEG_FIRST : 0) | (j == n - 1 ? JPEG_SEG_LAST : 0);
     row.entry = 0;
-    if (row_err) {
+    if (row_err) {      // a refused row is ORed in and its segments are marked dead: never decoded
       err |= row_err;
       row.flags |= JPEG_SEG_DEAD;
     } else {
@@ -263,7 +269,7 @@ JPEG_HD int jpeg_par_decode_segment(const jpeg_par_ctx& c, int64_t iv_begin, int
     out = coefs + at;
   }
   const uint8_t* seg_stop = c.files + seg_end;
-  int err = 0, n = 0;
+  int n = 0;
   for (;;) {
     if (r.b.n < 32) jpeg_pbits_fill(&r);
     if (bounded && jpeg_pbits_next(&r) >= seg_stop && jpeg_pbits_pos(&r, c.files) >= seg_end * 8) break;
@@ -276,31 +282,15 @@ JPEG_HD int jpeg_par_decode_segment(const jpeg_par_ctx& c, int64_t iv_begin, int
       } else {
         comp = blk < n0 ? 0 : blk - n0 + 1;
       }
-      const int s = jpeg_decode_symbol(&r.b, dc[comp], &err);
-      if (s < 0) return err;
-      if (s > 15) return err | ASM_JPEG_EBADCODE;
-      int diff = 0;
-      if (s) {
-        diff = jpeg_receive_extend(&r.b, s, &err);
-        if (err) return err;
-      }
-      if (out) out[0] = (int16_t)diff;
+      int diff;
+      const int err = jpeg_decode_dc_diff(&r.b, dc[comp], &diff);
+      if (err) return err;
+      if (out) out[0] = (int16_t)diff;      // the difference: jpeg_par_dc_* turn it into the value
       ++n;
       k = 1;
     } else {
-      const int rs = jpeg_decode_symbol(&r.b, ac[comp], &err);
-      if (rs < 0) return err;
-      const int run = rs >> 4, s = rs & 15;
-      if (s == 0) {
-        k = run == 15 ? k + 16 : 64;       // ZRL: sixteen zeros; EOB
-      } else {
-        k += run;
-        if (k > 63) return err | ASM_JPEG_EBADCODE;
-        const int val = jpeg_receive_extend(&r.b, s, &err);
-        if (err) return err;
-        if (out) out[c.zigzag[k]] = (int16_t)val;
-        ++k;
-      }
+      const int err = jpeg_decode_ac_step(&r.b, ac[comp], c.zigzag, &k, out);
+      if (err) return err;
     }
     if (k >= 64) {
       k = 0;

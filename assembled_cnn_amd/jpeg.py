@@ -436,31 +436,86 @@ def _interval_rows(image, intervals, rst, restart_interval, n_mcus, byte_shift) 
   return iv
 
 
-def _pack_progressive(pk: Packed, infos, arrays):
-  """The progressive rows' tables: per image one descriptor (its first_interval / n_intervals name its rows of the scan
-  table), per scan one row, one pool entry per Huffman table a scan reads, and the scans' interval rows."""
-  nd = len(pk.prog_index)
-  pk.prog_descs = np.zeros(nd, DESC_DTYPE)
-  pk.prog_tables = np.zeros(nd, TABLES_DTYPE)
-  bytes_at, blocks_at, n_scans, n_iv = 0, 0, 0, 0
-  chunks, scan_rows, huffs, iv_rows = [], [], [], []
-  for row, k in enumerate(pk.prog_index):
-    info, a = infos[k], arrays[k]
-    first, last = info.scans[0].begin, info.scans[-1].end
-    body = a[first:last]        # every scan of the image, the marker segments between them included
-    chunks.append((bytes_at, body))
-    shift = bytes_at - first
-    d = pk.prog_descs[row]
-    d['scan_offset'], d['scan_bytes'] = bytes_at, body.size
+def _byte_pool(chunks):
+  """(one zeroed uint8 array of at least 16 bytes holding the chunks at 16-byte-aligned offsets, those offsets)"""
+  sizes = [(c.size + 15) // 16 * 16 for c in chunks]
+  offsets = [int(o) for o in np.cumsum([0] + sizes)]
+  pool = np.zeros(max(offsets[-1], 16), np.uint8)
+  for o, c in zip(offsets, chunks):
+    pool[o:o + c.size] = c
+  return pool, offsets[:-1]
+
+
+def _fill_rows(pk: Packed, index, infos, bodies):
+  """What a sequential and a progressive group fill alike for its images `index` (batch indices in row order, their bytes
+  in `bodies`): the byte pool and, per row, the offsets into it, into coefficients, planes and dst, the geometry, qsel and
+  the quantisation tables.  Returns (descs, tables, pool, each body's offset in it, total_blocks, max_blocks, max_pixels)."""
+  descs = np.zeros(len(index), DESC_DTYPE)
+  tables = np.zeros(len(index), TABLES_DTYPE)
+  pool, offsets = _byte_pool(bodies)
+  blocks_at = max_blocks = max_pixels = 0
+  for row, k in enumerate(index):
+    info, d = infos[k], descs[row]
+    d['scan_offset'], d['scan_bytes'] = offsets[row], bodies[row].size
     d['coef_offset'] = d['plane_offset'] = blocks_at * 64
     d['dst_offset'] = pk.offsets[k]
     d['width'], d['height'], d['ncomp'] = info.width, info.height, info.ncomp
     d['hs'], d['vs'], d['mcus_x'], d['mcus_y'] = info.hs, info.vs, info.mcus_x, info.mcus_y
-    d['first_interval'], d['n_intervals'] = n_scans, len(info.scans)
     for c, (_, _, _, tq) in enumerate(info.components):
       d['qsel'][c] = tq
     for tq, q in info.qtables.items():
-      pk.prog_tables[row]['quant'][tq] = q
+      tables[row]['quant'][tq] = q
+    blocks_at += info.n_blocks
+    max_blocks = max(max_blocks, info.n_blocks)
+    max_pixels = max(max_pixels, info.width * info.height)
+  return descs, tables, pool, offsets, blocks_at, max_blocks, max_pixels
+
+
+def _pack_sequential(pk: Packed, infos, arrays):
+  """The sequential rows' tables: per image one descriptor, its (at most two per class) Huffman tables and its rows of
+  the interval table; with pk.segment_bytes also the segment table of asm_jpeg_decode_parallel."""
+  bodies = [arrays[k][infos[k].scan_begin:infos[k].scan_end] for k in pk.dev_index]
+  (pk.descs, pk.tables, pk.files, offsets, pk.total_blocks, pk.max_blocks,
+   pk.max_pixels) = _fill_rows(pk, pk.dev_index, infos, bodies)
+  n_iv, iv_rows = 0, []
+  for row, k in enumerate(pk.dev_index):
+    info, d, t = infos[k], pk.descs[row], pk.tables[row]
+    d['restart_interval'] = info.restart_interval
+    d['first_interval'], d['n_intervals'] = n_iv, len(info.intervals)
+    # Huffman slots: the (at most two) tables of each class the scan names, in order of first use
+    dc_ids, ac_ids = [], []
+    for c, (_, td, ta) in enumerate(info.scan_components):
+      if td not in dc_ids:
+        dc_ids.append(td)
+      if ta not in ac_ids:
+        ac_ids.append(ta)
+      d['dcsel'][c], d['acsel'][c] = dc_ids.index(td), ac_ids.index(ta)
+    for cls, name, ids in ((0, 'dc', dc_ids), (1, 'ac', ac_ids)):
+      for slot, th in enumerate(ids):
+        bits, vals = info.huffman[(cls, th)]
+        t[name][slot]['bits'] = bits
+        t[name][slot]['vals'][:vals.size] = vals
+    iv_rows.append(_interval_rows(row, info.intervals, info.rst, info.restart_interval, info.n_mcus,
+                                  offsets[row] - info.scan_begin))
+    n_iv += len(info.intervals)
+  pk.intervals = np.concatenate(iv_rows) if iv_rows else np.zeros(0, INTERVAL_DTYPE)
+  if pk.segment_bytes is not None:
+    pk.segment_first, pk.total_segments = segment_table(pk.intervals, pk.segment_bytes)
+
+
+def _pack_progressive(pk: Packed, infos, arrays):
+  """The progressive rows' tables: per image one descriptor (its first_interval / n_intervals name its rows of the scan
+  table), per scan one row, one pool entry per Huffman table a scan reads, and the scans' interval rows."""
+  # every scan of the image, the marker segments between them included
+  bodies = [arrays[k][infos[k].scans[0].begin:infos[k].scans[-1].end] for k in pk.prog_index]
+  (pk.prog_descs, pk.prog_tables, pk.prog_files, offsets, pk.prog_total_blocks, pk.prog_max_blocks,
+   pk.prog_max_pixels) = _fill_rows(pk, pk.prog_index, infos, bodies)
+  n_scans, n_iv = 0, 0
+  scan_rows, huffs, iv_rows = [], [], []
+  for row, k in enumerate(pk.prog_index):
+    info = infos[k]
+    shift = offsets[row] - info.scans[0].begin
+    pk.prog_descs[row]['first_interval'], pk.prog_descs[row]['n_intervals'] = n_scans, len(info.scans)
     rows = np.zeros(len(info.scans), SCAN_DTYPE)
     for j, sc in enumerate(info.scans):
       r = rows[j]
@@ -483,17 +538,9 @@ def _pack_progressive(pk: Packed, infos, arrays):
       n_iv += len(sc.intervals)
     scan_rows.append(rows)
     n_scans += len(rows)
-    bytes_at += (body.size + 15) // 16 * 16
-    blocks_at += info.n_blocks
-    pk.prog_max_blocks = max(pk.prog_max_blocks, info.n_blocks)
-    pk.prog_max_pixels = max(pk.prog_max_pixels, info.width * info.height)
-  pk.prog_files = np.zeros(max(bytes_at, 16), np.uint8)
-  for o, body in chunks:
-    pk.prog_files[o:o + body.size] = body
   pk.prog_scans = np.concatenate(scan_rows) if scan_rows else np.zeros(0, SCAN_DTYPE)
   pk.prog_huff = np.array(huffs, HUFF_DTYPE) if huffs else np.zeros(0, HUFF_DTYPE)
   pk.prog_intervals = np.concatenate(iv_rows) if iv_rows else np.zeros(0, INTERVAL_DTYPE)
-  pk.prog_total_blocks = blocks_at
 
 
 def check_segment_bytes(segment_bytes: int) -> int:
@@ -540,9 +587,6 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
     else:
       arrays[k] = _as_array(f)
       (pk.prog_index if info.progressive else pk.dev_index).append(k)
-  nd = len(pk.dev_index)
-  pk.descs = np.zeros(nd, DESC_DTYPE)
-  pk.tables = np.zeros(nd, TABLES_DTYPE)
   # output slots, 16-byte aligned (the src layout of asm_resize_crop_flip): the device-decoded entries first (sequential
   # rows, then progressive rows), then the already decoded ones back to back, so that those travel in one host-to-device
   # copy
@@ -551,49 +595,7 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
   pk.offsets, total = slot_layout([h * w * 3 for h, w in pk.sizes], pk.dev_index + pk.prog_index + hosted)
   pk.host_begin = int(pk.offsets[hosted[0]]) if hosted else total
   pk.total_bytes = max(total, 16)
-  scan_at, blocks_at, rows = 0, 0, []
-  chunks = []
-  for row, k in enumerate(pk.dev_index):
-    info, a = infos[k], arrays[k]
-    d = pk.descs[row]
-    scan = a[info.scan_begin:info.scan_end]
-    chunks.append((scan_at, scan))
-    d['scan_offset'], d['scan_bytes'] = scan_at, scan.size
-    d['coef_offset'] = d['plane_offset'] = blocks_at * 64
-    d['dst_offset'] = pk.offsets[k]
-    d['width'], d['height'], d['ncomp'] = info.width, info.height, info.ncomp
-    d['hs'], d['vs'], d['mcus_x'], d['mcus_y'] = info.hs, info.vs, info.mcus_x, info.mcus_y
-    d['restart_interval'] = info.restart_interval
-    d['first_interval'], d['n_intervals'] = sum(r.size for r in rows), len(info.intervals)
-    # Huffman slots: the (at most two) tables of each class the scan names, in order of first use
-    dc_ids, ac_ids = [], []
-    for c, ((_, _, _, tq), (_, td, ta)) in enumerate(zip(info.components, info.scan_components)):
-      if td not in dc_ids:
-        dc_ids.append(td)
-      if ta not in ac_ids:
-        ac_ids.append(ta)
-      d['qsel'][c], d['dcsel'][c], d['acsel'][c] = tq, dc_ids.index(td), ac_ids.index(ta)
-    t = pk.tables[row]
-    for tq, q in info.qtables.items():
-      t['quant'][tq] = q
-    for cls, name, ids in ((0, 'dc', dc_ids), (1, 'ac', ac_ids)):
-      for slot, th in enumerate(ids):
-        bits, vals = info.huffman[(cls, th)]
-        t[name][slot]['bits'] = bits
-        t[name][slot]['vals'][:vals.size] = vals
-    iv = _interval_rows(row, info.intervals, info.rst, info.restart_interval, info.n_mcus, scan_at - info.scan_begin)
-    rows.append(iv)
-    scan_at += (scan.size + 15) // 16 * 16
-    blocks_at += info.n_blocks
-    pk.max_blocks = max(pk.max_blocks, info.n_blocks)
-    pk.max_pixels = max(pk.max_pixels, info.width * info.height)
-  pk.files = np.zeros(max(scan_at, 16), np.uint8)
-  for o, scan in chunks:
-    pk.files[o:o + scan.size] = scan
-  pk.intervals = np.concatenate(rows) if rows else np.zeros(0, INTERVAL_DTYPE)
-  pk.total_blocks = blocks_at
-  if pk.segment_bytes is not None:
-    pk.segment_first, pk.total_segments = segment_table(pk.intervals, pk.segment_bytes)
+  _pack_sequential(pk, infos, arrays)
   if pk.prog_index:
     _pack_progressive(pk, infos, arrays)
   return pk

@@ -959,6 +959,23 @@ def autoaugment(images_f32, descs_dev, subtract_mean):
   return out
 
 
+def _jpeg_begin(name, counts, descs_dev, tables_dev, rows, dst, workspace_fn, *workspace_args):
+  """What the three JPEG wrappers do first.  counts: the call's counts by name, n first, in the order of the error text;
+  rows: (device table, bytes per row, name of its count) beside the n descriptors and n asm_jpeg_tables.  Returns (int32
+  [n] device status, workspace); for n = 0 the workspace is None and the library is not called.  workspace_fn /
+  workspace_args: the library's *_workspace_bytes (without asm_) and its arguments."""
+  rows = ((descs_dev, C.sizeof(_lib.JpegDesc), 'n'), (tables_dev, C.sizeof(_lib.JpegTables), 'n')) + rows
+  if any(t.numel() * t.element_size() != size * counts[c] for t, size, c in rows):
+    raise ValueError('%s: table sizes do not match %s' % (name, ', '.join('%s = %d' % kv for kv in counts.items())))
+  n = counts['n']
+  status = torch.empty((max(n, 1),), dtype=torch.int32, device=dst.device)[:n]
+  if n == 0:
+    return status, None
+  need = C.c_int64(0)
+  check(getattr(L(), 'asm_' + workspace_fn)(*workspace_args, C.byref(need)), workspace_fn)
+  return status, _workspace(max(need.value, 16), dst)
+
+
 def jpeg_decode(files_u8, descs_dev, tables_dev, intervals_dev, n, n_intervals, total_blocks, max_blocks, max_pixels, dst,
                 stages=3):
   """asm_jpeg_decode for a batch packed by jpeg.pack: uint8 device views of the entropy-coded bytes, n struct asm_jpeg_desc,
@@ -966,18 +983,13 @@ def jpeg_decode(files_u8, descs_dev, tables_dev, intervals_dev, n, n_intervals, 
   written into.  Three launches, no synchronisation.  Returns (int32 [n] device status, one word of JPEG_E* bits per image;
   workspace: the uint8 device buffer with the int16 coefficients [total_blocks][64] first, then the planes; None for n = 0).
   jpeg.decode_packed reads the status and raises for corrupt entropy-coded data."""
-  if (descs_dev.numel() != C.sizeof(_lib.JpegDesc) * n or tables_dev.numel() != C.sizeof(_lib.JpegTables) * n or
-      intervals_dev.numel() != C.sizeof(_lib.JpegInterval) * n_intervals):
-    raise ValueError('jpeg_decode: table sizes do not match n = %d, n_intervals = %d' % (n, n_intervals))
-  status = torch.empty((max(n, 1),), dtype=torch.int32, device=dst.device)[:n]
-  if n == 0:
-    return status, None
-  need = C.c_int64(0)
-  check(L().asm_jpeg_decode_workspace_bytes(total_blocks, C.byref(need)), 'jpeg_decode_workspace_bytes')
-  ws = _workspace(max(need.value, 16), dst)
-  check(L().asm_jpeg_decode(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev), _ptr(intervals_dev), n,
-                            n_intervals, total_blocks, max_blocks, max_pixels, _ptr(dst), dst.numel(), _ptr(status),
-                            _ptr(ws), ws.numel(), stages, _stream()), 'jpeg_decode')
+  rows = ((intervals_dev, C.sizeof(_lib.JpegInterval), 'n_intervals'),)
+  status, ws = _jpeg_begin('jpeg_decode', dict(n=n, n_intervals=n_intervals), descs_dev, tables_dev, rows, dst,
+                           'jpeg_decode_workspace_bytes', total_blocks)
+  if n:
+    check(L().asm_jpeg_decode(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev), _ptr(intervals_dev), n,
+                              n_intervals, total_blocks, max_blocks, max_pixels, _ptr(dst), dst.numel(), _ptr(status),
+                              _ptr(ws), ws.numel(), stages, _stream()), 'jpeg_decode')
   return status, ws
 
 
@@ -986,20 +998,16 @@ def jpeg_decode_parallel(files_u8, descs_dev, tables_dev, intervals_dev, segment
   """asm_jpeg_decode_parallel for a batch packed by jpeg.pack(segment_bytes=...): jpeg_decode's tables plus the int32
   device table of each interval's first segment.  Same return values as jpeg_decode (the workspace's state rows follow
   the planes), plus, with info, an int32 [n, 2] device tensor: segments and rounds per image."""
-  if (descs_dev.numel() != C.sizeof(_lib.JpegDesc) * n or tables_dev.numel() != C.sizeof(_lib.JpegTables) * n or
-      intervals_dev.numel() != C.sizeof(_lib.JpegInterval) * n_intervals or
-      segment_first_dev.numel() * segment_first_dev.element_size() != 4 * n_intervals):
-    raise ValueError('jpeg_decode_parallel: table sizes do not match n = %d, n_intervals = %d' % (n, n_intervals))
-  status = torch.empty((max(n, 1),), dtype=torch.int32, device=dst.device)[:n]
+  rows = ((intervals_dev, C.sizeof(_lib.JpegInterval), 'n_intervals'), (segment_first_dev, 4, 'n_intervals'))
+  status, ws = _jpeg_begin('jpeg_decode_parallel', dict(n=n, n_intervals=n_intervals), descs_dev, tables_dev, rows, dst,
+                           'jpeg_decode_parallel_workspace_bytes', total_blocks, total_segments)
   info_dev = torch.zeros((max(n, 1), 2), dtype=torch.int32, device=dst.device)[:n] if info else None
-  need = C.c_int64(0)
-  check(L().asm_jpeg_decode_parallel_workspace_bytes(total_blocks, total_segments, C.byref(need)),
-        'jpeg_decode_parallel_workspace_bytes')
-  ws = _workspace(max(need.value, 16), dst) if n else None
-  check(L().asm_jpeg_decode_parallel(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev), _ptr(intervals_dev),
-                                     _ptr(segment_first_dev), n, n_intervals, total_segments, segment_bytes, total_blocks,
-                                     max_blocks, max_pixels, _ptr(dst), dst.numel(), _ptr(status),
-                                     _ptr(info_dev), _ptr(ws), need.value, stages, _stream()), 'jpeg_decode_parallel')
+  if n:
+    check(L().asm_jpeg_decode_parallel(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev),
+                                       _ptr(intervals_dev), _ptr(segment_first_dev), n, n_intervals, total_segments,
+                                       segment_bytes, total_blocks, max_blocks, max_pixels, _ptr(dst), dst.numel(),
+                                       _ptr(status), _ptr(info_dev), _ptr(ws), ws.numel(), stages, _stream()),
+          'jpeg_decode_parallel')
   return (status, ws, info_dev) if info else (status, ws)
 
 
@@ -1007,21 +1015,15 @@ def jpeg_decode_progressive(files_u8, descs_dev, tables_dev, scans_dev, huff_dev
                             n_intervals, total_blocks, max_blocks, max_pixels, dst, stages=3):
   """asm_jpeg_decode_progressive for the progressive rows packed by jpeg.pack(progressive=True): as jpeg_decode, with
   n_scans struct asm_jpeg_scan and a pool of n_huff struct asm_jpeg_huff beside the descriptors.  Same return values."""
-  if (descs_dev.numel() != C.sizeof(_lib.JpegDesc) * n or tables_dev.numel() != C.sizeof(_lib.JpegTables) * n or
-      scans_dev.numel() != C.sizeof(_lib.JpegScan) * n_scans or huff_dev.numel() != C.sizeof(_lib.JpegHuff) * n_huff or
-      intervals_dev.numel() != C.sizeof(_lib.JpegInterval) * n_intervals):
-    raise ValueError('jpeg_decode_progressive: table sizes do not match n = %d, n_scans = %d, n_huff = %d, n_intervals = %d'
-                     % (n, n_scans, n_huff, n_intervals))
-  status = torch.empty((max(n, 1),), dtype=torch.int32, device=dst.device)[:n]
-  if n == 0:
-    return status, None
-  need = C.c_int64(0)
-  check(L().asm_jpeg_decode_workspace_bytes(total_blocks, C.byref(need)), 'jpeg_decode_workspace_bytes')
-  ws = _workspace(max(need.value, 16), dst)
-  check(L().asm_jpeg_decode_progressive(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev), _ptr(scans_dev),
-                                        _ptr(huff_dev), _ptr(intervals_dev), n, n_scans, n_huff, n_intervals, total_blocks,
-                                        max_blocks, max_pixels, _ptr(dst), dst.numel(), _ptr(status), _ptr(ws), ws.numel(),
-                                        stages, _stream()), 'jpeg_decode_progressive')
+  rows = ((scans_dev, C.sizeof(_lib.JpegScan), 'n_scans'), (huff_dev, C.sizeof(_lib.JpegHuff), 'n_huff'),
+          (intervals_dev, C.sizeof(_lib.JpegInterval), 'n_intervals'))
+  status, ws = _jpeg_begin('jpeg_decode_progressive', dict(n=n, n_scans=n_scans, n_huff=n_huff, n_intervals=n_intervals),
+                           descs_dev, tables_dev, rows, dst, 'jpeg_decode_workspace_bytes', total_blocks)
+  if n:
+    check(L().asm_jpeg_decode_progressive(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev),
+                                          _ptr(scans_dev), _ptr(huff_dev), _ptr(intervals_dev), n, n_scans, n_huff,
+                                          n_intervals, total_blocks, max_blocks, max_pixels, _ptr(dst), dst.numel(),
+                                          _ptr(status), _ptr(ws), ws.numel(), stages, _stream()), 'jpeg_decode_progressive')
   return status, ws
 
 

@@ -156,16 +156,19 @@ def test_corrupt_scans_give_a_status_zero_pixels_and_a_value_error(product):
     jpeg.decode_batch(files, 'cuda')
 
 
-def test_damaged_tables_take_the_status_paths(product):
+@pytest.mark.parametrize('entropy', ['sequential', 'parallel'])
+def test_damaged_tables_take_the_status_paths(product, entropy):
   """Damage done AFTER packing, so that it reaches the device as it is (the host parser would end the scan at a marker):
   a marker inside an interval, a restart marker out of sequence, an interval count that does not match the geometry, an
   interval row outside the image's scan, a descriptor with an impossible geometry.  Each ends its image with the status
   bit of its kind and zero pixels; the untouched images of the same launch decode.  The damaged scans are among those the
-  host sanitizer program runs (a byte replaced by FF)."""
+  host sanitizer programs run (a byte replaced by FF; the damaged rows of tools/probes/jpeg_probe.h).
+  entropy='parallel': the same pack in segments of 16 bytes, the segment table made from the damaged rows so that they
+  reach the kernel's own check of each interval row; every status word also equals the sequential run's."""
   from assembled_cnn_amd import jpeg, lib
   fxs = fixtures()
   names = ['noise_17x33_420', 'rst2_422_33x47', 'rst1_444_40x48', 'rst1_grey_40x48', 'smooth_13x17_444', 'noise_13x17_422']
-  pk = jpeg.pack([fxs[n][1] for n in names])
+  pk = jpeg.pack([fxs[n][1] for n in names], segment_bytes=16 if entropy == 'parallel' else None)
   d, iv = pk.descs, pk.intervals
   # 0: FF + a non-zero byte in the middle of the only interval: the data ends there, the MCUs after it are missing
   mid = int(d[0]['scan_offset'] + d[0]['scan_bytes'] // 2)
@@ -178,7 +181,11 @@ def test_damaged_tables_take_the_status_paths(product):
   iv['byte_end'][int(d[3]['first_interval']) + 5] = int(d[3]['scan_offset'] + d[3]['scan_bytes']) + 1
   # 4: a geometry that is none (the slot in dst still fits, so it is zeroed)
   d['mcus_x'][4] += 1
-  dst, status = jpeg.decode_packed(pk, 'cuda', check=False)
+  if entropy == 'parallel':
+    pk.segment_first, pk.total_segments = jpeg.segment_table(pk.intervals, pk.segment_bytes)
+    assert jpeg.decode_packed(pk, 'cuda', check=False)[1].cpu().tolist() == \
+        jpeg.decode_packed(pk, 'cuda', check=False, entropy='parallel')[1].cpu().tolist()
+  dst, status = jpeg.decode_packed(pk, 'cuda', check=False, entropy=entropy)
   status = status.cpu().tolist()
   assert status[0] & lib.JPEG_EOVERRUN and not status[0] & (lib.JPEG_ERESTART | lib.JPEG_EDESC)
   assert status[1] == lib.JPEG_ERESTART and status[2] == lib.JPEG_ERESTART

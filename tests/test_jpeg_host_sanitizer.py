@@ -1,9 +1,11 @@
 """The device JPEG entropy decoder's own text (csrc/jpeg_entropy.h), compiled for the host with the address and
 undefined-behaviour sanitizers and run as a stand-alone program (tools/probes/jpeg_entropy_host.cpp): every fixture intact
 (coefficients equal tests/jpeg_ref.py's), then every truncation of each scan and every single byte replaced by 00, FF and
-D9.  No GPU; nothing is loaded into this interpreter, nothing is preloaded, the environment is passed on as it is."""
+D9, then damaged interval rows.  The program's `status digest` line pins the status word of every damaged run to the
+value recorded in tests/golden/jpeg_status_digests.json.  No GPU; nothing is loaded into this interpreter, nothing is
+preloaded, the environment is passed on as it is."""
+import json
 import os
-import shutil
 import struct
 import subprocess
 
@@ -11,23 +13,15 @@ import numpy as np
 import pytest
 
 from tests import jpeg_ref
+from tests.sanitizer_build import compile_command
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'tools', 'probes', 'jpeg_entropy_host.cpp')
 
 
-def _compile_command(exe):
-  """host compiler + flags that link the sanitizer runtimes STATICALLY: the program then starts in whatever environment
-  the suite runs in, and the test leaves that environment alone"""
-  flags = ['-std=c++17', '-O2', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-pthread']
-  for name in ('c++', 'g++'):
-    cxx = shutil.which(name)
-    if cxx and 'clang' not in os.path.realpath(cxx):
-      return [cxx] + flags + ['-static-libasan', '-static-libubsan', SRC, '-o', exe]
-  for cxx in (shutil.which('clang++'), '/opt/rocm/llvm/bin/clang++', '/opt/rocm/lib/llvm/bin/clang++'):
-    if cxx and os.path.exists(cxx):
-      return [cxx] + flags + [SRC, '-o', exe]      # clang links its sanitizer runtimes statically by default
-  raise RuntimeError('no host C++ compiler found')
+def recorded_digest(program):
+  with open(os.path.join(ROOT, 'tests', 'golden', 'jpeg_status_digests.json')) as f:
+    return json.load(f)[program]
 
 
 def _cases():
@@ -49,7 +43,7 @@ def _cases():
 
 def test_entropy_decoder_is_clean_under_host_sanitizers(tmp_path):
   exe = str(tmp_path / 'jpeg_entropy_host')
-  r = subprocess.run(_compile_command(exe), capture_output=True, text=True)
+  r = subprocess.run(compile_command(SRC, exe), capture_output=True, text=True)
   assert r.returncode == 0, 'compile failed:\n%s\n%s' % (r.stdout, r.stderr)
   blob, n = _cases()
   path = str(tmp_path / 'cases.bin')
@@ -59,3 +53,4 @@ def test_entropy_decoder_is_clean_under_host_sanitizers(tmp_path):
   assert r.returncode == 0, 'sanitizer program failed (%d):\n%s\n%s' % (r.returncode, r.stdout, r.stderr[-4000:])
   assert 'ERROR' not in r.stderr and 'runtime error' not in r.stderr, r.stderr[-4000:]
   assert ('%d cases intact and equal' % n) in r.stdout and n >= 39, r.stdout
+  assert ('status digest: %s\n' % recorded_digest('jpeg_entropy_host')) in r.stdout, r.stdout

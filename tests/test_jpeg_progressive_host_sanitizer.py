@@ -1,8 +1,10 @@
 """The progressive entropy stage's own text (csrc/jpeg_entropy.h), compiled for the host with the address and
 undefined-behaviour sanitizers and run as a stand-alone program (tools/probes/jpeg_progressive_host.cpp): every progressive
 fixture and a re-coded file of every script intact (coefficients equal tests/jpeg_progressive_ref.py's), then every
-truncation of every scan and every entropy-coded byte replaced by 00, FF and D9.  No GPU; nothing is loaded into this
-interpreter, nothing is preloaded, the environment is passed on as it is."""
+truncation of every scan and every entropy-coded byte replaced by 00, FF and D9, then damaged table rows.  The program's
+`status digest` line pins the status word of every damaged run to the value recorded in
+tests/golden/jpeg_status_digests.json.  No GPU; nothing is loaded into this interpreter, nothing is preloaded, the
+environment is passed on as it is."""
 import os
 import struct
 import subprocess
@@ -10,7 +12,8 @@ import subprocess
 import numpy as np
 
 from tests import jpeg_progressive_ref, jpeg_progressive_writer
-from tests.test_jpeg_host_sanitizer import _compile_command
+from tests.sanitizer_build import compile_command
+from tests.test_jpeg_host_sanitizer import recorded_digest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, 'tools', 'probes', 'jpeg_progressive_host.cpp')
@@ -45,8 +48,7 @@ def _cases():
 
 def test_progressive_entropy_decoder_is_clean_under_host_sanitizers(tmp_path):
   exe = str(tmp_path / 'jpeg_progressive_host')
-  cmd = [SRC if arg.endswith('jpeg_entropy_host.cpp') else arg for arg in _compile_command(exe)]
-  r = subprocess.run(cmd, capture_output=True, text=True)
+  r = subprocess.run(compile_command(SRC, exe), capture_output=True, text=True)
   assert r.returncode == 0, 'compile failed:\n%s\n%s' % (r.stdout, r.stderr)
   blob, n = _cases()
   path = str(tmp_path / 'cases.bin')
@@ -56,3 +58,4 @@ def test_progressive_entropy_decoder_is_clean_under_host_sanitizers(tmp_path):
   assert r.returncode == 0, 'sanitizer program failed (%d):\n%s\n%s' % (r.returncode, r.stdout, r.stderr[-4000:])
   assert 'ERROR' not in r.stderr and 'runtime error' not in r.stderr, r.stderr[-4000:]
   assert ('%d cases intact and equal' % n) in r.stdout and n >= 51, r.stdout
+  assert ('status digest: %s\n' % recorded_digest('jpeg_progressive_host')) in r.stdout, r.stdout

@@ -12,19 +12,14 @@
 //   (2) every truncation of the scan, (3) every byte replaced by 00, FF and D9: the same status word.
 // A scan longer than kFullSweepBytes is damaged at every kStride-th position and at its middle (the cut the GPU tests
 // use) instead of at every position; it runs intact in full.
-//   (4) shared state rows: two images whose segment tables name the same rows of the state region, their phases
+//   (4) damaged rows (a wrong RSTm, an interval count off by one, an interval row one byte past the scan): the same
+//       status word, which has the bit of the damage's kind;
+//   (5) shared state rows: two images whose segment tables name the same rows of the state region, their phases
 //       interleaved, in both orders: any result, but no access out of range and no more than segments + 1 rounds.
 // The scan, the tables and the state region are exact-size heap blocks of their own, so one byte read or one row written
-// past them is an AddressSanitizer report.  One line per case and configuration reports segments and rounds.
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <atomic>
-#include <thread>
-#include <vector>
-
-#include "../../assembled_cnn_amd/csrc/jpeg_entropy.h"
+// past them is an AddressSanitizer report.  One line per case and configuration reports segments and rounds.  The damage
+// and the thread pool are jpeg_probe.h's.
+#include "jpeg_probe.h"
 
 static_assert(sizeof(asm_jpeg_desc) == 96 && sizeof(asm_jpeg_tables) == 1600 && sizeof(asm_jpeg_interval) == 32 &&
                   sizeof(jpeg_seg) == 32,
@@ -44,37 +39,13 @@ static const int kSegmentBytes[3] = {16, 48, 128};
 static const int kLanes[2] = {5, 256};
 static const int64_t kFullSweepBytes = 8192, kStride = 7;
 
-static bool read_exact(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
-
-// the descriptor and the interval rows of a file cut at `limit`, as the host parser would find them
-static bool cut_rows(const Case& c, int64_t limit, asm_jpeg_desc* d, jpeg_geom* g, std::vector<asm_jpeg_interval>* iv, int* st) {
-  *d = c.d;
-  if (!jpeg_make_geom(*d, g)) {
-    *st = ASM_JPEG_EDESC;
-    return false;
-  }
-  if (d->n_intervals != jpeg_expected_intervals(*d, *g) || d->n_intervals != (int)c.iv.size()) {
-    *st = ASM_JPEG_ERESTART;
-    return false;
-  }
-  *iv = c.iv;
-  d->scan_offset = 0;
-  d->scan_bytes = limit;
-  d->first_interval = 0;
-  for (auto& r : *iv) {
-    if (r.byte_begin > limit) r.byte_begin = limit;
-    if (r.byte_end > limit) r.byte_end = limit;
-  }
-  return true;
-}
-
 // the sequential decoder: one workgroup, one lane
 static int decode_sequential(const Case& c, const uint8_t* scan, int64_t limit, std::vector<int16_t>* out) {
   asm_jpeg_desc d;
   jpeg_geom g;
   std::vector<asm_jpeg_interval> iv;
   int st = 0;
-  if (!cut_rows(c, limit, &d, &g, &iv, &st)) return st;
+  if (!probe::cut_rows(c, limit, &d, &g, &iv, &st)) return st;
   out->assign((size_t)g.n_coefs, 0);
   return jpeg_decode_lane(scan, d, g, iv.data(), iv.empty() ? 0 : iv[0].image, c.tab.data(), kZigzag, 0, 1, out->data());
 }
@@ -86,7 +57,7 @@ static int decode_parallel(const Case& c, const uint8_t* scan, int64_t limit, in
   std::vector<asm_jpeg_interval> iv;
   int st = 0;
   *n_segs = *n_rounds = 0;
-  if (!cut_rows(c, limit, &x.d, &x.g, &iv, &st)) return st;
+  if (!probe::cut_rows(c, limit, &x.d, &x.g, &iv, &st)) return st;
   out->assign((size_t)x.g.n_coefs, 0);
   // the segment table, by the rule of include/asm_hip.h
   std::vector<int32_t> first(iv.size());
@@ -96,17 +67,8 @@ static int decode_parallel(const Case& c, const uint8_t* scan, int64_t limit, in
     total += jpeg_par_interval_segments(iv[k], segment_bytes);
   }
   std::vector<jpeg_seg> segs((size_t)total);
-  x.files = scan;
-  x.bpm = x.d.ncomp == 1 ? 1 : x.d.hs * x.d.vs + 2;
-  x.intervals = iv.data();
-  x.seg_first = first.data();
-  x.img = iv.empty() ? 0 : iv[0].image;
-  x.segment_bytes = segment_bytes;
-  x.tab = c.tab.data();
-  x.zigzag = kZigzag;
-  x.coefs = out->data();
-  x.segs = nullptr;
-  x.n_segs = 0;
+  jpeg_par_ctx_fill(&x, scan, iv.data(), first.data(), iv.empty() ? 0 : iv[0].image, segment_bytes, c.tab.data(), kZigzag,
+                    out->data());
   bool bad = false;
   for (int l = 0; l < lanes; ++l) bad |= jpeg_par_check_table(x, total, l, lanes);
   if (bad) return ASM_JPEG_EDESC;
@@ -134,7 +96,7 @@ static int decode_parallel(const Case& c, const uint8_t* scan, int64_t limit, in
   return err;
 }
 
-// (4): what two workgroups do when the segment table gives image 1 the state rows of image 0.  Each image has its own
+// (5): what two workgroups do when the segment table gives image 1 the state rows of image 0.  Each image has its own
 // exact-size interval and segment tables (an index past the image's own rows is a report), the scans share one block.
 static bool shared_rows(const Case& a, const Case& b, int segment_bytes, int lanes) {
   const Case* cs[2] = {&a, &b};
@@ -149,7 +111,7 @@ static bool shared_rows(const Case& a, const Case& b, int segment_bytes, int lan
   int64_t total[2];
   for (int i = 0; i < 2; ++i) {
     int st = 0;
-    if (!cut_rows(*cs[i], (int64_t)cs[i]->scan.size(), &x[i].d, &x[i].g, &iv[i], &st)) return false;
+    if (!probe::cut_rows(*cs[i], (int64_t)cs[i]->scan.size(), &x[i].d, &x[i].g, &iv[i], &st)) return false;
     x[i].d.scan_offset = off[i];
     total[i] = 0;
     for (auto& r : iv[i]) {
@@ -164,15 +126,8 @@ static bool shared_rows(const Case& a, const Case& b, int segment_bytes, int lan
   const int64_t rows = std::max(total[0], total[1]);
   std::vector<jpeg_seg> segs((size_t)rows);
   for (int i = 0; i < 2; ++i) {
-    x[i].files = files.data();
-    x[i].bpm = x[i].d.ncomp == 1 ? 1 : x[i].d.hs * x[i].d.vs + 2;
-    x[i].intervals = iv[i].data();
-    x[i].seg_first = first[i].data();
-    x[i].img = i;
-    x[i].segment_bytes = segment_bytes;
-    x[i].tab = cs[i]->tab.data();
-    x[i].zigzag = kZigzag;
-    x[i].coefs = coefs[i].data();
+    jpeg_par_ctx_fill(&x[i], files.data(), iv[i].data(), first[i].data(), i, segment_bytes, cs[i]->tab.data(), kZigzag,
+                      coefs[i].data());
     x[i].segs = segs.data();
     for (int l = 0; l < lanes; ++l)
       if (jpeg_par_check_table(x[i], rows, l, lanes)) return false;
@@ -210,37 +165,16 @@ static bool shared_rows(const Case& a, const Case& b, int segment_bytes, int lan
 }
 
 int main(int argc, char** argv) {
-  if (argc < 2) {
-    fprintf(stderr, "usage: %s cases.bin [threads]\n", argv[0]);
-    return 2;
-  }
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) {
-    perror(argv[1]);
-    return 2;
-  }
   int32_t count = 0;
-  if (!read_exact(f, &count, 4) || count < 0 || count > 100000) return 2;
+  FILE* f = probe::open_cases(argc, argv, &count);
+  if (!f) return 2;
   std::vector<Case> cases((size_t)count);
   for (auto& c : cases) {
-    int32_t ni = 0;
-    int64_t nb = 0, nc = 0;
-    if (!read_exact(f, &c.d, sizeof c.d) || !read_exact(f, &c.t, sizeof c.t) || !read_exact(f, &ni, 4) || ni < 0 ||
-        ni > (1 << 24))
+    if (!probe::read_exact(f, &c.d, sizeof c.d) || !probe::read_exact(f, &c.t, sizeof c.t) ||
+        !probe::read_rows<int32_t>(f, &c.iv, 1 << 24) || !probe::read_rows<int64_t>(f, &c.scan, 1ll << 30) ||
+        !probe::read_rows<int64_t>(f, &c.expected, 1ll << 30))
       return 2;
-    c.iv.resize((size_t)ni);
-    if (!read_exact(f, c.iv.data(), sizeof(asm_jpeg_interval) * (size_t)ni) || !read_exact(f, &nb, 8) || nb < 0 ||
-        nb > (1ll << 30))
-      return 2;
-    c.scan.resize((size_t)nb);
-    if (!read_exact(f, c.scan.data(), (size_t)nb) || !read_exact(f, &nc, 8) || nc < 0 || nc > (1ll << 30)) return 2;
-    c.expected.resize((size_t)nc);
-    if (!read_exact(f, c.expected.data(), 2 * (size_t)nc)) return 2;
-    c.tab.resize(4);
-    for (int i = 0; i < 4; ++i) {
-      jpeg_dtab_prepare(i < 2 ? c.t.dc[i] : c.t.ac[i - 2], &c.tab[i]);
-      jpeg_dtab_fill_look(&c.tab[i], 0, 1);
-    }
+    c.tab = probe::baseline_tabs(c.t);
   }
   fclose(f);
 
@@ -250,27 +184,18 @@ int main(int argc, char** argv) {
     std::vector<int16_t> seq, par;
     std::vector<uint8_t> scan(c.scan);
     const int st = decode_sequential(c, scan.data(), (int64_t)scan.size(), &seq);
-    if (st != 0 || seq != c.expected) {
-      fprintf(stderr, "case %zu: the sequential decoder fails on the intact scan (status %d)\n", k, st);
-      return 1;
-    }
+    probe::require_intact(k, st, seq == c.expected, " (sequential)");
     for (int sb : kSegmentBytes) {
       for (int lanes : kLanes) {
         int n_segs, rounds;
         const int pst = decode_parallel(c, scan.data(), (int64_t)scan.size(), sb, lanes, &par, &n_segs, &rounds);
         printf("case %zu segment_bytes %d lanes %d segments %d rounds %d\n", k, sb, lanes, n_segs, rounds);
-        if (pst != 0) {
-          fprintf(stderr, "case %zu (segment_bytes %d, %d lanes): status %d on the intact scan\n", k, sb, lanes, pst);
-          return 1;
-        }
-        if (par != c.expected) {
-          fprintf(stderr, "case %zu (segment_bytes %d, %d lanes): coefficients differ from the reference\n", k, sb, lanes);
-          return 1;
-        }
+        fflush(stdout);
+        probe::require_intact(k, pst, par == c.expected, " (parallel, the configuration printed last)");
       }
     }
   }
-  // (4) shared state rows: the single-interval case with the most bytes against the case with the most intervals
+  // (5) shared state rows: the single-interval case with the most bytes against the case with the most intervals
   {
     size_t one = 0, many = 0;
     for (size_t k = 0; k < cases.size(); ++k) {
@@ -291,66 +216,54 @@ int main(int argc, char** argv) {
     printf("shared state rows: cases %zu (%zu intervals) and %zu (%zu intervals), %d runs\n", one, cases[one].iv.size(), many,
            cases[many].iv.size(), done);
   }
-  // (2), (3) damaged scans: work items of CHUNK byte positions of one case, shared out over a few threads
-  const int64_t CHUNK = 64;
-  struct Item {
-    size_t k;
-    int64_t from, to;
-  };
-  std::vector<Item> items;
-  for (size_t k = 0; k < cases.size(); ++k)
-    for (int64_t at = 0; at < (int64_t)cases[k].scan.size(); at += CHUNK)
-      items.push_back({k, at, std::min<int64_t>(at + CHUNK, (int64_t)cases[k].scan.size())});
-  std::atomic<size_t> next{0};
+  // (2), (3) damaged scans: work items of 64 byte positions of one case
+  std::vector<probe::Item> items;
+  for (size_t k = 0; k < cases.size(); ++k) probe::add_items(&items, k, 0, 0, (int64_t)cases[k].scan.size(), 64);
+  // one damaged input at every segment size and lane count: the parallel decoder against the sequential one
   std::atomic<long> runs{0}, with_status{0}, mismatches{0};
-  auto worker = [&]() {
+  auto compare = [&](const Case& c, size_t k, const uint8_t* scan, int64_t n, probe::Damage kind, int64_t at) {
     std::vector<int16_t> seq, par;
-    auto compare = [&](const Case& c, size_t k, const uint8_t* scan, int64_t n, const char* what, int64_t at) {
-      const int want = decode_sequential(c, scan, n, &seq);
-      for (int sb : kSegmentBytes) {
-        for (int lanes : kLanes) {
-          int n_segs, rounds;
-          const int got = decode_parallel(c, scan, n, sb, lanes, &par, &n_segs, &rounds);
-          const bool same = got == want && (want != 0 || par == seq) && rounds >= (n_segs > 0 ? 1 : 0) && rounds <= n_segs + 1;
-          if (!same && mismatches++ < 20)
-            fprintf(stderr, "case %zu, %s at %lld (segment_bytes %d, %d lanes): status %d, sequential %d, %d rounds for %d segments\n",
-                    k, what, (long long)at, sb, lanes, got, want, rounds, n_segs);
-          ++runs;
-        }
-      }
-      if (want) ++with_status;
-    };
-    for (size_t i = next++; i < items.size(); i = next++) {
-      const size_t k = items[i].k;
-      const Case& c = cases[k];
-      const int64_t n = (int64_t)c.scan.size();
-      const bool full = n <= kFullSweepBytes;
-      for (int64_t cut = items[i].from; cut < items[i].to; ++cut) {      // a block of exactly `cut` bytes
-        if (!full && cut % kStride != 0 && cut != n / 2) continue;
-        std::vector<uint8_t> scan(c.scan.begin(), c.scan.begin() + cut);
-        compare(c, k, scan.data(), cut, "cut", cut);
-      }
-      const uint8_t repl[3] = {0x00, 0xFF, 0xD9};
-      std::vector<uint8_t> scan(c.scan);
-      for (int64_t at = items[i].from; at < items[i].to; ++at) {
-        if (!full && at % kStride != 0 && at != n / 2) continue;
-        const uint8_t keep = scan[(size_t)at];
-        for (uint8_t r : repl) {
-          if (r == keep) continue;
-          scan[(size_t)at] = r;
-          compare(c, k, scan.data(), n, r == 0 ? "00" : r == 0xFF ? "FF" : "D9", at);
-        }
-        scan[(size_t)at] = keep;
+    const int want = decode_sequential(c, scan, n, &seq);
+    for (int sb : kSegmentBytes) {
+      for (int lanes : kLanes) {
+        int n_segs, rounds;
+        const int got = decode_parallel(c, scan, n, sb, lanes, &par, &n_segs, &rounds);
+        const bool same = got == want && (want != 0 || par == seq) && rounds >= (n_segs > 0 ? 1 : 0) && rounds <= n_segs + 1;
+        if (!same && mismatches++ < 20)
+          fprintf(stderr, "case %zu, %s at %lld (segment_bytes %d, %d lanes): status %d, sequential %d, %d rounds for %d segments\n",
+                  k, probe::kDamageName[kind], (long long)at, sb, lanes, got, want, rounds, n_segs);
+        ++runs;
       }
     }
+    if (want) ++with_status;
+    return want;
   };
-  const unsigned hw = std::thread::hardware_concurrency();
-  const unsigned nthreads = argc > 2 ? (unsigned)atoi(argv[2]) : std::max(1u, std::min(8u, hw));
-  std::vector<std::thread> pool;
-  for (unsigned t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-  worker();
-  for (auto& t : pool) t.join();
+  probe::run_pool(items.size(), argc, argv, [&](size_t i) {
+    const size_t k = items[i].k;
+    const Case& c = cases[k];
+    const int64_t n = (int64_t)c.scan.size();
+    probe::Sweep sw;
+    if (n > kFullSweepBytes) {
+      sw.stride = kStride;
+      sw.also = n / 2;
+    }
+    probe::sweep_damage(c.scan, items[i].from, items[i].to, sw, [&](probe::Damage kind, int64_t at, const uint8_t* scan, int64_t m) {
+      compare(c, k, scan, m, kind, at);
+    });
+  });
+  // (4) damaged rows
+  long rows_damaged = 0;
+  for (size_t k = 0; k < cases.size(); ++k) {
+    Case w = cases[k];
+    probe::damage_rows(&w.iv, 0, &w.d.n_intervals, (int64_t)w.scan.size(), [&](probe::Damage kind, int want) {
+      std::vector<uint8_t> scan(w.scan);
+      const int st = compare(w, k, scan.data(), (int64_t)scan.size(), kind, 0);
+      ++rows_damaged;
+      probe::require_row_status(k, kind, st, want, (st & want) != 0);
+    });
+  }
   printf("jpeg_parallel_host: %zu cases intact and equal, %ld damaged runs (%ld damaged scans ended with a status), %ld mismatches\n",
          cases.size(), runs.load(), with_status.load(), mismatches.load());
+  printf("damaged rows: %ld\n", rows_damaged);
   return mismatches.load() ? 1 : 0;
 }

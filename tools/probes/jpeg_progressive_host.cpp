@@ -14,17 +14,11 @@
 // if that ends without a status the scans after it follow, as they would on the device) and (3) every entropy-coded byte
 // replaced by 00, FF and D9, and every pair of bytes by FF D9 (that scan and all scans after it are decoded, so the
 // refinement scans run over whatever the damaged scan left) must end with a non-zero status or a completed decode.
-// (4) Damaged rows, per case: a wrong RSTm, an interval count off by one, a Huffman-pool index out of range must each end
-// with the status bit of their kind.
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <atomic>
-#include <thread>
-#include <vector>
-
-#include "../../assembled_cnn_amd/csrc/jpeg_entropy.h"
+// (4) Damaged rows, per scan: a wrong RSTm, an interval count off by one, an interval row one byte past its scan's range
+// and a Huffman-pool index out of range must each end with the status of their kind.
+// The damage itself and the thread pool are jpeg_probe.h's.  `status digest` is the sum of probe::digest_term over every
+// damaged run: it pins each status word (tests/golden/jpeg_status_digests.json).
+#include "jpeg_probe.h"
 
 static_assert(sizeof(asm_jpeg_desc) == 96 && sizeof(asm_jpeg_scan) == 56 && sizeof(asm_jpeg_huff) == 272 &&
                   sizeof(asm_jpeg_interval) == 32,
@@ -40,38 +34,26 @@ struct Case {
   std::vector<std::vector<int16_t>> before;      // [k] the coefficients as the intact scans 0..k-1 leave them
 };
 
-static bool read_exact(FILE* f, void* p, size_t n) { return n == 0 || fread(p, 1, n, f) == n; }
-
-template <class T>
-static bool read_rows(FILE* f, std::vector<T>* v, int32_t limit) {
-  int32_t n = 0;
-  if (!read_exact(f, &n, 4) || n < 0 || n > limit) return false;
-  v->resize((size_t)n);
-  return read_exact(f, v->data(), sizeof(T) * (size_t)n);
-}
-
 // What the workgroup does for scans [from, to) of the image, on one "lane", on top of the coefficients in *coefs.
 // bytes: the image's bytes, of which only the first `limit` exist (a file cut there: rows are clipped to it).
 static int decode_scans(const Case& c, const uint8_t* bytes, int64_t limit, int from, int to, std::vector<int16_t>* coefs,
                         std::vector<std::vector<int16_t>>* snapshots = nullptr) {
   static const uint8_t zigzag[64] = JPEG_ZIGZAG_INIT;
+  const bool cut = limit < (int64_t)c.bytes.size();
   jpeg_geom g;
   asm_jpeg_desc d = c.d;
   d.scan_offset = 0;
   d.scan_bytes = limit;
   if (!jpeg_make_geom(d, &g) || (int64_t)coefs->size() != g.n_coefs) return ASM_JPEG_EDESC;
   std::vector<asm_jpeg_interval> iv(c.iv);      // exact-size copies: heap blocks of their own
-  for (auto& r : iv) {
-    r.byte_begin = std::min(r.byte_begin, limit);
-    r.byte_end = std::min(r.byte_end, limit);
-  }
+  if (cut)
+    for (auto& r : iv) probe::clip_row(&r, limit);
   std::vector<jpeg_dtab> tab(3);
   int err = 0;
   for (int k = from; k < to && !err; ++k) {
     if (snapshots) snapshots->push_back(*coefs);
     asm_jpeg_scan sc = c.scans[(size_t)k];
-    sc.byte_begin = std::min(sc.byte_begin, limit);
-    sc.byte_end = std::min(sc.byte_end, limit);
+    if (cut) probe::clip_row(&sc, limit);
     jpeg_scan_geom sg;
     err = jpeg_check_scan(d, g, sc, sc.image, (int)c.huff.size(), (int)iv.size(), &sg);
     if (err) break;
@@ -86,27 +68,15 @@ static int decode_scans(const Case& c, const uint8_t* bytes, int64_t limit, int 
 }
 
 int main(int argc, char** argv) {
-  if (argc < 2) {
-    fprintf(stderr, "usage: %s cases.bin [threads]\n", argv[0]);
-    return 2;
-  }
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) {
-    perror(argv[1]);
-    return 2;
-  }
   int32_t count = 0;
-  if (!read_exact(f, &count, 4) || count < 0 || count > 100000) return 2;
+  FILE* f = probe::open_cases(argc, argv, &count);
+  if (!f) return 2;
   std::vector<Case> cases((size_t)count);
   for (auto& c : cases) {
-    int64_t nb = 0, nc = 0;
-    if (!read_exact(f, &c.d, sizeof c.d) || !read_rows(f, &c.scans, 256) || !read_rows(f, &c.huff, 1024) ||
-        !read_rows(f, &c.iv, 1 << 24) || !read_exact(f, &nb, 8) || nb < 0 || nb > (1ll << 30))
+    if (!probe::read_exact(f, &c.d, sizeof c.d) || !probe::read_rows<int32_t>(f, &c.scans, 256) ||
+        !probe::read_rows<int32_t>(f, &c.huff, 1024) || !probe::read_rows<int32_t>(f, &c.iv, 1 << 24) ||
+        !probe::read_rows<int64_t>(f, &c.bytes, 1ll << 30) || !probe::read_rows<int64_t>(f, &c.expected, 1ll << 30))
       return 2;
-    c.bytes.resize((size_t)nb);
-    if (!read_exact(f, c.bytes.data(), (size_t)nb) || !read_exact(f, &nc, 8) || nc < 0 || nc > (1ll << 30)) return 2;
-    c.expected.resize((size_t)nc);
-    if (!read_exact(f, c.expected.data(), 2 * (size_t)nc)) return 2;
   }
   fclose(f);
 
@@ -116,115 +86,64 @@ int main(int argc, char** argv) {
     std::vector<int16_t> out(c.expected.size(), 0);
     std::vector<uint8_t> bytes(c.bytes);
     const int st = decode_scans(c, bytes.data(), (int64_t)bytes.size(), 0, (int)c.scans.size(), &out, &c.before);
-    if (st != 0) {
-      fprintf(stderr, "case %zu: status %d on the intact file\n", k, st);
-      return 1;
-    }
-    if (out != c.expected) {
-      fprintf(stderr, "case %zu: coefficients differ from the reference\n", k);
-      return 1;
-    }
+    probe::require_intact(k, st, out == c.expected);
   }
-  // (2), (3) damaged scans: work items of CHUNK byte positions of one scan, shared out over a few threads
-  const int64_t CHUNK = 128;
-  struct Item {
-    size_t k;
-    int scan;
-    int64_t from, to;
-  };
-  std::vector<Item> items;
+  // (2), (3) damaged scans: work items of 128 byte positions of one scan
+  std::vector<probe::Item> items;
   for (size_t k = 0; k < cases.size(); ++k)
-    for (size_t s = 0; s < cases[k].scans.size(); ++s) {
-      const asm_jpeg_scan& sc = cases[k].scans[s];
-      for (int64_t at = sc.byte_begin; at < sc.byte_end; at += CHUNK)
-        items.push_back({k, (int)s, at, std::min<int64_t>(at + CHUNK, sc.byte_end)});
-    }
-  std::atomic<size_t> next{0};
+    for (size_t s = 0; s < cases[k].scans.size(); ++s)
+      probe::add_items(&items, k, (int)s, cases[k].scans[s].byte_begin, cases[k].scans[s].byte_end, 128);
   std::atomic<long> runs{0}, failed_status{0}, completed{0};
-  auto worker = [&]() {
+  std::atomic<uint64_t> digest{0};
+  probe::run_pool(items.size(), argc, argv, [&](size_t i) {
+    const size_t k = items[i].k;
+    const Case& c = cases[k];
+    const int s = items[i].scan, n_scans = (int)c.scans.size();
     std::vector<int16_t> out;
-    for (size_t i = next++; i < items.size(); i = next++) {
-      const Case& c = cases[items[i].k];
-      const int s = items[i].scan, n_scans = (int)c.scans.size();
-      const int64_t n = (int64_t)c.bytes.size();
-      for (int64_t cut = items[i].from; cut < items[i].to; ++cut) {      // a block of exactly `cut` bytes
-        std::vector<uint8_t> bytes(c.bytes.begin(), c.bytes.begin() + cut);
-        out = c.before[(size_t)s];
-        int st = decode_scans(c, bytes.data(), cut, s, s + 1, &out);
-        if (!st && s + 1 < n_scans) {      // the shortened scan decoded: the scans after it run on what it left
-          std::vector<uint8_t> whole(c.bytes);
-          st = decode_scans(c, whole.data(), n, s + 1, n_scans, &out);
-        }
-        st ? ++failed_status : ++completed;
-        ++runs;
-      }
-      const uint8_t repl[3] = {0x00, 0xFF, 0xD9};
-      std::vector<uint8_t> bytes(c.bytes);
-      for (int64_t at = items[i].from; at < items[i].to; ++at) {
-        const uint8_t keep = bytes[(size_t)at];
-        for (uint8_t r : repl) {
-          if (r == keep) continue;
-          bytes[(size_t)at] = r;
-          out = c.before[(size_t)s];
-          decode_scans(c, bytes.data(), n, s, n_scans, &out) ? ++failed_status : ++completed;
-          ++runs;
-        }
-        bytes[(size_t)at] = keep;
-        if (at + 1 < c.scans[(size_t)s].byte_end) {      // a marker written over two bytes
-          const uint8_t keep1 = bytes[(size_t)at + 1];
-          bytes[(size_t)at] = 0xFF;
-          bytes[(size_t)at + 1] = 0xD9;
-          out = c.before[(size_t)s];
-          decode_scans(c, bytes.data(), n, s, n_scans, &out) ? ++failed_status : ++completed;
-          ++runs;
-          bytes[(size_t)at] = keep;
-          bytes[(size_t)at + 1] = keep1;
-        }
-      }
-    }
-  };
-  const unsigned hw = std::thread::hardware_concurrency();
-  const unsigned nthreads = argc > 2 ? (unsigned)atoi(argv[2]) : std::max(1u, std::min(8u, hw));
-  std::vector<std::thread> pool;
-  for (unsigned t = 1; t < nthreads; ++t) pool.emplace_back(worker);
-  worker();
-  for (auto& t : pool) t.join();
+    probe::Sweep sw;
+    sw.pair_end = c.scans[(size_t)s].byte_end;
+    probe::sweep_damage(c.bytes, items[i].from, items[i].to, sw,
+                        [&](probe::Damage kind, int64_t at, const uint8_t* bytes, int64_t n) {
+                          out = c.before[(size_t)s];
+                          int st;
+                          if (kind == probe::CUT) {
+                            st = decode_scans(c, bytes, n, s, s + 1, &out);
+                            if (!st && s + 1 < n_scans) {      // the shortened scan decoded: the scans after it run on what it left
+                              std::vector<uint8_t> whole(c.bytes);
+                              st = decode_scans(c, whole.data(), (int64_t)whole.size(), s + 1, n_scans, &out);
+                            }
+                          } else {
+                            st = decode_scans(c, bytes, n, s, n_scans, &out);
+                          }
+                          st ? ++failed_status : ++completed;
+                          ++runs;
+                          digest += probe::digest_term(k, s, kind, at, st);
+                        });
+  });
   // (4) damaged rows
   long rows_damaged = 0;
   for (size_t k = 0; k < cases.size(); ++k) {
-    const Case& c = cases[k];
-    const int n_scans = (int)c.scans.size();
-    auto run = [&](const Case& damaged, int want, const char* what) {
-      std::vector<int16_t> out(c.expected.size(), 0);
-      std::vector<uint8_t> bytes(c.bytes);
-      const int st = decode_scans(damaged, bytes.data(), (int64_t)bytes.size(), 0, n_scans, &out);
-      ++rows_damaged;
-      if (st != want) {
-        fprintf(stderr, "case %zu: %s gave status %d, expected %d\n", k, what, st, want);
-        exit(1);
-      }
-    };
+    const int n_scans = (int)cases[k].scans.size();
     for (int s = 0; s < n_scans; ++s) {
-      const asm_jpeg_scan& sc = c.scans[(size_t)s];
-      if (sc.n_intervals > 1) {
-        Case w = c;
-        w.iv[(size_t)sc.first_interval].rst ^= 1;
-        run(w, ASM_JPEG_ERESTART, "a wrong RSTm");
-      }
-      {
-        Case w = c;
-        w.scans[(size_t)s].n_intervals += sc.n_intervals > 1 ? -1 : 1;
-        if (sc.n_intervals == 1) w.iv.push_back(w.iv.back());      // keep first_interval + n_intervals inside the table
-        run(w, ASM_JPEG_ERESTART, "an interval count off by one");
-      }
+      Case w = cases[k];
+      auto run = [&](probe::Damage kind, int want) {
+        std::vector<int16_t> out(w.expected.size(), 0);
+        std::vector<uint8_t> bytes(w.bytes);
+        const int st = decode_scans(w, bytes.data(), (int64_t)bytes.size(), 0, n_scans, &out);
+        ++rows_damaged;
+        digest += probe::digest_term(k, s, kind, 0, st);
+        probe::require_row_status(k, kind, st, want, st == want);
+      };
+      asm_jpeg_scan& sc = w.scans[(size_t)s];
+      probe::damage_rows(&w.iv, sc.first_interval, &sc.n_intervals, sc.byte_end, run);
       if (jpeg_scan_tables(sc) > 0) {
-        Case w = c;
-        w.scans[(size_t)s].huff[0] = (int32_t)c.huff.size();
-        run(w, ASM_JPEG_EDESC, "a Huffman-pool index out of range");
+        sc.huff[0] = (int32_t)w.huff.size();
+        run(probe::ROW_HUFF, ASM_JPEG_EDESC);
       }
     }
   }
   printf("jpeg_progressive_host: %zu cases intact and equal, %ld damaged runs (%ld ended with a status, %ld completed), %ld damaged rows\n",
          cases.size(), runs.load(), failed_status.load(), completed.load(), rows_damaged);
+  printf("status digest: %016llx\n", (unsigned long long)digest.load());
   return 0;
 }
