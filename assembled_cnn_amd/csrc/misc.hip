@@ -736,6 +736,10 @@ extern "C" int asm_mixup_labels(const float* y, int Bin, int C, int mixup_type, 
 extern "C" int asm_sgd_momentum(float* w, float* accum, const float* grad, void* w_bf16, size_t n, float lr,
                                 float momentum, float weight_decay, float grad_scale, void* stream) {
   ASM_REQUIRE(w && accum && grad, "sgd_momentum: null pointer");
+  // sgd_kernel moves w, accum and grad as 16-byte vectors and the bf16 shadow as 8-byte ones
+  ASM_REQUIRE(((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(accum) | reinterpret_cast<uintptr_t>(grad)) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(w_bf16) & 7) == 0,
+              "sgd_momentum: w, accum and grad must be 16-byte aligned, w_bf16 8-byte aligned");
   if (n == 0) return ASM_OK;
   ASM_LAUNCH(sgd_kernel, dim3(ew_grid(cdivz(n, 4))), dim3(256), 0, (hipStream_t)stream, w, accum, grad,
                      (bf16_t*)w_bf16, n, lr, momentum, weight_decay, grad_scale);

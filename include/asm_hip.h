@@ -466,7 +466,9 @@ int asm_mixup_labels(const float* y, int Bin, int C, int mixup_type, const float
 /* ------------------------------------------------------------------------------------------------
  * Optimiser -- tf.train.MomentumOptimizer + the L2 term folded in (nets/optimizer_setting.py:23-38,
  * nets/run_loop_classification.py:166-178):  g' = g*grad_scale + wd*w ; a = mom*a + g' ; w -= lr*a ;
- * w_bf16 = bf16(w).  One launch over a flat arena.
+ * w_bf16 = bf16(w).  One launch over a flat arena.  w_bf16 may be NULL (no shadow is written); n = 0 does nothing.
+ * The kernel moves four elements at a time: w, accum and grad must be 16-byte aligned and w_bf16 8-byte aligned (a slice
+ * of the arena that starts at a multiple of 8 elements is), ASM_EINVAL otherwise, before anything is launched.
  * ---------------------------------------------------------------------------------------------- */
 int asm_sgd_momentum(float* w, float* accum, const float* grad, void* w_bf16, size_t n, float lr,
                      float momentum, float weight_decay, float grad_scale, void* stream);

@@ -1,5 +1,5 @@
 """Guard-band plumbing and element-wise bounds shared by the GPU edge-shape modules (tests/test_gpu_rows_edges.py,
-tests/test_gpu_pool_edges.py).  A plain module, not a conftest: the test modules import what they use, the autouse fixture
+tests/test_gpu_pool_edges.py, tests/test_gpu_bn_edges.py, tests/test_gpu_step_edges.py).  A plain module, not a conftest: the test modules import what they use, the autouse fixture
 ``_release_inputs`` included.
 
 * ``Out``: an output between two 4 KiB flanks of the byte 0xA5 which must survive the call; the output itself starts as 0xA5,
@@ -139,6 +139,15 @@ def close_ulp(case, out, ref, ulps=1):
   err, bound = np.abs(np.asarray(out, np.float64) - r32.astype(np.float64)), ulps * R.ulp32(r32)
   _report(case, err, bound)
   assert (err <= bound).all(), '%s: %.2f ulp' % (case, float(np.max(err / bound)))
+
+
+def close_terms(case, out, terms, roundings):
+  """a float32 expression the kernel evaluates from already rounded float32 values: ``roundings`` half-ulps of the sum of the
+  magnitudes of its terms"""
+  ref = sum(terms)
+  err, bound = np.abs(np.asarray(out, np.float64) - ref), roundings * R.U24 * sum(np.abs(t) for t in terms)
+  _report(case, err, bound)
+  assert (err <= bound).all(), '%s: |err| %.3e, bound %.3e' % (case, err.max(), bound.max())
 
 
 def exact(case, out, ref):

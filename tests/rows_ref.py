@@ -251,6 +251,58 @@ def filter_transpose(w, ldk=0):
   return out
 
 
+# ---- the step's first and last kernels: mixup + mean subtraction + stem halo, SGD with momentum -----------------------------------
+CHANNEL_MEANS = np.array([123.68, 116.78, 103.94], F32)     # preprocessing/imagenet_preprocessing.py:46-49, float32 constants
+
+
+def mixup_operands(a, mixup_type, lam1=None, lam2=None, dtype=F64):
+  """utils/data_util.py:97-158 on the leading axis of ``a`` [Bin, ...] -> (first operand, second operand, lambda [Bout]), the
+  last two None without mixup.  type 1 (2B -> B): a[b] with a[B + b] under lam1[b]; type 2 (B -> B): the first half as type 1,
+  the second half a[b] with the REVERSED second half, a[Bin - 1 - b], under lam2[b]."""
+  a = np.asarray(a, dtype)
+  if mixup_type == 0:
+    return a, None, None
+  h = a.shape[0] // 2
+  if mixup_type == 1:
+    return a[:h], a[h:], np.asarray(lam1, dtype)
+  return (np.concatenate([a[:h], a[:h]]), np.concatenate([a[h:], a[h:][::-1]]),
+          np.concatenate([np.asarray(lam1, dtype), np.asarray(lam2, dtype)]))
+
+
+def mixup_terms(a, mixup_type, lam1=None, lam2=None, dtype=F64):
+  """the mixed rows as the terms of their sum: (lam a, (1 - lam) b), or (a,) without mixup"""
+  fa, fb, lam = mixup_operands(a, mixup_type, lam1, lam2, dtype)
+  if fb is None:
+    return (fa,)
+  lam = lam.reshape((-1,) + (1,) * (fa.ndim - 1))
+  return lam * fa, (dtype(1) - lam) * fb
+
+
+def stem_pad(x):
+  """[N, H, W, 3] -> [N, H + 6, W + 6, 4]: a zero halo of 3 pixels and a zero fourth channel"""
+  x = np.asarray(x)
+  N, H, W, _ = x.shape
+  out = np.zeros((N, H + 6, W + 6, 4), x.dtype)
+  out[:, 3:3 + H, 3:3 + W, :3] = x
+  return out
+
+
+def mixup_meansub(images, mixup_type, lam1=None, lam2=None, dtype=F64):
+  """asm_mixup_meansub before its bf16 rounding: images [Bin, H, W, 3] in 0..255 minus CHANNEL_MEANS
+  (mean_image_subtraction), mixed (mixup), in the stem's padded layout"""
+  x = np.asarray(images, dtype) - CHANNEL_MEANS.astype(dtype)
+  return stem_pad(sum(mixup_terms(x, mixup_type, lam1, lam2, dtype)))
+
+
+def sgd_terms(w, accum, grad, lr, momentum, weight_decay, grad_scale, dtype=F64):
+  """tf.train.MomentumOptimizer with the L2 term folded in: g' = g grad_scale + wd w; a' = momentum a + g'; w' = w - lr a'.
+  The scalars are float32 arguments of the ABI.  -> (terms of a', terms of w'): each result is the sum of its terms"""
+  w, a, g = np.asarray(w, dtype), np.asarray(accum, dtype), np.asarray(grad, dtype)
+  lr, mom, wd, gs = (dtype(F32(v)) for v in (lr, momentum, weight_decay, grad_scale))
+  ta = (mom * a, g * gs, wd * w)
+  return ta, (w,) + tuple(-lr * t for t in ta)
+
+
 # ---- seeded inputs shared by the CPU and the GPU module ---------------------------------------------------------------------
 def rng(*key):
   return np.random.default_rng([int(k) for k in key])

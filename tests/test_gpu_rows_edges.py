@@ -24,7 +24,7 @@ import torch
 
 from tests import rows_ref as R
 from tests.gpu_guard import (_ALIVE, BF, DEV, FLANK, PATTERN, Out, _abi, _release_inputs, _report, call,  # noqa: F401
-                             close_bf16, close_rel, close_sum, close_ulp, dev, exact, ptr)
+                             close_bf16, close_rel, close_sum, close_terms, close_ulp, dev, exact, ptr)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,15 +34,6 @@ def padded(a, ld, fill):
   out = np.full((a.shape[0], ld), fill, a.dtype)
   out[:, :a.shape[1]] = a
   return out
-
-
-def close_terms(case, out, terms, roundings):
-  """a float32 expression the kernel evaluates from already rounded float32 values: ``roundings`` half-ulps of the sum of the
-  magnitudes of its terms"""
-  ref = sum(terms)
-  err, bound = np.abs(np.asarray(out, np.float64) - ref), roundings * R.U24 * sum(np.abs(t) for t in terms)
-  _report(case, err, bound)
-  assert (err <= bound).all(), '%s: |err| %.3e, bound %.3e' % (case, err.max(), bound.max())
 
 
 # ---- bias gradient / bias add ---------------------------------------------------------------------------------------------

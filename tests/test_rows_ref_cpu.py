@@ -157,6 +157,48 @@ def test_bn_references_against_oracle_autograd(N, HW, C, blocks):
     _close(dx, gx.permute(0, 2, 3, 1).reshape(M, C), 64, what='dx')
 
 
+@pytest.mark.parametrize('mixup_type', [0, 1, 2])
+@pytest.mark.parametrize('Bin,H,W', [(2, 1, 4), (6, 3, 5)])
+def test_mixup_meansub_and_labels_reference(Bin, H, W, mixup_type):
+  r = R.rng(15, Bin, H, W, mixup_type)
+  img = r.integers(0, 256, (Bin, H, W, 3)).astype(np.float32)
+  y = np.eye(11, dtype=np.float32)[r.integers(0, 11, Bin)]
+  lam1, lam2 = r.random(Bin // 2).astype(np.float32), r.random(Bin // 2).astype(np.float32)
+  x = O.mean_image_subtraction(torch.from_numpy(img))
+  if mixup_type == 0:
+    xr, yr = x, torch.from_numpy(y)
+  else:
+    xr, yr, _ = O.mixup(x, torch.from_numpy(y), torch.from_numpy(lam1), keep_batch_size=(mixup_type == 2),
+                        lam2=torch.from_numpy(lam2))
+  out = R.mixup_meansub(img, mixup_type, lam1, lam2)
+  assert out.shape == (xr.shape[0], H + 6, W + 6, 4)
+  _close(out[:, 3:3 + H, 3:3 + W, :3], xr, 8, mag=256.0, what='mixed images')
+  halo = out.copy()
+  halo[:, 3:3 + H, 3:3 + W, :3] = 0
+  assert (halo == 0).all()
+  _close(sum(R.mixup_terms(y, mixup_type, lam1, lam2)), yr, 4, mag=1.0, what='mixed labels')
+  if mixup_type:      # lambda = 1 gives the first operand, lambda = 0 the second
+    one, zero = np.ones(Bin // 2, np.float32), np.zeros(Bin // 2, np.float32)
+    fa, fb, _ = R.mixup_operands(img, mixup_type, lam1, lam2)
+    assert np.array_equal(sum(R.mixup_terms(img, mixup_type, one, one)), fa)
+    assert np.array_equal(sum(R.mixup_terms(img, mixup_type, zero, zero)), fb)
+    if mixup_type == 2:
+      assert np.array_equal(fb[Bin // 2:], img[Bin // 2:][::-1]) and np.array_equal(fa[Bin // 2:], img[:Bin // 2])
+
+
+@pytest.mark.parametrize('wd,gs', [(1e-4, 1.0 / 128), (0.0, 1.0)])
+def test_sgd_reference(wd, gs):
+  r = R.rng(16)
+  n = 1027
+  w, a = r.standard_normal(n).astype(np.float32), (r.standard_normal(n) * 0.1).astype(np.float32)
+  g = (r.standard_normal(n) / gs).astype(np.float32)
+  ta, tw = R.sgd_terms(w, a, g, 0.1, 0.9, wd, gs)
+  wr, ar = torch.from_numpy(w.copy()), torch.from_numpy(a.copy())
+  O.momentum_step([wr], [torch.from_numpy(g) * np.float32(gs) + np.float32(wd) * torch.from_numpy(w)], [ar], 0.1, 0.9)
+  _close(sum(ta), ar, 8, what='accum')
+  _close(sum(tw), wr, 8, what='w')
+
+
 def test_layout_references():
   r = R.rng(13)
   w = r.standard_normal((5, 2, 3, 8)).astype(np.float32)
