@@ -230,6 +230,17 @@ static inline hipError_t asm_ensure_dyn_lds(Kern kern, int lds_bytes, bool (&don
   if (e == hipSuccess && slot >= 0) done[slot] = true;
   return e;
 }
+// One checked launch of KERN(a) with `lds` bytes of dynamic LDS.  Owns the per-device flag table of the instantiation, the
+// opt-in, the launch and the launch check; `name` is the kernel's name in the error strings.
+template <auto KERN, class Args>
+static inline int asm_launch_dyn_lds(const char* name, dim3 grid, dim3 block, int lds, hipStream_t st, const Args& a) {
+  static bool done[ASM_MAX_DEVICES] = {};
+  if (hipError_t e = asm_ensure_dyn_lds(KERN, lds, done); e != hipSuccess)
+    ASM_FAIL(ASM_EHIP, "%s: dynamic LDS opt-in: %s", name, hipGetErrorString(e));
+  ASM_LAUNCH(KERN, grid, block, lds, st, a);
+  ASM_CHECK_LAUNCH(name);
+  return ASM_OK;
+}
 // compute units of the current device (cached per device; 256 on MI355X)
 static inline int asm_num_cus() {
   static int cached[ASM_MAX_DEVICES] = {};

@@ -18,6 +18,7 @@
 // The products are accumulated in exactly the order of the parity-class launches (taps of a class in filter order, 16
 // output channels at a time), so the result is BIT-IDENTICAL to them (tests/test_gpu_conv.py).
 #include "common.h"
+#include "igemm_common.h"
 
 namespace {
 
@@ -62,14 +63,7 @@ __global__ __launch_bounds__(256, 1) void dgrad_s2_kernel(S2Args p) {
 
   // this workgroup's run of patches (XCD-contiguous, as the other persistent kernels)
   int t_begin, t_end;
-  {
-    const int nb = gridDim.x, q = nb >> 3, r = nb & 7;
-    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    const int per = p.patches / nb, extra = p.patches - per * nb;
-    t_begin = logical * per + (logical < extra ? logical : extra);
-    t_end = t_begin + per + (logical < extra ? 1 : 0);
-  }
+  even_run(xcd_contiguous(blockIdx.x, gridDim.x), gridDim.x, p.patches, t_begin, t_end);
 
   // ---- the wave's filter slice, once: fw[t][kk] = wt[c = 32 wn + l31][t][16 kk + 8 lhi .. + 8] ----
   bf16x8 fw[9][4];
@@ -148,10 +142,7 @@ __global__ __launch_bounds__(256, 1) void dgrad_s2_kernel(S2Args p) {
     if (patch + 1 < t_end) prefetch(patch + 1, avn, amkn);     // in flight under this patch's MFMAs and stores
 
     f32x16 acc[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[c][i] = 0.f;
+    zero_acc(acc);
     // class by class, a class's taps in filter order, 16 output channels at a time: the parity-class launches' order
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -222,7 +213,5 @@ int asm_dgrad_s2_launch(const asm_conv_desc* d, const void* dy, const void* wt, 
   a.N = d->N; a.Ho = d->Ho; a.Wo = d->Wo;
   a.ppr = d->Wo / 8; a.ppi = a.ppr * (d->Ho / 8); a.patches = a.ppi * d->N;
   const int grid = a.patches < 256 ? a.patches : 256;      // one persistent workgroup per CU
-  ASM_LAUNCH(dgrad_s2_kernel, dim3(grid), dim3(256), S2_LDS, (hipStream_t)stream, a);
-  ASM_CHECK_LAUNCH("dgrad_s2_kernel");
-  return ASM_OK;
+  return asm_launch_dyn_lds<dgrad_s2_kernel>("dgrad_s2_kernel", dim3(grid), dim3(256), S2_LDS, (hipStream_t)stream, a);
 }

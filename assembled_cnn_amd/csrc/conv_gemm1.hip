@@ -70,12 +70,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm1_kernel(IGemmArgs p) {
   const int wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN;
 
-  int logical;
-  {
-    const int nb = p.n_blocks, q = nb >> 3, r = nb & 7;
-    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int logical = xcd_contiguous(blockIdx.x, p.n_blocks);
   const int tile_m = (int)fd_div((unsigned)logical, p.fd_ntn);
   const int tile_n = logical - tile_m * p.n_tiles_n;
 
@@ -94,18 +89,15 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm1_kernel(IGemmArgs p) {
   for (int j = 0; j < XP; ++j) {
     const int m = tile_m * BM + r0 + j * RPP;
     bool ok = c_ok && m < p.M;
-    const unsigned img = fd_div((unsigned)m, p.fd_howo);
-    const unsigned rem = (unsigned)m - img * (unsigned)p.HoWo;
-    const unsigned ho = fd_div(rem, p.fd_wo);
-    const unsigned wo = rem - ho * (unsigned)p.Wo;
-    int nh = (int)ho * p.so - p.pad, nw = (int)wo * p.so - p.pad_w;
+    const Pixel px = decode_pixel((unsigned)m, p.fd_howo, p.HoWo, p.fd_wo, p.Wo);
+    int nh = (int)px.ho * p.so - p.pad, nw = (int)px.wo * p.so - p.pad_w;
     if (p.sd == 2) {
       ok = ok && (((nh | nw) & 1) == 0);
       nh >>= 1;
       nw >>= 1;
     }
     ok = ok && ((unsigned)nh < (unsigned)p.Hi) && ((unsigned)nw < (unsigned)p.Wi);
-    vx[j] = ok ? (img * (unsigned)p.x_img_pitch + (unsigned)nh * (unsigned)p.x_row_pitch +
+    vx[j] = ok ? (px.img * (unsigned)p.x_img_pitch + (unsigned)nh * (unsigned)p.x_row_pitch +
                   (unsigned)nw * (unsigned)p.x_pix_pitch + (unsigned)csw) * 2u
                : ASM_OOB;
   }
@@ -130,7 +122,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm1_kernel(IGemmArgs p) {
                                                (int)(kb + wtap), 0, 0);
   };
 
-  f32x16 acc[TN][TM];
+  f32x16 acc[TN][TM];   // (written out: through zero_acc two instantiations come out with other register counts)
 #pragma unroll
   for (int a = 0; a < TN; ++a)
 #pragma unroll
@@ -203,13 +195,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm1_kernel(IGemmArgs p) {
 template <int BM, int BN, int BK, int WGM, int WGN, bool STATS, int NS, bool PFA, bool POOL, bool BNRED = false>
 int launch1_one(const IGemmArgs& a, hipStream_t st) {
   using C1 = Cfg1<BM, BN, BK, WGM, WGN, NS>;
-  auto kern = igemm1_kernel<BM, BN, BK, WGM, WGN, STATS, NS, PFA, POOL, BNRED>;
-  static bool attr_done[ASM_MAX_DEVICES] = {};
-  if (hipError_t e = asm_ensure_dyn_lds(kern, C1::LDS, attr_done); e != hipSuccess)
-    ASM_FAIL(ASM_EHIP, "igemm1_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-  ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(64 * WGM * WGN), C1::LDS, st, a);
-  ASM_CHECK_LAUNCH("igemm1_kernel");
-  return ASM_OK;
+  return asm_launch_dyn_lds<igemm1_kernel<BM, BN, BK, WGM, WGN, STATS, NS, PFA, POOL, BNRED>>(
+      "igemm1_kernel", dim3(a.n_blocks), dim3(64 * WGM * WGN), C1::LDS, st, a);
 }
 
 template <int BM, int BN, int BK, int WGM, int WGN, int NS>

@@ -50,12 +50,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_kernel(IGemmArgs p) {
 
   // XCD-aware bijective remap: each XCD (bid % 8) gets a contiguous range of logical tiles, and
   // the N-tiles of one M-tile are adjacent, so the activation tile is re-read from that XCD's L2.
-  int logical;
-  {
-    const int nb = p.n_blocks, q = nb >> 3, r = nb & 7;
-    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int logical = xcd_contiguous(blockIdx.x, p.n_blocks);
   const int tile_m = logical / p.n_tiles_n;
   const int tile_n = logical - tile_m * p.n_tiles_n;
 
@@ -147,12 +142,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm_kernel(IGemmArgs p) {
   };
 
   f32x16 acc[TN][TM];
-#pragma unroll
-  for (int a = 0; a < TN; ++a)
-#pragma unroll
-    for (int b = 0; b < TM; ++b)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+  zero_acc(acc);
 
   const int KT = p.R * p.S * p.kchunks;
   const int l31 = lane & 31, lhi = lane >> 5;
@@ -243,12 +233,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm2_kernel(IGemmArgs p) {
   const int wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN;
 
-  int logical;
-  {
-    const int nb = p.n_blocks, q = nb >> 3, r = nb & 7;
-    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int logical = xcd_contiguous(blockIdx.x, p.n_blocks);
   const int tile_m0 = (int)fd_div((unsigned)logical, p.fd_ntn);
   const int tile_n = logical - tile_m0 * p.n_tiles_n;
   const int tile_m = tile_m0 + p.m_tile0;
@@ -267,12 +252,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm2_kernel(IGemmArgs p) {
   for (int j = 0; j < XP; ++j) {
     const int m = tile_m * BM + r0 + j * RPP;
     const bool live = c_ok && m < p.M;
-    const unsigned img = fd_div((unsigned)m, p.fd_howo);
-    const unsigned rem = (unsigned)m - img * (unsigned)p.HoWo;
-    const unsigned ho = fd_div(rem, p.fd_wo);
-    const unsigned wo = rem - ho * (unsigned)p.Wo;
-    const int bh = (int)ho * p.so - p.pad, bw = (int)wo * p.so - p.pad_w;
-    const unsigned base = img * (unsigned)p.x_img_pitch + (unsigned)csw;
+    const Pixel px = decode_pixel((unsigned)m, p.fd_howo, p.HoWo, p.fd_wo, p.Wo);
+    const int bh = (int)px.ho * p.so - p.pad, bw = (int)px.wo * p.so - p.pad_w;
+    const unsigned base = px.img * (unsigned)p.x_img_pitch + (unsigned)csw;
     unsigned roff[R], coff[S];
     bool rok[R], cok[S];
 #pragma unroll
@@ -340,7 +322,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void igemm2_kernel(IGemmArgs p) {
                                                  (int)vw[j], (int)wso, 0, 0);
   };
 
-  f32x16 acc[TN][TM];
+  f32x16 acc[TN][TM];   // (written out: through zero_acc one instantiation comes out with other register counts)
 #pragma unroll
   for (int a = 0; a < TN; ++a)
 #pragma unroll
@@ -472,12 +454,7 @@ __global__ __launch_bounds__(256) void igemm3_kernel(IGemmArgs p) {
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN;
-  int logical;
-  {
-    const int nb = p.n_blocks, q = nb >> 3, r = nb & 7;
-    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int logical = xcd_contiguous(blockIdx.x, p.n_blocks);
   const int tile_m0 = (int)fd_div((unsigned)logical, p.fd_ntn);
   const int tile_n = logical - tile_m0 * p.n_tiles_n;
   const int tile_m = tile_m0 + p.m_tile0;
@@ -509,11 +486,8 @@ __global__ __launch_bounds__(256) void igemm3_kernel(IGemmArgs p) {
 #pragma unroll
   for (int b = 0; b < TM; ++b) {
     const int m = tile_m * BM + wm * WTM + b * 32 + l31;
-    const unsigned mm = m < p.M ? (unsigned)m : 0u;
-    const unsigned img = fd_div(mm, p.fd_howo);
-    const unsigned rem = mm - img * (unsigned)p.HoWo;
-    const int h = (int)fd_div(rem, p.fd_wo);
-    const int w = (int)rem - h * p.Wo;
+    const Pixel px = decode_pixel(m < p.M ? (unsigned)m : 0u, p.fd_howo, p.HoWo, p.fd_wo, p.Wo);
+    const int h = (int)px.ho, w = (int)px.wo;
     unsigned mk = 0;
 #pragma unroll
     for (int t = 0; t < NTAP; ++t) {
@@ -539,12 +513,7 @@ __global__ __launch_bounds__(256) void igemm3_kernel(IGemmArgs p) {
   };
 
   f32x16 acc[TN][TM];
-#pragma unroll
-  for (int a = 0; a < TN; ++a)
-#pragma unroll
-    for (int b = 0; b < TM; ++b)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+  zero_acc(acc);
 
   unsigned fwo[KK];
 #pragma unroll
@@ -633,13 +602,7 @@ int launch3_one(const IGemmArgs& a, hipStream_t st) {
   using C = Cfg<128, BN, 64, 2, 2, false, STATS>;
   constexpr int LDS = cmax(cmax(NHB * HR * 128 + 2 * BN * 128, C::EPI), C::RED);
   static_assert(LDS <= 80 * 1024, "two workgroups per CU");
-  auto kern = igemm3_kernel<BN, STATS, PFA, HR, NHB, BNRED>;
-  static bool attr_done[ASM_MAX_DEVICES] = {};
-  if (hipError_t e = asm_ensure_dyn_lds(kern, LDS, attr_done); e != hipSuccess)
-    ASM_FAIL(ASM_EHIP, "igemm3_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-  ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(256), LDS, st, a);
-  ASM_CHECK_LAUNCH("igemm3_kernel");
-  return ASM_OK;
+  return asm_launch_dyn_lds<igemm3_kernel<BN, STATS, PFA, HR, NHB, BNRED>>("igemm3_kernel", dim3(a.n_blocks), dim3(256), LDS, st, a);
 }
 
 template <int HR, int NHB>
@@ -656,14 +619,12 @@ int launch3(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
 // is the layer one igemm3_kernel covers?
 bool igemm3_covers(const IGemmArgs& a, bool out_f32) {
   if (out_f32 || a.R != 3 || a.S != 3 || a.so != 1 || a.sd != 1 || a.y_strided || a.pool_dy) return false;
-  if (!((a.tsign > 0 && a.pad == 1 && a.pad_w == 1) || (a.tsign < 0 && a.pad == -1 && a.pad_w == -1))) return false;
-  if (a.wt0 != 0 || a.wtr != 3 || a.wts != 1) return false;
+  if (!pad1_window(a) || !whole_3x3_filter(a)) return false;
   const bool one_chunk = a.Ci == 64;      // asm_tuning.igemm3 >= 2: also the single-chunk layers (one halo buffer)
   if (one_chunk && asm_tune().igemm3 == 1) return false;
   if (a.Ci % 64 || a.Co <= 64 || a.Wi > ((one_chunk ? 256 : 192) - 1 - 128 - 2) / 2) return false;
   if (a.HoWo != a.Hi * a.Wi || a.Wo != a.Wi || a.M % a.HoWo) return false;
-  if (a.x_pix_pitch != a.Ci || a.x_row_pitch != a.Wi * a.Ci || a.x_img_pitch != a.Hi * a.Wi * a.Ci) return false;
-  return true;
+  return packed_input(a);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -718,14 +679,7 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(IGemmArgs p) {
   // this workgroup's run of (row-tile) patches; block b runs on XCD b % 8, so give XCD x the x-th eighth of the patches
   const int n_m = p.M >> 7;
   int t_begin, t_end;
-  {
-    const int nb = gridDim.x, q = nb >> 3, r = nb & 7;
-    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;   // bijective remap
-    const int per = n_m / nb, extra = n_m - per * nb;
-    t_begin = logical * per + (logical < extra ? logical : extra);
-    t_end = t_begin + per + (logical < extra ? 1 : 0);
-  }
+  even_run(xcd_contiguous(blockIdx.x, gridDim.x), gridDim.x, n_m, t_begin, t_end);
   const int tiles_x = p.Wi >> 4, tpi = tiles_x * (p.Hi >> 3);
 
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
@@ -800,12 +754,7 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(IGemmArgs p) {
     if (tile + 1 < t_end) load_halo(tile + 1, hv);   // in flight under the MFMAs and the stores of this patch
 
     f32x16 acc[TN][TM];
-#pragma unroll
-    for (int a = 0; a < TN; ++a)
-#pragma unroll
-      for (int b = 0; b < TM; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+    zero_acc(acc);
     // tap loop: fprop (tsign > 0) reads halo (py + r, px + s) with filter tap (r, s); the input gradient (tsign < 0)
     // reads halo (py + 2 - r, px + 2 - s) with the same filter tap (dx(h, w) = sum dy(h + 1 - r, w + 1 - s) . w(r, s))
 #pragma unroll
@@ -837,13 +786,7 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(IGemmArgs p) {
 template <int KO, int CI, int WGM, int WGN, bool STATS>
 int launch_halo_one(const IGemmArgs& a, hipStream_t st) {
   using H = HaloCfg<KO, CI>;
-  auto kern = conv_halo_kernel<KO, CI, WGM, WGN, STATS>;
-  static bool attr_done[ASM_MAX_DEVICES] = {};
-  if (hipError_t e = asm_ensure_dyn_lds(kern, H::LDS, attr_done); e != hipSuccess)
-    ASM_FAIL(ASM_EHIP, "conv_halo_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-  ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(256), H::LDS, st, a);
-  ASM_CHECK_LAUNCH("conv_halo_kernel");
-  return ASM_OK;
+  return asm_launch_dyn_lds<conv_halo_kernel<KO, CI, WGM, WGN, STATS>>("conv_halo_kernel", dim3(a.n_blocks), dim3(256), H::LDS, st, a);
 }
 
 template <int KO, int CI, int WGM, int WGN>
@@ -855,9 +798,7 @@ int launch_halo(const ConvLaunch& L, const IGemmArgs& a, hipStream_t st) {
 bool halo_covers(const IGemmArgs& a, bool out_f32) {
   if (out_f32 || a.R != 3 || a.S != 3 || a.so != 1 || a.sd != 1 || a.y_strided || a.bn_scale) return false;
   if (a.Hi % 8 || a.Wi % 16 || a.M != (a.HoWo / a.Wo) * a.Wo * (a.M / a.HoWo) || a.HoWo != a.Hi * a.Wi) return false;
-  if (a.x_pix_pitch != a.Ci || a.x_row_pitch != a.Wi * a.Ci || a.x_img_pitch != a.Hi * a.Wi * a.Ci) return false;
-  if (!((a.tsign > 0 && a.pad == 1 && a.pad_w == 1) || (a.tsign < 0 && a.pad == -1 && a.pad_w == -1))) return false;
-  if (a.wt0 != 0 || a.wtr != 3 || a.wts != 1) return false;
+  if (!packed_input(a) || !pad1_window(a) || !whole_3x3_filter(a)) return false;
   return (a.Ci == 32 || a.Ci == 64) && (a.Co == 32 || a.Co == 64);
 }
 
@@ -872,13 +813,8 @@ int launch2_one(const IGemmArgs& a, hipStream_t st) {
   if constexpr (SCHED == 0 && BK == 64 && BN >= 128 && !OUT_F32 && !POOL && ((R == 3 && S == 3) || (R == 1 && S == 1))) {
     if (R == 3) return launch2_one<BM, BN, BK, WGM, WGN, OUT_F32, STATS, R, S, NS, PFA, POOL, 1>(a, st);
   }
-  auto kern = igemm2_kernel<BM, BN, BK, WGM, WGN, OUT_F32, STATS, R, S, NS, PFA, POOL, SCHED, BNRED>;
-  static bool attr_done[ASM_MAX_DEVICES] = {};
-  if (hipError_t e = asm_ensure_dyn_lds(kern, C::LDS, attr_done); e != hipSuccess)
-    ASM_FAIL(ASM_EHIP, "igemm2_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-  ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(NTHR), C::LDS, st, a);
-  ASM_CHECK_LAUNCH("igemm2_kernel");
-  return ASM_OK;
+  return asm_launch_dyn_lds<igemm2_kernel<BM, BN, BK, WGM, WGN, OUT_F32, STATS, R, S, NS, PFA, POOL, SCHED, BNRED>>(
+      "igemm2_kernel", dim3(a.n_blocks), dim3(NTHR), C::LDS, st, a);
 }
 
 // the epilogue variants igemm2_kernel is instantiated with (launch2) for an R x S tap shape on a BM x BN x BK tile: every one
@@ -928,13 +864,8 @@ struct Launch2 {
 template <int BM, int BN, int BK, int WGM, int WGN, bool OUT_F32, bool STATS, bool BNRED = false>
 int launch_one(const IGemmArgs& a, hipStream_t st) {
   using C = Cfg<BM, BN, BK, WGM, WGN, OUT_F32, STATS>;
-  auto kern = igemm_kernel<BM, BN, BK, WGM, WGN, OUT_F32, STATS, BNRED>;
-  static bool attr_done[ASM_MAX_DEVICES] = {};
-  if (hipError_t e = asm_ensure_dyn_lds(kern, C::LDS, attr_done); e != hipSuccess)
-    ASM_FAIL(ASM_EHIP, "igemm_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-  ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(C::NT), C::LDS, st, a);
-  ASM_CHECK_LAUNCH("igemm_kernel");
-  return ASM_OK;
+  return asm_launch_dyn_lds<igemm_kernel<BM, BN, BK, WGM, WGN, OUT_F32, STATS, BNRED>>("igemm_kernel", dim3(a.n_blocks), dim3(C::NT),
+                                                                                   C::LDS, st, a);
 }
 
 template <int BM, int BN, int BK, int WGM, int WGN>
@@ -1029,7 +960,7 @@ ConvLaunch tiled(int family, ConvTile t, const IGemmArgs& a, ConvOut out, int M,
 ConvPlan single(const ConvLaunch& L) { return ConvPlan{1, {L, {}}, nullptr}; }
 ConvPlan no_plan(const char* why) { return ConvPlan{0, {}, why}; }
 
-// asm_dense_shaped as fprop_impl / dgrad_args describe the layer (they resolve a zero pitch to the packed one)
+// asm_dense_shaped (igemm_common.h: why there are two, and that they must agree) on the argument block of the launch
 bool dense_shaped(const IGemmArgs& a) {
   return a.Hi == 1 && a.Wi == 1 && a.HoWo == 1 && a.R == 1 && a.S == 1 && a.x_img_pitch == a.Ci && a.x_row_pitch == a.Ci &&
          a.x_pix_pitch == a.Ci;

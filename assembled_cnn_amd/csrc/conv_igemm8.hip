@@ -68,12 +68,7 @@ __global__ __launch_bounds__(512) void igemm8_kernel(IGemmArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;      // waves w and w + 4 share a SIMD: one of each group per SIMD
 
-  int logical;
-  {
-    const int nb = p.n_blocks, q = nb >> 3, r = nb & 7;
-    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int logical = xcd_contiguous(blockIdx.x, p.n_blocks);
   const int tile_m = (int)fd_div((unsigned)logical, p.fd_ntn);
   const int tile_n = logical - tile_m * p.n_tiles_n;
 
@@ -92,12 +87,9 @@ __global__ __launch_bounds__(512) void igemm8_kernel(IGemmArgs p) {
   for (int q = 0; q < 4; ++q) {
     const int m = tile_m * 256 + q * 64 + r0;
     const bool live = m < p.M;
-    const unsigned mm = live ? (unsigned)m : 0u;
-    const unsigned img = fd_div(mm, p.fd_howo);
-    const unsigned rem = mm - img * (unsigned)p.HoWo;
-    const int ho = (int)fd_div(rem, p.fd_wo);
-    const int wo = (int)rem - ho * p.Wo;
-    vb[q] = (img * (unsigned)p.x_img_pitch + (unsigned)ho * (unsigned)p.x_row_pitch + (unsigned)wo * (unsigned)p.x_pix_pitch +
+    const Pixel px = decode_pixel(live ? (unsigned)m : 0u, p.fd_howo, p.HoWo, p.fd_wo, p.Wo);
+    const int ho = (int)px.ho, wo = (int)px.wo;
+    vb[q] = (px.img * (unsigned)p.x_img_pitch + (unsigned)ho * (unsigned)p.x_row_pitch + (unsigned)wo * (unsigned)p.x_pix_pitch +
              (unsigned)csw) * 2u;
     unsigned mk = 0;
 #pragma unroll
@@ -141,12 +133,7 @@ __global__ __launch_bounds__(512) void igemm8_kernel(IGemmArgs p) {
   };
 
   f32x16 acc[2][4];                                // [filter half a][pixel half h * 2 + 32-row sub-tile b]
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+  zero_acc(acc);
 
   const int l31 = lane & 31, lhi = lane >> 5;
   // fragment byte offsets inside a half-tile: rows 32 apart share the swizzle term, k-substeps differ by an XOR of 32 bytes
@@ -259,13 +246,7 @@ int launch8_one(const IGemmArgs& a, hipStream_t st) {
   using C = Cfg<256, 256, 64, 2, 4, false, STATS>;
   constexpr int LDS = cmax(cmax(2 * 4 * 128 * 128, C::EPI), C::RED);
   static_assert(LDS <= 160 * 1024, "lds");
-  auto kern = igemm8_kernel<STATS, PFA, BNRED>;
-  static bool attr_done[ASM_MAX_DEVICES] = {};
-  if (hipError_t e = asm_ensure_dyn_lds(kern, LDS, attr_done); e != hipSuccess)
-    ASM_FAIL(ASM_EHIP, "igemm8_kernel: dynamic LDS opt-in: %s", hipGetErrorString(e));
-  ASM_LAUNCH(kern, dim3(a.n_blocks), dim3(512), LDS, st, a);
-  ASM_CHECK_LAUNCH("igemm8_kernel");
-  return ASM_OK;
+  return asm_launch_dyn_lds<igemm8_kernel<STATS, PFA, BNRED>>("igemm8_kernel", dim3(a.n_blocks), dim3(512), LDS, st, a);
 }
 
 }  // namespace
@@ -273,7 +254,7 @@ int launch8_one(const IGemmArgs& a, hipStream_t st) {
 // is the layer one igemm8_kernel covers?
 bool asm_igemm8_covers(const IGemmArgs& a, bool out_f32) {
   if (out_f32 || a.R != 3 || a.S != 3 || a.so != 1 || a.sd != 1 || a.y_strided || a.pool_dy) return false;
-  if (!((a.tsign > 0 && a.pad == 1 && a.pad_w == 1) || (a.tsign < 0 && a.pad == -1 && a.pad_w == -1))) return false;
+  if (!pad1_window(a)) return false;
   if (a.Ci % 64 || a.Co % 8) return false;
   const long long span = (long long)a.x_bytes + 2ll * (a.x_row_pitch + a.x_pix_pitch);
   return span < (long long)ASM_OOB;

@@ -49,12 +49,6 @@ struct IC8 {
   static constexpr int value = N;
 };
 
-__device__ __forceinline__ bf16x4 ds_read_tr(const unsigned char* p) {
-  typedef __attribute__((ext_vector_type(4))) short s4;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s4*)(const_cast<unsigned char*>(p)));
-}
-
 // 16-byte-chunk XOR swizzle for an LDS tile whose rows are RB bytes: the 4 pixel rows x 64 bytes one
 // transposing read touches must cover all 64 banks exactly once.
 template <int RB>
@@ -103,12 +97,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs p) {
   // XCD-aware bijective remap (block b runs on XCD b % 8, each XCD has its own L2): give every XCD a
   // contiguous range of logical blocks, i.e. whole pixel ranges (splits) / whole dy row-tiles, so the tiles
   // that share operands hit the same L2 instead of every XCD re-fetching every operand from HBM.
-  int bid;
-  {
-    const int nb = gridDim.x, q = nb >> 3, r = nb & 7;
-    const int b = blockIdx.x, xcd = b & 7, idx = b >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int bid = xcd_contiguous(blockIdx.x, gridDim.x);
   const int tiles = p.tiles_n * p.tiles_c;
   const int split = bid / tiles;
   bid -= split * tiles;
@@ -158,15 +147,11 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs p) {
         rxv[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, (mok && col_ok) ? offl : ASM_OOB, 0, 0);
         continue;
       }
-      const unsigned um = mok ? (unsigned)m : 0u;
-      const unsigned img = fd_div(um, p.fd_howo);
-      const unsigned rem = um - img * (unsigned)p.HoWo;
-      const unsigned ho = fd_div(rem, p.fd_wo);
-      const unsigned wo = rem - ho * (unsigned)p.Wo;
-      const int ih = (int)ho * p.so + tap_r - p.pad;
-      const int iw = (int)wo * p.so + tap_s - p.pad;
+      const Pixel px = decode_pixel(mok ? (unsigned)m : 0u, p.fd_howo, p.HoWo, p.fd_wo, p.Wo);
+      const int ih = (int)px.ho * p.so + tap_r - p.pad;
+      const int iw = (int)px.wo * p.so + tap_s - p.pad;
       const bool ok = mok && col_ok && ((unsigned)ih < (unsigned)p.Hi) && ((unsigned)iw < (unsigned)p.Wi);
-      const unsigned offx = (img * (unsigned)p.x_img_pitch + (unsigned)ih * (unsigned)p.x_row_pitch +
+      const unsigned offx = (px.img * (unsigned)p.x_img_pitch + (unsigned)ih * (unsigned)p.x_row_pitch +
                              (unsigned)iw * (unsigned)p.x_pix_pitch + (unsigned)tap_c) * 2u;
       rxv[j] = __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? offx : ASM_OOB, 0, 0);
     }
@@ -187,12 +172,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs p) {
   };
 
   f32x16 acc[NT][CT];
-#pragma unroll
-  for (int a = 0; a < NT; ++a)
-#pragma unroll
-    for (int b = 0; b < CT; ++b)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+  zero_acc(acc);
 
   // transposing-read lane geometry (32x32x16 fragment: channel = lane&31, reduction group = lane>>5)
   const int t16 = lane & 15;          // lane within its 16-lane group
@@ -214,17 +194,15 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs p) {
       for (int a = 0; a < NT; ++a) {
         const int cy = nbase + a * 32 + colsel + tcol;  // channel (element) index in the dy row
         const int o = ((cy & 4) << 1);
-        const bf16x4 y0 = ds_read_tr(ys + row * YROWB + ((((cy >> 3) ^ tr_swz<YROWB>(row)) << 4) | o));
-        const bf16x4 y1 = ds_read_tr(ys + row2 * YROWB + ((((cy >> 3) ^ tr_swz<YROWB>(row2)) << 4) | o));
-        fy[a] = __builtin_shufflevector(y0, y1, 0, 1, 2, 3, 4, 5, 6, 7);
+        fy[a] = tr_frag(ys + row * YROWB + ((((cy >> 3) ^ tr_swz<YROWB>(row)) << 4) | o),
+                        ys + row2 * YROWB + ((((cy >> 3) ^ tr_swz<YROWB>(row2)) << 4) | o));
       }
 #pragma unroll
       for (int b = 0; b < CT; ++b) {
         const int cx = cbase + b * 32 + colsel + tcol;
         const int o = ((cx & 4) << 1);
-        const bf16x4 x0 = ds_read_tr(xs + row * WROWB + ((((cx >> 3) ^ tr_swz<WROWB>(row)) << 4) | o));
-        const bf16x4 x1 = ds_read_tr(xs + row2 * WROWB + ((((cx >> 3) ^ tr_swz<WROWB>(row2)) << 4) | o));
-        fx[b] = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
+        fx[b] = tr_frag(xs + row * WROWB + ((((cx >> 3) ^ tr_swz<WROWB>(row)) << 4) | o),
+                        xs + row2 * WROWB + ((((cx >> 3) ^ tr_swz<WROWB>(row2)) << 4) | o));
       }
 #pragma unroll
       for (int a = 0; a < NT; ++a)
@@ -299,7 +277,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs p) {
   }
   }
 
-  // D[i = n_local][j = col_local]: col = lane&31, n = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
+  // store_acc_tile (igemm_common.h: the accumulator layout) written out: through the helper the ring form (LIN, NS = 2,
+  // BNW = 128) takes three more scalar registers
   float* out = p.out + (size_t)split * p.Co * p.cols;
   const int l31 = lane & 31, lhi = lane >> 5;
 #pragma unroll
@@ -350,12 +329,7 @@ __global__ __launch_bounds__(512) void wgrad8_kernel(WgradArgs p) {
   const int wn = wave >> 1, wc = wave & 1;
   const int nbase = wn * 64, cbase = wc * 128;
 
-  int bid;
-  {
-    const int nb = gridDim.x, q = nb >> 3, r = nb & 7;
-    const int b = blockIdx.x, xcd = b & 7, idx = b >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int bid = xcd_contiguous(blockIdx.x, gridDim.x);
   const int tiles = p.tiles_n * p.tiles_c;
   const int split = bid / tiles;
   bid -= split * tiles;
@@ -399,27 +373,18 @@ __global__ __launch_bounds__(512) void wgrad8_kernel(WgradArgs p) {
     if constexpr (LIN) {
       offx = ((unsigned)m * (unsigned)p.Ci + (unsigned)j0) * 2u;
     } else {
-      const unsigned um = (unsigned)min(m, p.M - 1);
-      const unsigned img = fd_div(um, p.fd_howo);
-      const unsigned rem = um - img * (unsigned)p.HoWo;
-      const unsigned ho = fd_div(rem, p.fd_wo);
-      const unsigned wo = rem - ho * (unsigned)p.Wo;
-      const int ih = (int)ho * p.so + dr;
-      const int iw = (int)wo * p.so + ds;
+      const Pixel px = decode_pixel((unsigned)min(m, p.M - 1), p.fd_howo, p.HoWo, p.fd_wo, p.Wo);
+      const int ih = (int)px.ho * p.so + dr;
+      const int iw = (int)px.wo * p.so + ds;
       ok &= (unsigned)((unsigned)ih < (unsigned)p.Hi) & (unsigned)((unsigned)iw < (unsigned)p.Wi);
-      offx = (img * (unsigned)p.x_img_pitch + (unsigned)ih * (unsigned)p.x_row_pitch + (unsigned)iw * (unsigned)p.x_pix_pitch +
+      offx = (px.img * (unsigned)p.x_img_pitch + (unsigned)ih * (unsigned)p.x_row_pitch + (unsigned)iw * (unsigned)p.x_pix_pitch +
               (unsigned)tap_c) * 2u;
     }
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lptr_t)(xdst + slot * BLK), 16, (int)(ok ? offx : ASM_OOB), 0, 0, 0);
   };
 
   f32x16 acc[2][4];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+  zero_acc(acc);
 
   // transposing-read lane geometry (wgrad_kernel): the two reads of a fragment are rows `row` and `row + 4` of the block
   const int t16 = lane & 15, g4 = lane >> 4;
@@ -501,20 +466,11 @@ __global__ __launch_bounds__(512) void wgrad8_kernel(WgradArgs p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the zero-fill requests past the end
 
   float* out = p.out + (size_t)split * p.Co * p.cols;
-  const int l31 = lane & 31, lhi = lane >> 5;
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int col = tile_c * 256 + cbase + b * 32 + l31;
-      if (col < p.cols) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int n = tile_n * 256 + nbase + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-          if (n < p.Co) out[(size_t)n * p.cols + col] = acc[a][b][r];
-        }
-      }
-    }
+    for (int b = 0; b < 4; ++b)
+      store_acc_tile(out, acc[a][b], tile_n * 256 + nbase + a * 32, tile_c * 256 + cbase + b * 32, p.Co, p.cols, lane);
 }
 
 // slab reduce: dw[i] = sum_k slab[k][i].  256 threads = 32 float4 columns x 8 split-lanes; every lane keeps 4
@@ -591,18 +547,10 @@ __global__ __launch_bounds__((WHalo<KF, CI, PH, PW>::NTHR)) void wgrad_halo_kern
   const int khalves = p.tiles_n;                     // K / KF workgroups per patch run
   const int tiles_x = p.Wi / PW, tpi = tiles_x * (p.Hi / PH);
   const int n_m = (p.M / (p.Hi * p.Wi)) * tpi;       // patches
-  int t_begin, t_end, logical, khalf;
-  {
-    const int nb = gridDim.x, q = nb >> 3, r = nb & 7;
-    const int bid = blockIdx.x, xcd = bid & 7, idx = bid >> 3;
-    const int lg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;   // XCD-contiguous runs of patches
-    logical = lg / khalves;
-    khalf = lg - logical * khalves;
-    const int runs = nb / khalves;
-    const int per = n_m / runs, extra = n_m - per * runs;
-    t_begin = logical * per + (logical < extra ? logical : extra);
-    t_end = t_begin + per + (logical < extra ? 1 : 0);
-  }
+  const int lg = xcd_contiguous(blockIdx.x, gridDim.x);   // XCD-contiguous runs of patches
+  const int logical = lg / khalves, khalf = lg - logical * khalves;
+  int t_begin, t_end;
+  even_run(logical, (int)gridDim.x / khalves, n_m, t_begin, t_end);
   const __amdgpu_buffer_rsrc_t rdy = make_rsrc(p.dy, p.dy_bytes);
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x, p.x_bytes);
 
@@ -670,10 +618,7 @@ __global__ __launch_bounds__((WHalo<KF, CI, PH, PW>::NTHR)) void wgrad_halo_kern
   };
 
   f32x16 acc[W::UPW];
-#pragma unroll
-  for (int i = 0; i < W::UPW; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  zero_acc(acc);
 
   // transposing-read lane geometry (see wgrad_kernel): lane l of a 32x32x16 operand = channel l & 31, pixels (l >> 5) * 8 ..
   const int t16 = lane & 15, g = lane >> 4;
@@ -700,9 +645,7 @@ __global__ __launch_bounds__((WHalo<KF, CI, PH, PW>::NTHR)) void wgrad_halo_kern
       bf16x8 fy[W::KT];
 #pragma unroll
       for (int kt = 0; kt < W::KT; ++kt) {
-        const unsigned char* a = ys + (kk * 16 + prow) * YRB + (kt * 32 + chan) * 2;
-        const bf16x4 y0 = ds_read_tr(a), y1 = ds_read_tr(a + 4 * YRB);
-        fy[kt] = __builtin_shufflevector(y0, y1, 0, 1, 2, 3, 4, 5, 6, 7);
+        fy[kt] = tr_frag(ys + (kk * 16 + prow) * YRB + (kt * 32 + chan) * 2, YRB);
       }
       bf16x8 fx;
 #pragma unroll
@@ -712,8 +655,7 @@ __global__ __launch_bounds__((WHalo<KF, CI, PH, PW>::NTHR)) void wgrad_halo_kern
           if (!(PAIRED && i < 4 && (i & 1))) {      // (the second unit of a pair multiplies the same x fragment)
             const int r = t / 3, q = t - r * 3;
             const unsigned tapo = (unsigned)((r * HWD + q) * XRB + (ct * 32 + chan) * 2);
-            const bf16x4 x0 = ds_read_tr(xs + hb0[kk] + tapo), x1 = ds_read_tr(xs + hb1[kk] + tapo);
-            fx = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
+            fx = tr_frag(xs + hb0[kk] + tapo, xs + hb1[kk] + tapo);   // (the two pixels may sit in different halo rows)
           }
           const bf16x8 fa = (W::KT == 1 || kt == 0) ? fy[0] : fy[W::KT - 1];   // static register indices only
           acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fx, acc[i], 0, 0, 0);
@@ -724,18 +666,10 @@ __global__ __launch_bounds__((WHalo<KF, CI, PH, PW>::NTHR)) void wgrad_halo_kern
   // this workgroup's partial dW: rows [khalf * KF, + KF) of slab [logical][K][9 * CI]
   const int cols = 9 * CI;
   float* out = p.out + ((size_t)logical * p.Co + (size_t)khalf * KF) * cols;
-  const int l31 = lane & 31, lhi = lane >> 5;
 #pragma unroll
   for (int i = 0; i < W::UPW; ++i) {
     int t, kt, ct;
-    if (unit_of(i, t, kt, ct)) {
-      const int col = t * CI + ct * 32 + l31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int n = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-        out[(size_t)n * cols + col] = acc[i][r];
-      }
-    }
+    if (unit_of(i, t, kt, ct)) store_acc_tile<false>(out, acc[i], kt * 32, t * CI + ct * 32, KF, cols, lane);   // whole tiles: no guards
   }
 }
 
@@ -918,22 +852,18 @@ WgradPlan plan_wgrad(const asm_conv_desc* d) {
   return p;
 }
 
-// one launch of the plan on kernel KERN, with the dynamic-LDS opt-in it needs above 64 KiB
+// one checked launch of the plan on kernel KERN
 template <auto KERN>
-int launch_wg(const WgradPlan& pl, const WgradArgs& a, hipStream_t st) {
-  static bool done[ASM_MAX_DEVICES] = {};
-  if (hipError_t e = asm_ensure_dyn_lds(KERN, (int)pl.lds, done); e != hipSuccess)
-    ASM_FAIL(ASM_EHIP, "conv wgrad: dynamic LDS opt-in: %s", hipGetErrorString(e));
-  ASM_LAUNCH(KERN, dim3(pl.grid), dim3(pl.block), pl.lds, st, a);
-  return ASM_OK;
+int launch_wg(const char* name, const WgradPlan& pl, const WgradArgs& a, hipStream_t st) {
+  return asm_launch_dyn_lds<KERN>(name, dim3(pl.grid), dim3(pl.block), (int)pl.lds, st, a);
 }
 
 // wgrad_kernel with 128-wide column tiles on the plan's dy-tile rows
 template <bool LIN, int NS>
 int launch_128(const WgradPlan& pl, const WgradArgs& a, hipStream_t st) {
-  if (pl.bnw == 128) return launch_wg<wgrad_kernel<128, 128, LIN, NS>>(pl, a, st);
-  if (pl.bnw == 64) return launch_wg<wgrad_kernel<64, 128, LIN, NS>>(pl, a, st);
-  return launch_wg<wgrad_kernel<32, 128, LIN, NS>>(pl, a, st);
+  if (pl.bnw == 128) return launch_wg<wgrad_kernel<128, 128, LIN, NS>>("wgrad_kernel", pl, a, st);
+  if (pl.bnw == 64) return launch_wg<wgrad_kernel<64, 128, LIN, NS>>("wgrad_kernel", pl, a, st);
+  return launch_wg<wgrad_kernel<32, 128, LIN, NS>>("wgrad_kernel", pl, a, st);
 }
 
 }  // namespace
@@ -992,13 +922,15 @@ extern "C" int asm_conv2d_wgrad(const asm_conv_desc* d, const void* x, const voi
   hipStream_t st = (hipStream_t)stream;
   int rc = ASM_OK;
   switch (pl.form) {
-    case WgradForm::halo: rc = on_halo(pl, [&](auto h) { return launch_wg<decltype(h)::kernel>(pl, a, st); }); break;
+    case WgradForm::halo: rc = on_halo(pl, [&](auto h) { return launch_wg<decltype(h)::kernel>("wgrad_halo_kernel", pl, a, st); }); break;
     case WgradForm::reg: rc = pl.lin ? launch_128<true, 0>(pl, a, st) : launch_128<false, 0>(pl, a, st); break;
     case WgradForm::ring: rc = launch_128<true, 2>(pl, a, st); break;
-    case WgradForm::big: rc = pl.lin ? launch_wg<wgrad8_kernel<true>>(pl, a, st) : launch_wg<wgrad8_kernel<false>>(pl, a, st); break;
+    case WgradForm::big:
+      rc = pl.lin ? launch_wg<wgrad8_kernel<true>>("wgrad8_kernel", pl, a, st) : launch_wg<wgrad8_kernel<false>>("wgrad8_kernel", pl, a, st);
+      break;
+    case WgradForm::dense: break;   // not reached: the dense form returned above, it has no WgradArgs
   }
   if (rc != ASM_OK) return rc;
-  ASM_CHECK_LAUNCH(pl.form == WgradForm::halo ? "wgrad_halo_kernel" : pl.form == WgradForm::big ? "wgrad8_kernel" : "wgrad_kernel");
   if (pl.slabs) {
     const size_t n = (size_t)d->K * a.cols;
     ASM_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)cdivz(n, 128)), dim3(256), 0, st,

@@ -1,11 +1,17 @@
-// Shared by the MFMA implicit-GEMM convolution kernels (conv_igemm.hip, conv_gemm1.hip): the argument block, the tile
-// configuration and the epilogue (bf16 pack through LDS, coalesced NHWC stores, fused batch-norm statistics, gradient
-// fan-in addend with its ReLU mask, pooled-gradient gather, inference batch norm).
+// Shared by the MFMA convolution kernels (conv_*.hip): the idioms all of them use (XCD-contiguous block order, patch runs,
+// pixel decode, accumulator zero fill and fp32 tile store, transposing fragment reads) and, for the implicit-GEMM kernels
+// (conv_igemm.hip, conv_gemm1.hip, conv_igemm8.hip), the argument block, the tile configuration and the epilogue (bf16 pack
+// through LDS, coalesced NHWC stores, fused batch-norm statistics, gradient fan-in addend with its ReLU mask, pooled-gradient
+// gather, inference batch norm).
 #pragma once
 #include "common.h"
 
 // ---- the [N,1,1,C] squeeze / excite / classifier layers (dense_small.hip) ----
 // Is d one?  A 1x1 image under a 1x1 filter with packed rows: the layer is a row-major product [N][C] x [K][C]^T.
+// Stated twice, and the two must agree: here on the caller's descriptor (a zero pitch means packed), which is all plan_wgrad
+// has, and as dense_shaped(const IGemmArgs&) in conv_igemm.hip on the argument block of a forward / input-gradient launch, in
+// which fprop_impl / dgrad_args have already resolved the pitches and an input gradient has swapped C and K.  The multiple-of-8
+// channel count asked for here is what check_desc / dgrad_check have required of such a block before it is planned.
 static inline bool asm_dense_shaped(const asm_conv_desc* d) {
   return d->H == 1 && d->W == 1 && d->Ho == 1 && d->Wo == 1 && d->R == 1 && d->S == 1 && d->C % 8 == 0 &&
          (d->x_img_pitch == 0 || d->x_img_pitch == d->C) && (d->x_row_pitch == 0 || d->x_row_pitch == d->C) &&
@@ -18,6 +24,97 @@ int asm_dense_small_launch(const void* p, int ldp, const void* q, int ldq, int M
 int asm_dense_small_wgrad_launch(const void* x, int ldx, const void* dy, int ldy, int M, int Cin, int Cout, float* dw, int ldw,
                                  hipStream_t st);
 static inline bool asm_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---- idioms every convolution kernel shares ----
+// XCD-contiguous block order.  Hardware block b runs on XCD b % 8 and every XCD has its own L2: logical block
+// xcd_contiguous(b, n_blocks) gives each XCD one contiguous range of the n_blocks logical blocks (the first n_blocks % 8 XCDs
+// one more than the rest), so that neighbours in the logical order -- the column tiles of a row tile, the splits of a pixel
+// range, the patches of a run -- re-read their shared operand from one L2.
+constexpr __host__ __device__ __forceinline__ int xcd_contiguous(int block, int n_blocks) {
+  const int q = n_blocks >> 3, r = n_blocks & 7;
+  const int xcd = block & 7, idx = block >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+// what every caller relies on: each logical block of [0, nb) is taken exactly once
+constexpr bool xcd_contiguous_bijective(int nb_max) {
+  for (int nb = 1; nb <= nb_max; ++nb) {
+    unsigned long long seen = 0;
+    for (int b = 0; b < nb; ++b) {
+      const int l = xcd_contiguous(b, nb);
+      if (l < 0 || l >= nb || ((seen >> l) & 1)) return false;
+      seen |= 1ull << l;
+    }
+  }
+  return true;
+}
+static_assert(xcd_contiguous_bijective(64), "xcd_contiguous must map [0, nb) onto itself");
+
+// Persistent kernels: the run [begin, end) of `total` items that workgroup `logical` of `runs` walks (the first total % runs
+// runs are one longer).
+__device__ __forceinline__ void even_run(int logical, int runs, int total, int& begin, int& end) {
+  const int per = total / runs, extra = total - per * runs;
+  begin = logical * per + (logical < extra ? logical : extra);
+  end = begin + per + (logical < extra ? 1 : 0);
+}
+
+// Output row m -> (image, row, column) by multiply-shift division.  m must be a row of the tensor: callers clamp theirs.
+struct Pixel {
+  unsigned img, ho, wo;
+};
+__device__ __forceinline__ Pixel decode_pixel(unsigned m, const FastDiv& fd_howo, int HoWo, const FastDiv& fd_wo, int Wo) {
+  Pixel px;
+  px.img = fd_div(m, fd_howo);
+  const unsigned rem = m - px.img * (unsigned)HoWo;
+  px.ho = fd_div(rem, fd_wo);
+  px.wo = rem - px.ho * (unsigned)Wo;
+  return px;
+}
+
+template <int N>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+}
+template <int A, int B>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[A][B]) {
+#pragma unroll
+  for (int a = 0; a < A; ++a) zero_acc(acc[a]);
+}
+
+// One 32 x 32 accumulator of v_mfma_f32_32x32x16 to fp32 out[n][col] (row pitch `cols`): register r of lane l holds row
+// n_first + (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), column col_first + (l & 31).  GUARDED: rows from Co and columns from cols
+// on are not written; without it the caller vouches for the whole tile (Co is not read).
+template <bool GUARDED = true>
+__device__ __forceinline__ void store_acc_tile(float* out, const f32x16& acc, int n_first, int col_first, int Co, int cols,
+                                               int lane) {
+  const int col = col_first + (lane & 31), lhi = lane >> 5;
+  if (!GUARDED || col < cols) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int n = n_first + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+      if (!GUARDED || n < Co) out[(size_t)n * cols + col] = acc[r];
+    }
+  }
+}
+
+// gfx950's transposing LDS read: every 16-lane group reads a 4 (row) x 16 (bf16 column) block and each lane receives the four
+// rows of one column
+__device__ __forceinline__ bf16x4 ds_read_tr(const unsigned char* p) {
+  typedef __attribute__((ext_vector_type(4))) short s4;
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) s4*)(const_cast<unsigned char*>(p)));
+}
+// The 8 reduction elements of a lane's 32x32x16 MFMA operand from a reduction-major LDS tile: two transposing reads, at the
+// lane's row (p0) and four rows on (p1, or p0 + 4 * row_stride_bytes where the tile's rows are evenly spaced).
+__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p0, const unsigned char* p1) {
+  const bf16x4 lo = ds_read_tr(p0), hi = ds_read_tr(p1);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p, int row_stride_bytes) {
+  return tr_frag(p, p + 4 * row_stride_bytes);
+}
 
 namespace asm_igemm {
 
@@ -91,6 +188,18 @@ struct ConvPlan {
 };
 // a dispatcher handed a variant its family was not instantiated with (plan and dispatcher disagree)
 static inline int conv_no_variant(const char* kernel, int epi) { ASM_FAIL(ASM_EINVAL, "conv: %s has no epilogue variant %d", kernel, epi); }
+
+// ---- what the coverage predicates of the 3x3 families ask, named once ----
+// the gathered tensor is dense NHWC
+static inline bool packed_input(const IGemmArgs& a) {
+  return a.x_pix_pitch == a.Ci && a.x_row_pitch == a.Wi * a.Ci && a.x_img_pitch == a.Hi * a.Wi * a.Ci;
+}
+// the taps of a pad-1 window around the pixel: a forward layer, or its input gradient
+static inline bool pad1_window(const IGemmArgs& a) {
+  return (a.tsign > 0 && a.pad == 1 && a.pad_w == 1) || (a.tsign < 0 && a.pad == -1 && a.pad_w == -1);
+}
+// loop tap (i, j) is filter tap (i, j) of a 3x3 filter (not the sub-filter of a parity class)
+static inline bool whole_3x3_filter(const IGemmArgs& a) { return a.wt0 == 0 && a.wtr == 3 && a.wts == 1; }
 
 template <int BK>
 __device__ __forceinline__ int swz(int row) {
@@ -180,11 +289,8 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& p, f32x16 (&acc)
     auto row_off = [&](int row, int m) -> size_t {
       if (patch_base >= 0) return (size_t)(patch_base + (row >> 4) * p.Wi + (row & 15)) * p.ldy + n0;
       if (p.y_strided) {   // workgroup-uniform: rows of a parity class scatter into the full-resolution tensor
-        const unsigned img = fd_div((unsigned)m, p.fd_howo);
-        const unsigned rem = (unsigned)m - img * (unsigned)p.HoWo;
-        const unsigned ho = fd_div(rem, p.fd_wo);
-        const unsigned wo = rem - ho * (unsigned)p.Wo;
-        return (size_t)p.y_base + (size_t)img * p.y_img_pitch + (size_t)ho * p.y_row_pitch + (size_t)wo * p.y_pix_pitch + n0;
+        const Pixel px = decode_pixel((unsigned)m, p.fd_howo, p.HoWo, p.fd_wo, p.Wo);
+        return (size_t)p.y_base + (size_t)px.img * p.y_img_pitch + (size_t)px.ho * p.y_row_pitch + (size_t)px.wo * p.y_pix_pitch + n0;
       }
       return (size_t)m * p.ldy + n0;
     };
@@ -244,11 +350,8 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& p, f32x16 (&acc)
       const int row = ps * RPO + orow;
       const int m = tile_m * BM + row;
       const bool ok = m < p.M && n0 < co8;
-      const unsigned mm = ok ? (unsigned)m : 0u;
-      const unsigned img = fd_div(mm, p.fd_howo);
-      const unsigned rem = mm - img * (unsigned)p.HoWo;
-      const unsigned ph = fd_div(rem, p.fd_wo);
-      const unsigned pw = rem - ph * (unsigned)p.Wo;
+      const Pixel px = decode_pixel(ok ? (unsigned)m : 0u, p.fd_howo, p.HoWo, p.fd_wo, p.Wo);
+      const unsigned img = px.img, ph = px.ho, pw = px.wo;
       const int H = p.pool_H, W = p.Wo;
       const int sh = p.pool_stride >> 1;                     // stride in {1, 2}
       const int th = (int)ph + p.pool_pad, tw = (int)pw + p.pool_pad;

@@ -182,6 +182,8 @@ BIG_WGRAD_SHAPES = [
     (2, 14, 14, 256, 256, 3, 2),     # strided gather, 98 pixels (< 2 steps)
     (2, 16, 16, 64, 256, 3, 1),      # 576 columns -> 3 tiles with a 64-column tail
     (5, 9, 9, 72, 264, 3, 1),        # K = 264: second row-tile has 8 valid rows; channel count not a power of two
+    (1, 9, 11, 40, 264, 3, 1),       # the 3x3 gather ragged on every side at once: 99 pixels (less than one eight-phase trip),
+                                     # 360 columns (tail of the second column tile), K = 264 (tail of the second row tile)
 ]
 
 
@@ -204,17 +206,20 @@ def test_wgrad_256x256_kernel_forced_vs_oracle(hip_lib, shape, splits, monkeypat
     assert plan[4] > 1, plan
   dw = torch.empty((K, k, k, Cn), dtype=torch.float32, device='cuda')
   ops.conv_wgrad(d, x.cuda(), dy.cuda(), dw)
-  wr = torch.zeros((K, k, k, Cn), requires_grad=True)
-  yr = O._conv_raw(x.float().permute(0, 3, 1, 2), wr.permute(1, 2, 3, 0), k, stride)
-  (gw,) = torch.autograd.grad(yr, [wr], dy.float().permute(0, 3, 1, 2))
+  wr = torch.zeros((K, k, k, Cn), dtype=torch.float64, requires_grad=True)      # the reference in fp64
+  yr = O._conv_raw(x.double().permute(0, 3, 1, 2), wr.permute(1, 2, 3, 0), k, stride)
+  (gw,) = torch.autograd.grad(yr, [wr], dy.double().permute(0, 3, 1, 2))
   r = util.rel_l2(dw.cpu(), gw)
   assert r <= 2e-3, 'wgrad8 rel_l2 %.3e (plan %s)' % (r, plan)
   # the same call with the 128-wide kernels gives the same numbers up to summation order
   util.set_knob(monkeypatch, 'ASM_WGRAD_BIG', '0')
   dw0 = torch.empty_like(dw)
   ops.conv_wgrad(d, x.cuda(), dy.cuda(), dw0)
-  assert _plan(hip_lib, d)[1] == 128
+  plan0 = _plan(hip_lib, d)
+  assert plan0[1] == 128
   assert util.rel_l2(dw, dw0) <= 1e-4
+  if plan0[4:] == plan[4:]:     # the same pixel split: both kernels add the same 16-pixel blocks in the same order
+    assert torch.equal(dw, dw0), 'wgrad8 differs from the 128-wide kernels on the same pixel split %s' % plan[4:]
   # deterministic (fixed-order slab reduce)
   util.set_knob(monkeypatch, 'ASM_WGRAD_BIG', '1')
   dw1 = torch.empty_like(dw)
