@@ -472,6 +472,58 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(size_t nvec, int C, F
   });
 }
 
+// ---- backward apply of a BigLittle merge layer (packed mask, no dz) + the big branch's share in the same pass ---------
+// The merge adds the nearest-upsampled big branch before its ReLU, so the big branch receives the 2 x 2 block sums of the
+// masked gradient g = dy * [mask bit] -- the operands this pass reads anyway.  One thread owns a 2 x 2 pixel block of its 8
+// channels: 4 x (dy, x, mask byte) in, 4 x dx and one block sum out; the separate block-sum pass (upsample_bwd_kernel<true>,
+// pool.hip: dy and the mask once more) disappears.  The sum runs in that kernel's order (r, then s) and is rounded to bf16
+// once, dx comes out of bwd_dx as above: both are the same bits.  for_each_vec walks the quads [N][Hs][Ws][C/8], so the
+// coefficients stay once per thread; a wave's lanes are consecutive (quad column, vector column), i.e. each of its loads
+// covers whole C-channel pixels (every second one of a row; the s = 0 / s = 1 loads of a trip interleave to the full row).
+__global__ __launch_bounds__(256) void bn_bwd_apply_bsum_kernel(size_t nquad, int C, FastDiv fd_vcols,
+                                                                const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
+                                                                const uint8_t* __restrict__ mask, const float* __restrict__ cA,
+                                                                const float* __restrict__ cB, const float* __restrict__ cC,
+                                                                bf16_t* __restrict__ dx, bf16_t* __restrict__ bsum,
+                                                                FastDiv fd_ws, FastDiv fd_hs, int Hs, int Ws) {
+  const float* const coef[3] = {cA, cB, cC};
+  const unsigned vcols = (unsigned)(C >> 3);
+  for_each_vec<3>(nquad, C, fd_vcols, coef, [&](size_t i, unsigned m, int vc, const float (&k)[3][8]) {
+    const unsigned nh = fd_div(m, fd_ws);
+    const unsigned j = m - nh * (unsigned)Ws;
+    const unsigned n = fd_div(nh, fd_hs);
+    const unsigned h = nh - n * (unsigned)Hs;
+    const unsigned p00 = (n * 2u * (unsigned)Hs + 2u * h) * (2u * (unsigned)Ws) + 2u * j;   // < M, and M * vcols < 2^31
+    size_t idx[4];
+    u32x4 vg[4], vx[4];
+    unsigned mk[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      idx[q] = (size_t)((p00 + (unsigned)(q >> 1) * 2u * (unsigned)Ws + (unsigned)(q & 1)) * vcols + (unsigned)vc);
+      vg[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(dy + idx[q] * 8));
+      vx[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(x + idx[q] * 8));
+      mk[q] = mask[idx[q]];
+    }
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float g[8], fx[8], o[8];
+      unpack8(vg[q], g);
+      unpack8(vx[q], fx);
+      mask8(g, mk[q]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        acc[e] += g[e];
+        o[e] = bwd_dx(k[0][e], g[e], k[1][e], fx[e], k[2][e]);
+      }
+      BN_ST_BWD(pack8(o), reinterpret_cast<u32x4*>(dx + idx[q] * 8));
+    }
+    *reinterpret_cast<u32x4*>(bsum + i * 8) = pack8(acc);
+  });
+}
+
 // ---- two batch norms behind ONE ReLU: the block-final BN and the projection-shortcut BN of a bottleneck ---------------
 // out = relu(bn_a(ya) + bn_b(yb)): both backward passes consume the same masked gradient g = dout * [out > 0].  Run as two
 // independent BN backwards that is 2 x (reduce: dout, y, mask; apply: dout, y, mask -> dy) = 20.5 B per element; here dout
@@ -923,6 +975,20 @@ extern "C" int asm_bn_bwd_apply(const void* dy, const void* x, const void* yout,
   launch_vecs(kernels[relu][dz_out != nullptr], stream, M, C, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)yout, coefA,
               coefB, coefC, (bf16_t*)dx, (bf16_t*)dz_out);
   ASM_CHECK_LAUNCH("bn_bwd_apply");
+  return ASM_OK;
+}
+
+extern "C" int asm_bn_bwd_apply_blocksum(const void* dy, const void* x, const uint8_t* relu_mask, int N, int H, int W, int C,
+                                         const float* coefA, const float* coefB, const float* coefC, void* dx,
+                                         void* block_sum, void* stream) {
+  ASM_REQUIRE(dy && x && relu_mask && dx && block_sum && coefA && coefB && coefC, "bn_bwd_apply_blocksum: null pointer");
+  ASM_REQUIRE(N > 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0 && C > 0 && C % 8 == 0,
+              "bn_bwd_apply_blocksum: bad shape (N=%d H=%d W=%d C=%d; H and W must be even)", N, H, W, C);
+  ASM_REQUIRE((size_t)N * H * W * (C / 8) < 0x7fffffffull, "bn_bwd_apply_blocksum: tensor too large");
+  const int Hs = H / 2, Ws = W / 2;
+  launch_vecs(bn_bwd_apply_bsum_kernel, stream, N * Hs * Ws, C, (const bf16_t*)dy, (const bf16_t*)x, relu_mask, coefA, coefB,
+              coefC, (bf16_t*)dx, (bf16_t*)block_sum, make_fastdiv((unsigned)Ws), make_fastdiv((unsigned)Hs), Hs, Ws);
+  ASM_CHECK_LAUNCH("bn_bwd_apply_blocksum");
   return ASM_OK;
 }
 

@@ -2,6 +2,7 @@
 // All are HBM-bound gathers with fp32 accumulation; backward passes are written in gather form
 // (each input pixel sums the outputs whose window covers it) so there are no atomics.
 #include "common.h"
+#include "blur3s2.h"
 
 namespace {
 
@@ -230,24 +231,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const bf16_t* __restr
 }
 
 // ---- blur pool (REFLECT pad (k-1)/2, binomial k x k / sum, stride) --------------------------------
-struct BlurCoef {
-  float a[8];  // normalised 1-D binomial; 2-D weight = a[r]*a[s] (exact: all factors are dyadic)
-};
-inline BlurCoef blur_coef(int k) {
-  static const int tri[8][7] = {{0}, {1}, {1, 1}, {1, 2, 1}, {1, 3, 3, 1}, {1, 4, 6, 4, 1}, {1, 5, 10, 10, 5, 1},
-                                {1, 6, 15, 20, 15, 6, 1}};
-  BlurCoef c;
-  int sum = 0;
-  for (int i = 0; i < k; ++i) sum += tri[k][i];
-  for (int i = 0; i < 8; ++i) c.a[i] = i < k ? (float)tri[k][i] / (float)sum : 0.f;
-  return c;
-}
-__device__ __forceinline__ int reflect(int i, int L) {
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
-}
-
+// (coefficients, REFLECT index and the stride-2 adjoint of one pixel: blur3s2.h, shared with sk_fused.hip)
 __global__ __launch_bounds__(256) void blur_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int N,
                                                        int H, int W, int C, int k, int stride, int Ho, int Wo,
                                                        BlurCoef cf) {
@@ -322,12 +306,8 @@ __global__ __launch_bounds__(256) void blur_bwd_kernel(const bf16_t* __restrict_
 
 // The workload's case -- 3 taps (1 2 1) / 4, stride 2, even H and W -- without the generic kernel's nest of tap loops and
 // divisibility tests (2.3 TB/s: 27 mostly-failing predicate evaluations per 16 bytes stored): one thread owns a 2 x 2
-// quad of dx, which draws on the 2 x 2 neighbourhood dy[i..i+1][j..j+1] only.  Per dimension (h = 2i + u):
-//   u = 0: tap 1 of output i                                      -> 1/2 g[i]
-//   u = 1: tap 0 of output i + 1 (if it exists), tap 2 of output i -> 1/4 g[i+1] + 1/4 g[i]
-//          h = 1 is also what the REFLECT pad shows at padded position 0 (tap 0 of output 0) -> + 1/4 g[0]
-// (the far-end reflection lands on tap positions no stride-2 output uses when the extent is even).  The terms are
-// added in the generic kernel's order, so the result is the same bits.
+// quad of dx, which draws on the 2 x 2 neighbourhood dy[i..i+1][j..j+1] only (blur3s2_bwd_pixel, blur3s2.h: the terms
+// are added in the generic kernel's order, so the result is the same bits).
 __global__ __launch_bounds__(256) void blur3s2_bwd_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ dx, int N,
                                                           int Hh, int Wh, int C, float a0, float a1, float a2) {
   const int vcols = C >> 3;
@@ -345,33 +325,16 @@ __global__ __launch_bounds__(256) void blur3s2_bwd_kernel(const bf16_t* __restri
       const size_t off = (((size_t)p.n * Hh + p.h + (ok ? a : 0)) * Wh + p.w + (ok ? b : 0)) * C + p.vc * 8;
       unpack8(ldv(dy, off), g[a][b]);
     }
-  // per dimension and parity: up to three (source, weight) terms in the generic kernel's order
-  const int src_odd[3] = {1, 0, 0};
-  const float wgt_odd[3] = {a0, a2, a0};
-  const bool okh[3] = {hv, true, p.h == 0}, okw[3] = {wv, true, p.w == 0};
   const int W2 = 2 * Wh;
 #pragma unroll
   for (int u = 0; u < 2; ++u)
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
       float acc[8];
+      blur3s2_bwd_pixel([&](int a, int b, float* t) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-#pragma unroll
-      for (int th = 0; th < (u ? 3 : 1); ++th) {
-        const int sh = u ? src_odd[th] : 0;
-        const float wh = u ? wgt_odd[th] : a1;
-        if (u && !okh[th]) continue;
-#pragma unroll
-        for (int tw = 0; tw < (v ? 3 : 1); ++tw) {
-          const int sw = v ? src_odd[tw] : 0;
-          const float ww = v ? wgt_odd[tw] : a1;
-          if (v && !okw[tw]) continue;
-          const float wgt = wh * ww;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[e] += g[sh][sw][e] * wgt;
-        }
-      }
+        for (int e = 0; e < 8; ++e) t[e] = g[a][b][e];
+      }, u != 0, v != 0, hv, wv, p.h == 0, p.w == 0, a0, a1, a2, acc);
       const size_t off = (((size_t)p.n * 2 * Hh + 2 * p.h + u) * W2 + 2 * p.w + v) * C + p.vc * 8;
       *reinterpret_cast<u32x4*>(dx + off) = pack8(acc);
     }

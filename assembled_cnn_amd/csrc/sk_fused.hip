@@ -12,6 +12,7 @@
 // bit-compatible with bn_apply -> sk_gap / sk_select; df is NOT rounded to bf16 (the un-fused path stored it), which
 // is strictly closer to the fp32 reference.  HBM-bound, 16-byte vectors, no atomics (fixed-order partials).
 #include "common.h"
+#include "blur3s2.h"
 
 namespace {
 
@@ -31,7 +32,8 @@ __device__ __forceinline__ void load_coef(const float* __restrict__ scale, const
     k.sh[e] = h0[e]; k.sh[e + 4] = h1[e];
   }
 }
-__device__ __forceinline__ void bnrelu8(const u32x4& vy, const Coef8& k, float* f) {
+template <class K>      // Coef8, or CoefLds (below) where the coefficients wait in LDS
+__device__ __forceinline__ void bnrelu8(const u32x4& vy, const K& k, float* f) {
   float y[8];
   unpack8(vy, y);
 #pragma unroll
@@ -97,7 +99,12 @@ __device__ __forceinline__ void lane_sum8(float (*red)[9], const float* v, float
 // f, its ReLU mask ([y * sc + sh > 0], as in the backward kernels) and the masked raw value of 8 channels of y.  The
 // statistics are sums of mask and mask * y (and the same times dV); xhat = (y - mean) / sigma is affine in y, so the
 // finalize turns them into the xhat sums per image -- the streaming loops carry no mean / sigma registers.
-__device__ __forceinline__ void bnrelu8m(const u32x4& vy, const Coef8& k, float* f, float* m, float* my) {
+struct CoefLds {
+  const float* sc;
+  const float* sh;
+};
+template <class K>
+__device__ __forceinline__ void bnrelu8m(const u32x4& vy, const K& k, float* f, float* m, float* my) {
   float y[8];
   unpack8(vy, y);
 #pragma unroll
@@ -189,6 +196,122 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 1) void sk_gap_bn_kernel(const 
   }
 }
 
+// ---- strided unit: the blur pool behind V folded into the passes around it ------------------------------------------------
+// A strided bottleneck runs its unit at stride 1 and blur-pools V (3 taps, stride 2, REFLECT; blocks.anti_aliased_downsample).
+// V has no other reader and dV no other writer, so neither needs to exist in HBM: the select pass blurs V out of LDS, and
+// the two backward passes rebuild each dV vector from the (four times smaller) gradient of the pooled tensor.
+struct PoolGeom {
+  int W, Hh, Wh;        // full-resolution width; pooled extents H / 2, W / 2
+  FastDiv fd_w;
+  float a0, a1, a2;     // blur_coef(3)
+};
+
+// dV of pixel r = h * W + w of one image, 8 channels: the terms, order and weights of blur3s2_bwd_kernel (pool.hip), rounded
+// to bf16 where that kernel stores dV.  gimg = the image's pooled gradient + the thread's channel offset.  Neighbouring
+// threads share the pooled values (a 2 x 2 quad of dV reads the same four vectors): the re-reads are L1 / L2 hits.
+__device__ __forceinline__ u32x4 dv_from_pooled(const bf16_t* __restrict__ gimg, const PoolGeom& pg, int F, int r) {
+  const int h = (int)fd_div((unsigned)r, pg.fd_w), w = r - h * pg.W;
+  const int i = h >> 1, j = w >> 1;
+  const bool u = h & 1, v = w & 1;
+  const bool hv = i + 1 < pg.Hh, wv = j + 1 < pg.Wh;
+  // the four neighbours are requested together (with the y vectors of the trip), and kept packed: a term unpacks its own
+  u32x4 g[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const bool ok = (a == 0 || (u && hv)) && (b == 0 || (v && wv));   // a neighbour no term uses re-reads g[0][0]
+      g[a][b] = ldv(gimg, ((size_t)(i + (ok ? a : 0)) * pg.Wh + j + (ok ? b : 0)) * F);
+    }
+  float acc[8];
+  blur3s2_bwd_pixel([&](int a, int b, float* t) { unpack8(g[a][b], t); }, u, v, hv, wv, i == 0, j == 0, pg.a0, pg.a1, pg.a2,
+                    acc);
+  return pack8(acc);
+}
+
+// blur(V) [N, H/2, W/2, F] straight from y.  grid (bands, N, column groups); block = fvb vector columns x rpb row lanes, a
+// thread keeps its 8 channels (coefficients and gates derived once, as in the select kernel below).  A band is bh output
+// rows: its 2 bh + 1 rows of V -- consecutive rows of the image, the top band's row -1 being REFLECT row 1 -- are computed
+// once each (not once per tap: the BN + ReLU + gate arithmetic is ~60 VALU operations per vector and a V value feeds up to
+// four outputs), rounded to bf16 and staged in LDS; the nine taps are then applied out of LDS in blur_fwd_kernel's order
+// with its weights, so the result is the same bits as select -> blur.  Even H and W: no tap reaches past the far edge.
+// bh = 2: one extra y row read per four (the band overlap), 5 x 7 KB of LDS for every unit of the workload -> 4 workgroups
+// per CU; bh = 1 reads every second row twice, bh = 4 leaves 2 workgroups per CU with a barrier in the middle.
+__global__ __launch_bounds__(256) void sk_select_blur_fwd_kernel(const bf16_t* __restrict__ y, const float* __restrict__ scale,
+                                                                 const float* __restrict__ shift,
+                                                                 const float* __restrict__ att, bf16_t* __restrict__ out,
+                                                                 int H, int W, int F, int fvb, int rpb, int bh,
+                                                                 FastDiv fd_wo, float b0, float b1, float b2) {
+  extern __shared__ u32x4 vband[];   // [2 bh + 1][W][fvb] vectors of 8 bf16
+  const int fv = F >> 3;
+  const int vcl = threadIdx.x % fvb, rr = threadIdx.x / fvb;
+  const int vc = blockIdx.z * fvb + vcl;
+  const int n = blockIdx.y;
+  const bool live = rr < rpb && vc < fv;
+  const int Ho = H >> 1, Wo = W >> 1;
+  const int ho0 = blockIdx.x * bh;
+  const int nbh = min(bh, Ho - ho0);
+  if (live) {
+    Coef8 k0, k1;
+    load_coef(scale, shift, vc * 8, k0);
+    load_coef(scale, shift, F + vc * 8, k1);
+    float a0[8];
+    gate8(att, n, F, vc * 8, a0);
+    const bf16_t* yn = y + (size_t)n * H * W * 2 * F + vc * 8;
+    const int npix = (2 * nbh + 1) * W;
+    const int first = (2 * ho0 - 1) * W;      // pixel index of the band's first row; negative only for the top band's row -1
+    constexpr int U = 2;
+    for (int p = rr; p < npix; p += U * rpb) {
+      u32x4 y0[U], y1[U];
+#pragma unroll
+      for (int q = 0; q < U; ++q) {
+        const int pq = p + q * rpb;
+        int gp = first + (pq < npix ? pq : p);
+        if (gp < 0) gp += 2 * W;              // REFLECT: row -1 is row 1
+        y0[q] = ldv(yn, (size_t)gp * 2 * F);
+        y1[q] = ldv(yn, (size_t)gp * 2 * F + F);
+      }
+#pragma unroll
+      for (int q = 0; q < U; ++q) {
+        const int pq = p + q * rpb;
+        if (pq >= npix) break;
+        float f0[8], f1[8], o[8];
+        bnrelu8(y0[q], k0, f0);
+        bnrelu8(y1[q], k1, f1);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = a0[e] * f0[e] + (1.0f - a0[e]) * f1[e];
+        vband[pq * fvb + vcl] = pack8(o);
+      }
+    }
+  }
+  __syncthreads();
+  if (live) {
+    const float bw[3] = {b0, b1, b2};
+    const int nout = nbh * Wo;
+    for (int q = rr; q < nout; q += rpb) {
+      const int oh = (int)fd_div((unsigned)q, fd_wo), ow = q - oh * Wo;
+      float acc[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const int lr = 2 * oh + r;            // band row 0 is image row 2 ho0 - 1
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+          int iw = 2 * ow + t - 1;
+          if (iw < 0) iw = 1;                 // REFLECT
+          float f[8];
+          unpack8(vband[(lr * W + iw) * fvb + vcl], f);
+          const float wgt = bw[r] * bw[t];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[e] += f[e] * wgt;
+        }
+      }
+      *reinterpret_cast<u32x4*>(out + (((size_t)n * Ho + ho0 + oh) * Wo + ow) * F + vc * 8) = pack8(acc);
+    }
+  }
+}
+
 // ---- V = a0 f0 + a1 f1 -----------------------------------------------------------------------------------------------
 // grid (chunks, N); block = F/8 vector columns x rpb row lanes: a thread keeps its 8 channels of one image, so the two
 // coefficient vectors and the gates (8 exponentials) are derived ONCE and the loop streams y -> V.  (Round 4: the
@@ -235,13 +358,20 @@ __global__ __launch_bounds__(256) void sk_select_bn_fwd_kernel(const bf16_t* __r
 // ---- datt[n][c] = a0 a1 sum_hw (f0 - f1) dV ;  datt[n][F + c] = -that ----------------------------------------------------
 // ST: also the per-image gradient statistics of the factorised batch-norm backward:
 //     stats[n][0][ch] = sum_hw [f > 0] dV,  stats[n][1][ch] = sum_hw [f > 0] dV y    (ch over the 2F conv channels)
-template <int NT, bool ST>
+// PG: `dv` is the gradient of the blur-pooled V [N, H/2, W/2, F] and every dV vector is rebuilt from it (dv_from_pooled);
+//     the thread-to-pixel decomposition and the order of the sums are those of the dV form, so every output keeps its bits.
+template <int NT, bool ST, bool PG>
 __global__ __launch_bounds__(NT, NT == 256 ? 4 : 1) void sk_bn_bwd_att_kernel(const bf16_t* __restrict__ y, const float* __restrict__ scale,
                                                            const float* __restrict__ shift, const bf16_t* __restrict__ dv,
                                                            const float* __restrict__ att, bf16_t* __restrict__ datt,
                                                            int HW, int F, int vcb, const float* __restrict__ mean,
-                                                           const float* __restrict__ invstd, float* __restrict__ stats) {
+                                                           const float* __restrict__ invstd, float* __restrict__ stats,
+                                                           PoolGeom pg) {
   __shared__ float red[NT][9];
+  // PG: the statistics form holds 40 accumulators and sits at the 128 registers a 1024-thread workgroup leaves a thread;
+  // the gather on top of that spilled 23 of them.  Its 32 coefficients wait in LDS instead ([scale0 shift0 scale1 shift1]
+  // x the <= 32 vector columns of the workgroup), read back per vector as broadcast 16-byte reads.
+  __shared__ float cfl[PG ? 4 * 256 : 1];
   const int vcols = F >> 3;
   const int vcl = threadIdx.x % vcb, rl = threadIdx.x / vcb, nrl = NT / vcb;
   const int vc = blockIdx.x * vcb + vcl;
@@ -249,11 +379,27 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 1) void sk_bn_bwd_att_kernel(co
   float acc[8], g0[8], x0[8], g1[8], x1[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = g0[e] = x0[e] = g1[e] = x1[e] = 0.f;
+  if (PG) {
+    if (rl == 0 && vc < vcols) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        cfl[vcl * 8 + e] = scale[vc * 8 + e];
+        cfl[256 + vcl * 8 + e] = shift[vc * 8 + e];
+        cfl[512 + vcl * 8 + e] = scale[F + vc * 8 + e];
+        cfl[768 + vcl * 8 + e] = shift[F + vc * 8 + e];
+      }
+    }
+    __syncthreads();
+  }
   if (vc < vcols && rl < nrl) {
-    Coef8 k0, k1;
-    load_coef(scale, shift, vc * 8, k0);
-    load_coef(scale, shift, F + vc * 8, k1);
-    auto consume = [&](const u32x4& v0, const u32x4& v1, const u32x4& vg) {
+    Coef8 r0, r1;
+    if (!PG) {
+      load_coef(scale, shift, vc * 8, r0);
+      load_coef(scale, shift, F + vc * 8, r1);
+    }
+    const CoefLds l0 = {cfl + vcl * 8, cfl + 256 + vcl * 8}, l1 = {cfl + 512 + vcl * 8, cfl + 768 + vcl * 8};
+    // one pixel's vectors into the sums; k0, k1: the two branches' coefficients (registers, or LDS for PG)
+    auto add_pixel = [&](const auto& k0, const auto& k1, const u32x4& v0, const u32x4& v1, const u32x4& vg) {
       float g[8];
       unpack8(vg, g);
       if (ST) {
@@ -272,6 +418,16 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 1) void sk_bn_bwd_att_kernel(co
         for (int e = 0; e < 8; ++e) acc[e] += (f0[e] - f1[e]) * g[e];
       }
     };
+    auto consume = [&](const u32x4& v0, const u32x4& v1, const u32x4& vg) {
+      if (PG) {
+        __asm__ volatile("" ::: "memory");     // the coefficient reads stay in the loop (hoisted, they are registers again)
+        add_pixel(l0, l1, v0, v1, vg);
+      } else {
+        add_pixel(r0, r1, v0, v1, vg);
+      }
+    };
+    const bf16_t* gimg = PG ? dv + (size_t)n * pg.Hh * pg.Wh * F + vc * 8 : nullptr;
+    auto load_dv = [&](int rq) { return PG ? dv_from_pooled(gimg, pg, F, rq) : ldv(dv, ((size_t)n * HW + rq) * F + vc * 8); };
     constexpr int U = ST ? 1 : 2;
     int r = rl;
     for (; r + (U - 1) * nrl < HW; r += U * nrl) {
@@ -281,14 +437,14 @@ __global__ __launch_bounds__(NT, NT == 256 ? 4 : 1) void sk_bn_bwd_att_kernel(co
         const size_t m = (size_t)n * HW + r + u * nrl;
         v0[u] = ldv(y, m * 2 * F + vc * 8);
         v1[u] = ldv(y, m * 2 * F + F + vc * 8);
-        vg[u] = ldv(dv, m * F + vc * 8);
+        vg[u] = load_dv(r + u * nrl);
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) consume(v0[u], v1[u], vg[u]);
     }
     for (; r < HW; r += nrl) {
       const size_t m = (size_t)n * HW + r;
-      consume(ldv(y, m * 2 * F + vc * 8), ldv(y, m * 2 * F + F + vc * 8), ldv(dv, m * F + vc * 8));
+      consume(ldv(y, m * 2 * F + vc * 8), ldv(y, m * 2 * F + F + vc * 8), load_dv(r));
     }
   }
   const bool leader = rl == 0 && vc < vcols;
@@ -455,12 +611,14 @@ __global__ __launch_bounds__(1024) void sk_bn_bwd_finalize_kernel(const float* _
 // Same (chunk, image) x (vector column, row lane) decomposition as the reducer: a thread keeps its 8 channels, so the
 // gates, ds / HW and the five per-channel coefficient vectors are loaded ONCE and the loop streams y, dV -> dy (the
 // one-vector-per-thread form re-derived 56 scalars for every 32 bytes moved and ran at 3.3 TB/s).
+// PG: dV rebuilt from the gradient of the blur-pooled V, as in sk_bn_bwd_att_kernel.
+template <bool PG>
 __global__ __launch_bounds__(256) void sk_bn_bwd_apply_kernel(const bf16_t* __restrict__ dv, const float* __restrict__ att,
                                                               const bf16_t* __restrict__ ds, const bf16_t* __restrict__ y,
                                                               const float* __restrict__ scale,
                                                               const float* __restrict__ shift, const float* __restrict__ cA,
                                                               const float* __restrict__ cB, const float* __restrict__ cC,
-                                                              bf16_t* __restrict__ dy, SkBnGeom g) {
+                                                              bf16_t* __restrict__ dy, SkBnGeom g, PoolGeom pg) {
   const int tid = threadIdx.x;
   const int vc = tid % g.vcols;
   const int rr = tid / g.vcols;
@@ -479,6 +637,7 @@ __global__ __launch_bounds__(256) void sk_bn_bwd_apply_kernel(const bf16_t* __re
     kC[e] = cC[vc * 8 + e];
   }
   sk_thread_setup(g, n, vc, att, ds, ab, u);
+  const bf16_t* gimg = PG ? dv + (size_t)n * pg.Hh * pg.Wh * g.F + cv * 8 : nullptr;
   const int r_begin = blockIdx.x * g.rows_per_chunk;
   const int r_end = min(g.HW, r_begin + g.rows_per_chunk);
   constexpr int U = 2;
@@ -487,9 +646,10 @@ __global__ __launch_bounds__(256) void sk_bn_bwd_apply_kernel(const bf16_t* __re
 #pragma unroll
     for (int q = 0; q < U; ++q) {
       const int rq = r + q * g.rpb;
-      const size_t m = (size_t)n * g.HW + (rq < r_end ? rq : r);
+      const int rc = rq < r_end ? rq : r;
+      const size_t m = (size_t)n * g.HW + rc;
       vy[q] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(y + m * C2 + vc * 8));
-      vg[q] = ldv(dv, m * g.F + cv * 8);
+      vg[q] = PG ? dv_from_pooled(gimg, pg, g.F, rc) : ldv(dv, m * g.F + cv * 8);
     }
 #pragma unroll
     for (int q = 0; q < U; ++q) {
@@ -590,18 +750,59 @@ extern "C" int asm_sk_select_bn_fwd(const void* y, const float* scale, const flo
   return ASM_OK;
 }
 
+// pooled: `dv` is the gradient of the blur-pooled V [N, H/2, W/2, F] (statistics form only), else nullptr
+// The strided unit's folded blur pool covers the case blur3s2_bwd_kernel serves: 3 taps, stride 2, even H and W.
+#define SKB_OK(name)                                                                                                    \
+  ASM_REQUIRE(k == 3 && stride == 2, name ": blur filter size %d / stride %d not supported (3 / 2 only)", k, stride);    \
+  ASM_REQUIRE(H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0, name ": H=%d W=%d must be even", H, W);                        \
+  const int HW = H * W;                                                                                                 \
+  SKF_OK(name)
+
+static PoolGeom make_pool_geom(int H, int W) {
+  const BlurCoef cf = blur_coef(3);
+  return PoolGeom{W, H / 2, W / 2, make_fastdiv((unsigned)W), cf.a[0], cf.a[1], cf.a[2]};
+}
+
+// Band height and column group of sk_select_blur_fwd_kernel: 2 output rows (5 rows of V) per band, and as many of the F / 8
+// vector columns (<= 32) as keep the band within 40 KB of LDS -- 4 workgroups per CU.
+constexpr int SKB_BAND = 2;
+constexpr int SKB_MAX_W = 512;          // 5 rows x 512 pixels x one 16-byte column = 40 KB
+constexpr size_t SKB_LDS = 40 * 1024;
+
+extern "C" int asm_sk_select_bn_blur_fwd(const void* y, const float* scale, const float* shift, const float* att, void* out,
+                                         int N, int H, int W, int F, int k, int stride, void* stream) {
+  SKB_OK("sk_select_bn_blur_fwd");
+  ASM_REQUIRE(y && scale && shift && att && out, "sk_select_bn_blur_fwd: null pointer");
+  ASM_REQUIRE(W <= SKB_MAX_W, "sk_select_bn_blur_fwd: W=%d above %d", W, SKB_MAX_W);
+  const int fv = F / 8, rows = 2 * SKB_BAND + 1;
+  int fvb = fv < 32 ? fv : 32;
+  while (fvb > 1 && (size_t)rows * W * fvb * 16 > SKB_LDS) fvb = cdiv(fvb, 2);
+  const int groups = cdiv(fv, fvb);
+  ASM_REQUIRE(groups <= 65535, "sk_select_bn_blur_fwd: too many column groups");
+  const BlurCoef cf = blur_coef(3);
+  const unsigned lds = (unsigned)((size_t)rows * W * fvb * 16);
+  ASM_LAUNCH(sk_select_blur_fwd_kernel, dim3(cdiv(H / 2, SKB_BAND), N, groups), dim3(256), lds, (hipStream_t)stream,
+                     (const bf16_t*)y, scale, shift, att, (bf16_t*)out, H, W, F, fvb, 256 / fvb, SKB_BAND,
+                     make_fastdiv((unsigned)(W / 2)), cf.a[0], cf.a[1], cf.a[2]);
+  ASM_CHECK_LAUNCH("sk_select_bn_blur_fwd");
+  return ASM_OK;
+}
+
 static int sk_att_impl(const void* y, const float* scale, const float* shift, const void* dv, const float* att, void* datt,
-                       int N, int HW, int F, const float* mean, const float* invstd, float* stats, void* stream) {
+                       int N, int HW, int F, const float* mean, const float* invstd, float* stats, void* stream,
+                       const PoolGeom* pooled = nullptr) {
   SKF_OK("sk_select_bn_bwd_att");
   ASM_REQUIRE(y && scale && shift && dv && att && datt, "sk_select_bn_bwd_att: null pointer");
   const int vcb = image_pass_vcb(N, F);
   const dim3 grid(cdiv(F / 8, vcb), N);
   hipStream_t st = (hipStream_t)stream;
-#define LAUNCH_ATT(NT, ST)                                                                                          \
-  ASM_LAUNCH((sk_bn_bwd_att_kernel<NT, ST>), grid, dim3(NT), 0, st, (const bf16_t*)y, scale, shift, (const bf16_t*)dv, \
-                     att, (bf16_t*)datt, HW, F, vcb, mean, invstd, stats)
-  if (stats) { if (HW >= 512) LAUNCH_ATT(1024, true); else LAUNCH_ATT(256, true); }
-  else { if (HW >= 512) LAUNCH_ATT(1024, false); else LAUNCH_ATT(256, false); }
+  const PoolGeom pg = pooled ? *pooled : PoolGeom{};
+#define LAUNCH_ATT(NT, ST, PG)                                                                                          \
+  ASM_LAUNCH((sk_bn_bwd_att_kernel<NT, ST, PG>), grid, dim3(NT), 0, st, (const bf16_t*)y, scale, shift, (const bf16_t*)dv, \
+                     att, (bf16_t*)datt, HW, F, vcb, mean, invstd, stats, pg)
+  if (pooled) { if (HW >= 512) LAUNCH_ATT(1024, true, true); else LAUNCH_ATT(256, true, true); }
+  else if (stats) { if (HW >= 512) LAUNCH_ATT(1024, true, false); else LAUNCH_ATT(256, true, false); }
+  else { if (HW >= 512) LAUNCH_ATT(1024, false, false); else LAUNCH_ATT(256, false, false); }
 #undef LAUNCH_ATT
   ASM_CHECK_LAUNCH("sk_select_bn_bwd_att");
   return ASM_OK;
@@ -617,6 +818,16 @@ extern "C" int asm_sk_select_bn_bwd_att_stats(const void* y, const float* scale,
                                               float* grad_stats, int N, int HW, int F, void* stream) {
   ASM_REQUIRE(mean && invstd && grad_stats, "sk_select_bn_bwd_att_stats: null pointer");
   return sk_att_impl(y, scale, shift, dv, att, datt, N, HW, F, mean, invstd, grad_stats, stream);
+}
+
+extern "C" int asm_sk_select_bn_bwd_att_stats_blur(const void* y, const float* scale, const float* shift, const float* mean,
+                                                   const float* invstd, const void* dpool, const float* att, void* datt,
+                                                   float* grad_stats, int N, int H, int W, int F, int k, int stride,
+                                                   void* stream) {
+  SKB_OK("sk_select_bn_bwd_att_stats_blur");
+  ASM_REQUIRE(mean && invstd && grad_stats, "sk_select_bn_bwd_att_stats_blur: null pointer");
+  const PoolGeom pg = make_pool_geom(H, W);
+  return sk_att_impl(y, scale, shift, dpool, att, datt, N, HW, F, mean, invstd, grad_stats, stream, &pg);
 }
 
 extern "C" int asm_sk_bn_bwd_finalize(const float* grad_stats, const float* mask_stats, const float* att, const void* ds,
@@ -654,9 +865,23 @@ extern "C" int asm_sk_bn_bwd_apply(const void* dv, const float* att, const void*
   SKF_OK("sk_bn_bwd_apply");
   ASM_REQUIRE(dv && att && ds && y && scale && shift && coefA && coefB && coefC && dy, "sk_bn_bwd_apply: null pointer");
   const SkBnGeom g = make_geom(N, HW, F);
-  ASM_LAUNCH(sk_bn_bwd_apply_kernel, dim3(g.chunks, N), dim3(256), 0, (hipStream_t)stream,
+  ASM_LAUNCH(sk_bn_bwd_apply_kernel<false>, dim3(g.chunks, N), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)dv, att, (const bf16_t*)ds, (const bf16_t*)y, scale, shift, coefA, coefB, coefC,
-                     (bf16_t*)dy, g);
+                     (bf16_t*)dy, g, PoolGeom{});
   ASM_CHECK_LAUNCH("sk_bn_bwd_apply");
+  return ASM_OK;
+}
+
+extern "C" int asm_sk_bn_bwd_apply_blur(const void* dpool, const float* att, const void* ds, const void* y,
+                                        const float* scale, const float* shift, const float* coefA, const float* coefB,
+                                        const float* coefC, void* dy, int N, int H, int W, int F, int k, int stride,
+                                        void* stream) {
+  SKB_OK("sk_bn_bwd_apply_blur");
+  ASM_REQUIRE(dpool && att && ds && y && scale && shift && coefA && coefB && coefC && dy, "sk_bn_bwd_apply_blur: null pointer");
+  const SkBnGeom g = make_geom(N, HW, F);
+  ASM_LAUNCH(sk_bn_bwd_apply_kernel<true>, dim3(g.chunks, N), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)dpool, att, (const bf16_t*)ds, (const bf16_t*)y, scale, shift, coefA, coefB, coefC,
+                     (bf16_t*)dy, g, make_pool_geom(H, W));
+  ASM_CHECK_LAUNCH("sk_bn_bwd_apply_blur");
   return ASM_OK;
 }

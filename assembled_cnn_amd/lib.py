@@ -193,6 +193,7 @@ SIGNATURES = {
     'asm_bn_bwd_finalize': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'asm_bn_bwd_finalize_raw': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'asm_bn_bwd_apply': (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'asm_bn_bwd_apply_blocksum': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     'asm_maxpool3x3s2_fwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     'asm_maxpool3x3s2_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     'asm_avgpool_fwd': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
@@ -209,12 +210,15 @@ SIGNATURES = {
     'asm_sk_select_bwd_f': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'asm_sk_gap_bn': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     'asm_sk_select_bn_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    'asm_sk_select_bn_blur_fwd': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'asm_sk_select_bn_bwd_att': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'asm_sk_bn_bwd_blocks': (_I, [_I, _I, _I]),
     'asm_sk_bn_bwd_reduce': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     'asm_sk_bn_bwd_apply': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    'asm_sk_bn_bwd_apply_blur': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'asm_sk_gap_bn_stats': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     'asm_sk_select_bn_bwd_att_stats': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    'asm_sk_select_bn_bwd_att_stats_blur': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'asm_sk_bn_bwd_finalize': (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'asm_se_scale_fwd': (_I, [_P, _P, _P, _I, _I, _I, _P]),
     'asm_se_scale_bwd_e': (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),

@@ -339,6 +339,15 @@ class SavedBN(NamedTuple):
   shift: torch.Tensor
 
 
+class LazyV(NamedTuple):
+  """What the select pass of a fused selective-kernel unit reads: V = a0 f0 + a1 f1 is left to its first reader (Var.lazy_v)"""
+  y: torch.Tensor
+  scale: torch.Tensor
+  shift: torch.Tensor
+  att: torch.Tensor
+  F: int
+
+
 class RedCtx(NamedTuple):
   """What a convolution reading the output of a conv -> BN [-> + shortcut] [-> ReLU] layer needs to reduce that layer's
   batch-norm backward sums (Var.red) while it writes the gradient: the layer's pre-BN convolution output and its packed
@@ -356,6 +365,9 @@ class Var(object):
       projection shortcut) read (dy, mask) directly, so dz is never written;
     * ``pool_grad``: (dpool [N,Hp,Wp,C], k, stride, pad, count_valid) stands for avgpool_bwd(dpool); a 1x1 stride-1
       convolution reading this activation gathers it in its input-gradient epilogue (asm_conv2d_dgrad_pooled).
+  A third form stands alone: ``blur_grad`` = (dpool, k, stride) stands for blurpool_bwd(dpool) while it is the WHOLE gradient
+  of the V of a selective-kernel unit whose blur pool ran fused (``lazy_v``, nn.blur_pool); the unit's backward passes take it
+  (take_blur_grad) and rebuild dV in registers.
   Anything else just reads ``.grad``, which materialises the sum through the ordinary kernels.  What always holds:
     * only a tensor nobody else reads (``grad_owned``) is updated in place;
     * a reader that bypasses ``.grad`` (take_masked_grad) cannot drop a pending pooled term;
@@ -364,13 +376,13 @@ class Var(object):
       is dropped by ANY change of the gradient's value (another term, a mask, a replacement).
   ``pre_dy``: this layer's batch-norm backward has been run by the block-final layer (ops.bn_bwd_dual); its dy waits here."""
   __slots__ = ('_data', 'shape', '_grad', 'grad_mask', 'grad_owned', 'needs_grad', 'deferred', 'bn_ctx', 'red_ctx', 'red',
-               'pre_dy', 'pool_grad')
+               'pre_dy', 'pool_grad', 'lazy_v', 'blur_grad')
 
   def __init__(self, data, shape=None, needs_grad=True):
     self._data = data
     self.shape = tuple(data.shape) if data is not None else tuple(shape)
     self.needs_grad = needs_grad
-    self._grad = self.grad_mask = self.pool_grad = self.red = self.pre_dy = None
+    self._grad = self.grad_mask = self.pool_grad = self.red = self.pre_dy = self.lazy_v = self.blur_grad = None
     self.grad_owned = False
     # set by conv_bn in the forward pass: SavedBN (deferred: its batch norm is left to the first reader), SavedBN, RedCtx
     self.deferred = self.bn_ctx = self.red_ctx = None
@@ -380,7 +392,19 @@ class Var(object):
     if self.bn_pending():
       s = self.deferred
       self._data = ops.bn_apply(s.y, s.M, s.C, s.scale, s.shift, None, 0, False)
+    elif self._data is None and self.lazy_v is not None:
+      s, self.lazy_v = self.lazy_v, None
+      self._data = ops.sk_select_bn_fwd(s.y, s.scale, s.shift, s.att, s.F)
     return self._data
+
+  def take_lazy_v(self, k: int, stride: int):
+    """-> the LazyV of a selective-kernel output nobody has read, if blur_pool(k, stride) of it can run as one pass with the
+    select (ops.sk_blur_ok), and V is then never made; else None (``data`` makes V)"""
+    s = self.lazy_v
+    if self._data is not None or s is None or not ops.sk_blur_ok(self.shape[1], self.shape[2], k, stride):
+      return None
+    self.lazy_v = None
+    return s
 
   def bn_pending(self) -> bool:
     """a deferred batch norm that nobody has applied: no tensor yet"""
@@ -393,6 +417,7 @@ class Var(object):
   @property
   def grad(self):
     """the gradient as one tensor (materialises a lazy mask and a pending pooled term)"""
+    self._scatter_blur_grad()
     if self.grad_mask is not None:
       self.set_grad(ops.mask_apply(self._grad, self.grad_mask), True)
     if self.pool_grad is not None:
@@ -414,6 +439,7 @@ class Var(object):
   def add_grad(self, g, owned: bool, mask=None):
     """+= g [* mask].  ``owned`` says whether g may later be updated in place by us."""
     self.red = None
+    self._scatter_blur_grad()
     if mask is not None:
       if self._grad is None:
         self._grad, self.grad_mask, self.grad_owned = g, mask, False
@@ -447,9 +473,28 @@ class Var(object):
       self._grad = ops.add_bf16(self._grad, ops.avgpool_bwd(dp, self.shape, k, stride, pad, count_valid))
     self.grad_owned = True
 
+  def add_blur_grad(self, dp, k, stride):
+    """+= blurpool_bwd(dp), left in pooled form while it is the only term (take_blur_grad)"""
+    self.red = None
+    if self._grad is None and self.pool_grad is None and self.blur_grad is None:
+      self.blur_grad = (dp, k, stride)
+    else:
+      self.add_grad(ops.blurpool_bwd(dp, self.shape, k, stride), True)
+
+  def take_blur_grad(self):
+    """-> (dpool, k, stride) if that is the whole gradient (and clear it), else None (.grad has everything)"""
+    bg, self.blur_grad = self.blur_grad, None
+    return bg
+
+  def _scatter_blur_grad(self):
+    if self.blur_grad is not None:       # (the only term: add_blur_grad)
+      (dp, k, stride), self.blur_grad = self.blur_grad, None
+      self.set_grad(ops.blurpool_bwd(dp, self.shape, k, stride), True)
+
   def take_masked_grad(self):
     """-> (gradient tensor, packed mask or None) without materialising the product.  A pooled contribution nobody
     gathered (take_pool_grad) is scattered first."""
+    self._scatter_blur_grad()
     if self.pool_grad is not None:
       self.grad      # the getter scatters it (and materialises a lazy mask)
     return self._grad, self.grad_mask
@@ -477,11 +522,13 @@ class Var(object):
     return dy
 
   def no_grad_yet(self) -> bool:
-    return self._grad is None and self.pre_dy is None
+    return self._grad is None and self.pre_dy is None and self.blur_grad is None
 
   def held(self):
     """-> (gradient tensor, its lazy mask, parked dy, pooled term) as they are: whoever reads them on another stream keeps
-    them alive with this; tests look at the lazy state without touching it"""
+    them alive with this; tests look at the lazy state without touching it.  (A pending blur-pool term is written out first:
+    only the unit that owns it reads it in pooled form, and it must not look like no gradient at all.)"""
+    self._scatter_blur_grad()
     return self._grad, self.grad_mask, self.pre_dy, self.pool_grad
 
 
@@ -850,12 +897,18 @@ def conv_bn(ctx: Ctx, x: Var, conv: ConvKernel, bn: BatchNorm, stride: int, relu
         residual.park_dy(dy_sc)
       else:
         # the input gradient that wrote dout may have reduced (sum dz, sum dz * y) already (Var.red)
-        dy, dz = ops.bn_bwd(dout, y, bmask, brelu, M, Cn, gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta),
-                            route == 'dz', raw_part=out.take_red(dout, bmask))
+        # the BigLittle merge's lazy route: the 2x2 block sum of (dout, mask) rides in this layer's backward apply pass, which
+        # reads the pair anyway (bmask is mask_t here: a ReLU layer with a residual never borrows the incoming mask)
+        bsum_hw = ((d.Ho, d.Wo) if (route == 'lazy' and rm == 2 and bmask is mask_t
+                                    and ops.bn_blocksum_ok(bmask, brelu, False, d.Ho, d.Wo)) else None)
+        dy, dz, *bsum = ops.bn_bwd(dout, y, bmask, brelu, M, Cn, gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta),
+                                   route == 'dz', raw_part=out.take_red(dout, bmask), block_sum=bsum_hw)
       a.notify_grad(bn.gamma)
       if route in ('lazy', 'dz', 'dout'):
         g, g_mask, owned = (dout, mask_t, False) if route == 'lazy' else (dz, None, True) if route == 'dz' else (dout, None, False)
-        if rm == 2:                    # the BigLittle merge: the 2x2 block sum reads the pair itself
+        if rm == 2 and bsum:
+          g, g_mask, owned = bsum[0], None, True
+        elif rm == 2:                  # the BigLittle merge: the 2x2 block sum reads the pair itself
           g, g_mask, owned = ops.upsample2x_bwd(g, g_mask), None, True
         accum_grad(residual, g, owned, mask=g_mask)
       conv_input_grad(conv, d, x, x_t, dy)
@@ -972,23 +1025,32 @@ class SKUnit(object):
       s = Var(ops.sk_gap_bn(y, scale, shift, F_))                       # mean_hw(f0 + f1)  :131-134
     z = conv_bn(ctx, s, self.fc1, self.bn1, 1, relu=True)               # :137-143
     att, fc2_bwd, _ = conv_plain(ctx, z, self.fc2, out_f32=True)         # :144-148 (fp32 logits)
-    v = Var(ops.sk_select_bn_fwd(y, scale, shift, att, F_))             # :149-152
+    if factor and ops.sk_blur_ok(d.Ho, d.Wo, 3, 2):
+      # V is left to its first reader (Var.data).  In a strided bottleneck that reader is the block's blur pool, which has
+      # no other input and whose output is all that is read of V: nn.blur_pool then runs select + blur as one pass, and
+      # hands its gradient back in pooled form (Var.blur_grad) for the two backward passes below to rebuild dV from --
+      # neither V nor dV reaches memory.  Any other reader gets V from the select pass, as before.
+      v = Var(None, (N, d.Ho, d.Wo, F_))
+      v.lazy_v = LazyV(y, scale, shift, att, F_)
+    else:
+      v = Var(ops.sk_select_bn_fwd(y, scale, shift, att, F_))           # :149-152
     if ctx.tape is not None:
       bwd_z = ctx.tape.pop()        # re-sequenced below: select_bwd_att -> fc2 -> (bn1, fc1) -> BN backward -> conv
       x_t = x.data
 
       def bwd():
-        dv = v.grad
+        blur = v.take_blur_grad() if factor else None     # (dpool, k, stride): dV = blurpool_bwd(dpool), not written
+        dv, blur = (blur[0], blur[1:]) if blur is not None else (v.grad, None)
         if dv is None:
           raise RuntimeError('sk unit backward: no gradient reached this layer')
         if factor:
-          datt, grad_stats = ops.sk_select_bn_bwd_att(y, scale, shift, dv, att, F_, mean, invstd)
+          datt, grad_stats = ops.sk_select_bn_bwd_att(y, scale, shift, dv, att, F_, mean, invstd, blur=blur)
         else:
           datt, grad_stats = ops.sk_select_bn_bwd_att(y, scale, shift, dv, att, F_), None
         fc2_bwd(datt)                      # -> z.grad
         bwd_z()                            # -> s.grad
         dy = ops.sk_bn_bwd(dv, att, s.grad, y, scale, shift, gamma, mean, invstd, a.g(bn.gamma), a.g(bn.beta), F_,
-                           grad_stats, mask_stats if factor else None)
+                           grad_stats, mask_stats if factor else None, blur=blur)
         s.grad = None
         a.notify_grad(bn.gamma)
         conv_input_grad(conv, d, x, x_t, dy)
@@ -1076,6 +1138,15 @@ def blur_pool(ctx: Ctx, x: Var, k: int, stride: int) -> Var:
     raise NotImplementedError('anti_alias_filter_size=1 hard-codes NCHW slicing in the reference (blocks.py:79-84)')
   if ctx.dry:
     return Var(None, (N, ops.blur_out_size(H, k, stride), ops.blur_out_size(W, k, stride), Cn))
+  lazy = x.take_lazy_v(k, stride) if ctx.tape is not None else None
+  if lazy is not None:            # the V of a selective-kernel unit that nobody has read: select + blur in one pass
+    y = Var(ops.sk_select_bn_blur_fwd(lazy.y, lazy.scale, lazy.shift, lazy.att, lazy.F, k, stride))
+
+    def bwd_lazy():
+      x.add_blur_grad(y.grad, k, stride)
+      y.grad = None
+    ctx.record(bwd_lazy)
+    return y
   y = Var(ops.blurpool_fwd(x.data, k, stride))
   if ctx.tape is not None:
     def bwd():

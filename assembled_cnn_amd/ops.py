@@ -475,14 +475,25 @@ def _bn_bwd_coeffs(part, M, Cn, gamma, mean, invstd, dgamma, dbeta, co, raw=Fals
             _ptr(co[0]), _ptr(co[1]), _ptr(co[2]), _stream()), what)
 
 
-def bn_bwd(dy, x, yout, relu, M, Cn, gamma, mean, invstd, dgamma, dbeta, want_dz, raw_part=None):
+def bn_blocksum_ok(yout, relu, want_dz, H, W) -> bool:
+  """can bn_bwd(block_sum=(H, W)) serve this layer?  A packed mask, no dz, even H and W, and a C-ABI provider that has the
+  entry point (a CPU test double written before it does not: the caller keeps the separate block-sum pass).
+  ASM_BL_SUM=0: never"""
+  return (knob('ASM_BL_SUM', '1') != '0' and relu and not want_dz and yout is not None and yout.dtype == torch.uint8
+          and H > 0 and W > 0 and H % 2 == 0 and W % 2 == 0 and getattr(L(), 'asm_bn_bwd_apply_blocksum', None) is not None)
+
+
+def bn_bwd(dy, x, yout, relu, M, Cn, gamma, mean, invstd, dgamma, dbeta, want_dz, raw_part=None, block_sum=None):
   """-> dx, dz (dz None unless want_dz).  dgamma/dbeta: f32 [C] views, overwritten.
   ``yout`` is the bf16 forward output or (uint8) the packed ReLU mask from bn_apply(want_mask=True).
   ``raw_part``: the (sum dz, sum dz * y) partials the input gradient that wrote ``dy`` already reduced in its epilogue
-  (conv_dgrad_bnred): the reduce pass over (dy, x) is skipped."""
+  (conv_dgrad_bnred): the reduce pass over (dy, x) is skipped.
+  ``block_sum`` = (H, W) of the layer (where bn_blocksum_ok): -> dx, dz, bsum with bsum [N, H/2, W/2, C] the 2x2 block sums
+  of dy * [mask bit], i.e. upsample2x_bwd(dy, mask), written by the apply pass."""
   rk = 0 if not relu else (2 if yout.dtype == torch.uint8 else 1)
   red_bytes = 0.0 if raw_part is not None else (4.0 + (0.125 if rk == 2 else 2.0 if rk == 1 else 0.0))
-  ev = _bn_ev(M * Cn * (red_bytes + 4.0 + 2.0 + (2.0 if want_dz else 0.0) + (0.125 if rk == 2 else 2.0 if rk == 1 else 0.0)))
+  ev = _bn_ev(M * Cn * (red_bytes + 4.0 + 2.0 + (2.0 if want_dz else 0.0) + (0.125 if rk == 2 else 2.0 if rk == 1 else 0.0)
+                        + (0.5 if block_sum is not None else 0.0)))
   co = empty((3, Cn), F32, dy)
   part = raw_part
   if part is None:
@@ -491,6 +502,15 @@ def bn_bwd(dy, x, yout, relu, M, Cn, gamma, mean, invstd, dgamma, dbeta, want_dz
                                 _ptr(mean), _ptr(invstd), _ptr(part), _stream()), 'bn_bwd_reduce')
   _bn_bwd_coeffs(part, M, Cn, gamma, mean, invstd, dgamma, dbeta, co, raw=raw_part is not None)
   dx = torch.empty_like(x)
+  if block_sum is not None:
+    H, W = block_sum
+    Nb = M // (H * W)
+    bsum = empty((Nb, H // 2, W // 2, Cn), BF16, dy)
+    check(L().asm_bn_bwd_apply_blocksum(_ptr(dy), _ptr(x), _ptr(yout), Nb, H, W, Cn, _ptr(co[0]), _ptr(co[1]), _ptr(co[2]),
+                                        _ptr(dx), _ptr(bsum), _stream()), 'bn_bwd_apply_blocksum')
+    if ev is not None:
+      ev.record()
+    return dx, None, bsum
   dz = torch.empty_like(x) if want_dz else None
   check(L().asm_bn_bwd_apply(_ptr(dy), _ptr(x), _ptr(yout if relu else None), rk, M, Cn,
                              _ptr(co[0]), _ptr(co[1]), _ptr(co[2]), _ptr(dx), _ptr(dz), _stream()), 'bn_bwd_apply')
@@ -691,10 +711,37 @@ def sk_select_bn_fwd(y, scale, shift, att, F_):
   return v
 
 
-def sk_select_bn_bwd_att(y, scale, shift, dv, att, F_, mean=None, invstd=None):
-  """-> datt, or with (mean, invstd): (datt, per-image gradient statistics [N, 2, 2F] f32)"""
+_SK_BLUR_ENTRIES = ('asm_sk_select_bn_blur_fwd', 'asm_sk_select_bn_bwd_att_stats_blur', 'asm_sk_bn_bwd_apply_blur')
+
+
+def sk_blur_ok(H, W, k, stride) -> bool:
+  """can the strided SK unit's blur pool ride in its select / gate-gradient / BN-apply passes (V and dV never written)?  The
+  case the workload has -- 3 taps, stride 2, even H and W -- and a C-ABI provider that has the entry points (a CPU test
+  double written before them does not: the unit keeps select -> blur_pool).  ASM_SK_BLUR=0: never"""
+  return (knob('ASM_SK_BLUR', '1') != '0' and k == 3 and stride == 2 and H > 0 and W > 0 and H % 2 == 0 and W % 2 == 0
+          and W <= 512 and all(getattr(L(), e, None) is not None for e in _SK_BLUR_ENTRIES))
+
+
+def sk_select_bn_blur_fwd(y, scale, shift, att, F_, k, stride):
+  """blurpool_fwd(sk_select_bn_fwd(...), k, stride) in one pass (where sk_blur_ok) -> [N, H/2, W/2, F]"""
+  N, H, W, _ = y.shape
+  out = empty((N, H // 2, W // 2, F_), BF16, y)
+  check(L().asm_sk_select_bn_blur_fwd(_ptr(y), _ptr(scale), _ptr(shift), _ptr(att), _ptr(out), N, H, W, F_, k, stride,
+                                      _stream()), 'sk_select_bn_blur_fwd')
+  return out
+
+
+def sk_select_bn_bwd_att(y, scale, shift, dv, att, F_, mean=None, invstd=None, blur=None):
+  """-> datt, or with (mean, invstd): (datt, per-image gradient statistics [N, 2, 2F] f32).
+  ``blur`` = (k, stride) (statistics form, where sk_blur_ok): ``dv`` is the gradient of the blur-pooled V."""
   N, H, W, _ = y.shape
   datt = empty((N, 1, 1, 2 * F_), BF16, y)
+  if blur is not None:
+    st = empty((N, 2, 2 * F_), F32, y)
+    check(L().asm_sk_select_bn_bwd_att_stats_blur(_ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), _ptr(dv),
+                                                  _ptr(att), _ptr(datt), _ptr(st), N, H, W, F_, blur[0], blur[1], _stream()),
+          'sk_select_bn_bwd_att_stats_blur')
+    return datt, st
   if mean is not None:
     st = empty((N, 2, 2 * F_), F32, y)
     check(L().asm_sk_select_bn_bwd_att_stats(_ptr(y), _ptr(scale), _ptr(shift), _ptr(mean), _ptr(invstd), _ptr(dv), _ptr(att),
@@ -705,14 +752,17 @@ def sk_select_bn_bwd_att(y, scale, shift, dv, att, F_, mean=None, invstd=None):
   return datt
 
 
-def sk_bn_bwd(dv, att, ds, y, scale, shift, gamma, mean, invstd, dgamma, dbeta, F_, grad_stats=None, mask_stats=None):
+def sk_bn_bwd(dv, att, ds, y, scale, shift, gamma, mean, invstd, dgamma, dbeta, F_, grad_stats=None, mask_stats=None,
+              blur=None):
   """BN backward of the SK unit's 2F-channel batch norm from dV (df is rebuilt in registers) -> dy [N,H,W,2F].
-  With the per-image statistics of sk_select_bn_bwd_att / sk_gap_bn the reduce pass is replaced by a tiny finalize."""
+  With the per-image statistics of sk_select_bn_bwd_att / sk_gap_bn the reduce pass is replaced by a tiny finalize.
+  ``blur`` = (k, stride) (with the statistics, where sk_blur_ok): ``dv`` is the gradient of the blur-pooled V."""
   N, H, W, C2 = y.shape
   HW, M = H * W, N * H * W
   co = empty((3, C2), F32, y)
   if grad_stats is not None and mask_stats is not None:
-    ev = _bn_ev(M * (2.0 * C2 + 2.0 * F_ + 2.0 * C2))         # one pass over (y, dV), one write of dy
+    # one pass over (y, dV) -- or the four times smaller pooled gradient --, one write of dy
+    ev = _bn_ev(M * (2.0 * C2 + (0.5 if blur is not None else 2.0) * F_ + 2.0 * C2))
     check(L().asm_sk_bn_bwd_finalize(_ptr(grad_stats), _ptr(mask_stats), _ptr(att), _ptr(ds), N, HW, F_, _ptr(gamma),
                                      _ptr(mean), _ptr(invstd), _ptr(dgamma), _ptr(dbeta), _ptr(co[0]), _ptr(co[1]),
                                      _ptr(co[2]), _stream()), 'sk_bn_bwd_finalize')
@@ -726,6 +776,15 @@ def sk_bn_bwd(dv, att, ds, y, scale, shift, gamma, mean, invstd, dgamma, dbeta, 
                                    _ptr(invstd), N, HW, F_, _ptr(part), _stream()), 'sk_bn_bwd_reduce')
     _bn_bwd_coeffs(part, M, C2, gamma, mean, invstd, dgamma, dbeta, co)
   dy = torch.empty_like(y)
+  if blur is not None:
+    if grad_stats is None or mask_stats is None:
+      raise ValueError('sk_bn_bwd: the pooled-gradient form needs the per-image statistics')
+    check(L().asm_sk_bn_bwd_apply_blur(_ptr(dv), _ptr(att), _ptr(ds), _ptr(y), _ptr(scale), _ptr(shift), _ptr(co[0]),
+                                       _ptr(co[1]), _ptr(co[2]), _ptr(dy), N, H, W, F_, blur[0], blur[1], _stream()),
+          'sk_bn_bwd_apply_blur')
+    if ev is not None:
+      ev.record()
+    return dy
   check(L().asm_sk_bn_bwd_apply(_ptr(dv), _ptr(att), _ptr(ds), _ptr(y), _ptr(scale), _ptr(shift), _ptr(co[0]),
                                 _ptr(co[1]), _ptr(co[2]), _ptr(dy), N, HW, F_, _stream()), 'sk_bn_bwd_apply')
   if ev is not None:

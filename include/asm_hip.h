@@ -294,6 +294,13 @@ int asm_bn_bwd_finalize_raw(const float* partial, int blocks, int M, int C, cons
 int asm_bn_bwd_apply(const void* dy, const void* x, const void* yout, int relu, int M, int C,
                      const float* coefA, const float* coefB, const float* coefC, void* dx,
                      void* dz_out, void* stream);
+/* asm_bn_bwd_apply for a layer [N, H, W, C] with a packed mask (relu == 2, no dz) whose masked gradient also flows through
+ * an UpSampling2D((2,2)) -- the BigLittle merge: dx as above and, in the same pass, block_sum [N, H/2, W/2, C] bf16 = the
+ * 2 x 2 block sums of dy * [mask bit], bit-identical to asm_upsample2x_bwd_masked (whose launch and second read of dy and
+ * the mask it saves).  H and W must be even (ASM_EINVAL otherwise). */
+int asm_bn_bwd_apply_blocksum(const void* dy, const void* x, const uint8_t* relu_mask, int N, int H, int W, int C,
+                              const float* coefA, const float* coefB, const float* coefC, void* dx, void* block_sum,
+                              void* stream);
 
 /* Two batch norms behind one ReLU -- out = relu(bn_a(xa) + bn_b(xb)), the block-final and the projection-shortcut batch
  * norm of a bottleneck (nets/resnet_model.py:92-96) -- share the masked gradient g = dy * [mask bit]: one reduce and one
@@ -414,6 +421,23 @@ int asm_sk_select_bn_bwd_att_stats(const void* y, const float* scale, const floa
 int asm_sk_bn_bwd_finalize(const float* grad_stats, const float* mask_stats, const float* att, const void* ds, int N,
                            int HW, int F, const float* gamma, const float* mean, const float* invstd, float* dgamma,
                            float* dbeta, float* coefA, float* coefB, float* coefC, void* stream);
+/* A strided bottleneck blur-pools V (asm_blurpool_fwd, k = 3, stride = 2) and nothing else reads V, so for that case the
+ * blur pool rides in the three passes around it and neither V nor dV reaches memory:
+ *   asm_sk_select_bn_blur_fwd:           out [N, H/2, W/2, F] = blurpool(V), V as asm_sk_select_bn_fwd (rounded to bf16);
+ *   asm_sk_select_bn_bwd_att_stats_blur,
+ *   asm_sk_bn_bwd_apply_blur:            as the entry points without _blur, fed with dpool [N, H/2, W/2, F], the gradient
+ *                                        of the pooled tensor, in place of dV = asm_blurpool_bwd(dpool) (rebuilt in
+ *                                        registers, rounded to bf16).
+ * Every output is bit-identical to the chain through asm_blurpool_fwd / asm_blurpool_bwd.  Only k == 3, stride == 2 and
+ * even H and W (forward: W <= 512) are covered: ASM_EINVAL otherwise, nothing is launched. */
+int asm_sk_select_bn_blur_fwd(const void* y, const float* scale, const float* shift, const float* att, void* out, int N,
+                              int H, int W, int F, int k, int stride, void* stream);
+int asm_sk_select_bn_bwd_att_stats_blur(const void* y, const float* scale, const float* shift, const float* mean,
+                                        const float* invstd, const void* dpool, const float* att, void* datt,
+                                        float* grad_stats, int N, int H, int W, int F, int k, int stride, void* stream);
+int asm_sk_bn_bwd_apply_blur(const void* dpool, const float* att, const void* ds, const void* y, const float* scale,
+                             const float* shift, const float* coefA, const float* coefB, const float* coefC, void* dy,
+                             int N, int H, int W, int F, int k, int stride, void* stream);
 /* SE: y = x * sigmoid(e[n][c]);  e float32 [N, C] (pre-sigmoid) */
 int asm_se_scale_fwd(const void* x, const float* e, void* y, int N, int HW, int C, void* stream);
 /* de[n][c] = sigmoid'(e) * sum_hw x*dy (bf16 out) */
