@@ -78,6 +78,15 @@ assert C.sizeof(JpegScan) == 56
 JPEG_EBADCODE, JPEG_EOVERRUN, JPEG_ERESTART, JPEG_EDESC = 1, 2, 4, 8      # asm_jpeg_decode's status bits
 
 
+class SpanDesc(C.Structure):
+  """struct asm_span_desc"""
+  _fields_ = [('offset', C.c_int64), ('length', C.c_int64), ('expect_masked', C.c_uint32), ('flags', C.c_uint32)]
+
+
+assert C.sizeof(SpanDesc) == 24
+SPAN_EDESC, SPAN_EMISMATCH = 1, 2      # asm_crc32c_spans' status bits
+
+
 class ConvDesc(C.Structure):
   """struct asm_conv_desc"""
   _fields_ = [('N', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32),
@@ -273,6 +282,7 @@ SIGNATURES = {
                                       _P, _P, C.c_int64, _I, _P]),
     'asm_jpeg_decode_progressive': (_I, [_P, C.c_int64, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, _I, _I, _P, C.c_int64, _P,
                                          _P, C.c_int64, _I, _P]),
+    'asm_crc32c_spans': (_I, [_P, C.c_int64, _P, _I, _P, _P, _P]),
     'asm_model_plan': (_I, [C.POINTER(ModelCfg), _I, _I, _I, C.POINTER(PlanEntry), _I, C.POINTER(PlanSummary)]),
 }
 

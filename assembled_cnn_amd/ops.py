@@ -1086,6 +1086,23 @@ def jpeg_decode_progressive(files_u8, descs_dev, tables_dev, scans_dev, huff_dev
   return status, ws
 
 
+def crc32c_spans(buf_u8, spans_dev, n):
+  """asm_crc32c_spans: buf_u8 a 1-D uint8 device buffer, spans_dev a uint8 device view of n packed struct asm_span_desc
+  (byte ranges of buf_u8, optionally with the masked crc each must have).  One launch, no synchronisation.  Returns (int32
+  [n] device crc: the plain CRC-32C of every span, the uint32 bit pattern; int32 [n] device status: a word of SPAN_E* bits
+  per span).  records.RecordDataset reads the status and raises for a corrupt record."""
+  if buf_u8.dim() != 1 or buf_u8.dtype != torch.uint8 or spans_dev.dtype != torch.uint8:
+    raise ValueError('crc32c_spans: buffer and descriptor table are 1-D uint8 tensors')
+  if n < 0 or spans_dev.numel() != C.sizeof(_lib.SpanDesc) * n:
+    raise ValueError('crc32c_spans: descriptor table must hold %d bytes' % (C.sizeof(_lib.SpanDesc) * max(n, 0)))
+  out = torch.empty((2, max(n, 1)), dtype=torch.int32, device=buf_u8.device)[:, :n]
+  crc, status = out[0], out[1]
+  if n:
+    check(L().asm_crc32c_spans(_ptr(buf_u8), buf_u8.numel(), _ptr(spans_dev), n, _ptr(crc), _ptr(status), _stream()),
+          'crc32c_spans')
+  return crc, status
+
+
 # ---------------------------------------------------------------------------------------------------
 # retrieval evaluation (metric/recall_metric.py)
 # ---------------------------------------------------------------------------------------------------

@@ -36,7 +36,7 @@ extern "C" {
 #define ASM_EHIP (-3)
 
 /* Changes when an existing struct or signature changes.  Additions keep it: asm_jpeg_decode_progressive,
- * asm_jpeg_scan and asm_jpeg_decode_parallel came in under 11. */
+ * asm_jpeg_scan, asm_jpeg_decode_parallel, asm_crc32c_spans and asm_span_desc came in under 11. */
 #define ASM_ABI_VERSION 11
 
 const char* asm_last_error(void);
@@ -771,7 +771,32 @@ int asm_jpeg_decode_progressive(const uint8_t* files, int64_t files_bytes, const
                                 int32_t* status, void* workspace, int64_t workspace_bytes, int stages, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Flag surface and topology planner.  asm_model_cfg carries the flags of nets/hparams_config.py:30-292 (+
+ * Record checksums (TFRecord shards: tf.data.TFRecordDataset, functions/input_fns.py:63-74): TensorFlow's record reader
+ * verifies the masked CRC-32C behind every payload; here the payloads of a batch are checked where they are needed, on the
+ * device, in one launch (assembled_cnn_amd/records.py gathers them and reads the status).
+ *   buf     buf_bytes (0 .. 2^40 - 1) of device memory, any alignment
+ *   spans   n descriptors (device): the bytes buf[offset, offset + length) of each; any alignment, overlaps allowed
+ *   crc     uint32 [n], written by the call: the plain CRC-32C of the span (Castagnoli polynomial, reflected, init and final
+ *           xor 0xffffffff; the empty span gives 0)
+ *   status  int32 [n], written by the call: 0, or a bit set of ASM_SPAN_E*.  ASM_SPAN_EDESC: negative offset or length,
+ *           or a span that does not lie inside buf (checked without overflow): nothing is read for it and its crc is 0.
+ *           ASM_SPAN_EMISMATCH: flags & 1 is set and the LevelDB-masked crc, ((c >> 15) | (c << 17)) + 0xa282ead8, differs
+ *           from expect_masked -- the word a record file stores.  The other flag bits are reserved (zero).
+ * One workgroup per span, every read bounded by the span, no synchronisation; n == 0 returns ASM_OK without a launch.
+ * Null pointers, n < 0 and buf_bytes outside its range are ASM_EINVAL, before anything is launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define ASM_SPAN_EDESC 1      /* the descriptor does not describe bytes of buf                                         */
+#define ASM_SPAN_EMISMATCH 2  /* the masked crc is not expect_masked                                                   */
+typedef struct asm_span_desc {
+  int64_t offset, length;                  /* bytes                                                                */
+  uint32_t expect_masked;                  /* compared under flags & 1                                             */
+  uint32_t flags;
+} asm_span_desc;                           /* 24 bytes */
+int asm_crc32c_spans(const uint8_t* buf, int64_t buf_bytes, const asm_span_desc* spans, int n, uint32_t* crc,
+                     int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Flag surface and topology planner. asm_model_cfg carries the flags of nets/hparams_config.py:30-292 (+
  * official/utils/flags/_performance.py:29-42) that reach the hot path, with the reference's names; asm_model_plan walks
  * functions/model_fns.Model + nets/resnet_model.Model.__call__ (:305-599) for that configuration and an input of
  * N x H x W x 3 and returns the layers in creation order: every variable-owning layer with its TensorFlow scope name

@@ -2,7 +2,8 @@
 """Throughput of the rows either side of the training step: the GPU input-pipeline tail (resize/crop/flip/mean-sub
 kernel), the device JPEG decoder in front of it, and evaluation-mode inference with the on-device metrics (BASELINE
 configs 1 and 3-eval).  `--only jpeg` runs the JPEG leg alone, `--only jpeg_progressive` the progressive-file leg,
-`--only jpeg_parallel` the sequential entropy stage against the segment-parallel one."""
+`--only jpeg_parallel` the sequential entropy stage against the segment-parallel one, `--only records` the record
+checksum kernel against that stage and the assembly of a batch out of TFRecord shards."""
 import os, sys, time
 import numpy as np
 import torch
@@ -247,9 +248,74 @@ def jpeg_progressive_leg(n=256):
         % (ms_e / ms_be, 100 * ms_e / (ms_e + ms_p)))
 
 
-if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] in ('jpeg', 'jpeg_progressive', 'jpeg_parallel'):
-  {'jpeg': jpeg_leg, 'jpeg_progressive': jpeg_progressive_leg, 'jpeg_parallel': jpeg_parallel_leg}[
-      sys.argv[sys.argv.index('--only') + 1]]()
+def records_leg(n=256):
+  """The files of jpeg_leg wrapped into TFRecord shards.  asm_crc32c_spans alone on the payloads of the batch (device
+  events), alternating with the segment-parallel entropy stage of the same files, three runs each in this process; the
+  whole RecordDataset batch assembly (walk, gather, copy, check, parse) with each verify mode; and the same bytes through
+  tf_bundle.crc32c.  Ends with the bar: the slowest kernel run is at most a tenth of the fastest parallel-entropy run."""
+  import tempfile
+  from assembled_cnn_amd import jpeg, records, tf_bundle
+  try:
+    import PIL  # noqa: F401
+    files = photographic_files(n, np.random.default_rng(1))
+    source = 'the generated files of the jpeg leg'
+  except ImportError:
+    fx = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden', 'jpeg_fixtures.npz'))
+    big = sorted((str(k) for k in fx['names'] if str(fx['kind_' + str(k)]) == 'device'), key=lambda k: -fx['file_' + k].size)[:8]
+    files = [fx['file_' + big[k % len(big)]].tobytes() for k in range(n)]
+    source = 'Pillow not importable: the 8 largest test fixtures tiled'
+  payloads = [records.encode_example({'image/encoded': [f], 'image/filename': [b'n%08d.JPEG' % i],
+                                      'image/class/label': np.array([i % 1000 + 1])}) for i, f in enumerate(files)]
+  total = sum(map(len, payloads))
+  print('records: %d records, %s; mean payload %.1f KB, %.2f MB in all' % (n, source, total / n / 1e3, total / 1e6))
+  # the kernel alone, on the batch laid out as RecordDataset lays it out
+  lengths = np.array([len(p) for p in payloads], dtype=np.int64)
+  offsets, nbytes = staging.slot_layout(lengths)
+  host = np.zeros(nbytes, np.uint8)
+  spans = np.zeros(n, dtype=records.SPAN_DTYPE)
+  for i, (p, o) in enumerate(zip(payloads, offsets)):
+    host[int(o):int(o) + len(p)] = np.frombuffer(p, np.uint8)
+    spans[i] = (int(o), len(p), tf_bundle.mask_crc(tf_bundle.crc32c(p)), 1)
+  bd, sd = torch.from_numpy(host).cuda(), staging.upload_table(spans, 'cuda')
+  crc = lambda: ops.crc32c_spans(bd, sd, n)
+  assert not crc()[1].any(), 'a record of the batch fails its check'
+  pk = jpeg.pack(files, segment_bytes=jpeg.DEFAULT_SEGMENT_BYTES)
+  tabs = [staging.upload_table(t, 'cuda') for t in (pk.files, pk.descs, pk.tables, pk.intervals, pk.segment_first)]
+  dst = torch.empty(pk.total_bytes, dtype=torch.uint8, device='cuda')
+  par = lambda: ops.jpeg_decode_parallel(*tabs, n, len(pk.intervals), pk.total_segments, jpeg.DEFAULT_SEGMENT_BYTES, pk.total_blocks,
+                                         pk.max_blocks, pk.max_pixels, dst, stages=1)
+  assert not par()[0].any()
+  ms_c, ms_p = [], []
+  for _ in range(3):       # alternating
+    ms_c.append(ev(crc, iters=20))
+    ms_p.append(ev(par, iters=3))
+  print('asm_crc32c_spans alone, ms per batch   : %s  (worst %.1f GB/s)' % (' '.join('%8.4f' % m for m in ms_c), total / max(ms_c) / 1e6))
+  print('parallel entropy stage, ms per batch   : %s' % ' '.join('%8.4f' % m for m in ms_p))
+  # batch assembly out of shards
+  with tempfile.TemporaryDirectory() as d:
+    for s in range(4):
+      records.write_records(os.path.join(d, 'validation-%05d-of-00004' % s), payloads[s::4])
+    names = records.get_filenames(False, d)
+    for verify in ('device', 'none', 'host'):
+      ds = records.RecordDataset(names, False, n, 1, cycle_length=4, num_epochs=3, verify=verify, device='cuda')
+      it, ms = iter(ds), []
+      for _ in range(3):
+        t0 = time.time(); b = next(it); torch.cuda.synchronize(); ms.append(1e3 * (time.time() - t0))
+      assert len(b.encoded) == n and all(e.tobytes() == f for e, f in zip(b.encoded, files)), 'the shards dealt and read round-robin'
+      print('RecordDataset batch of %d, verify=%-6s: %s ms per batch (each batch walks the four shards again)'
+            % (n, verify, ' '.join('%8.2f' % m for m in ms)))
+  t0 = time.time(); [tf_bundle.crc32c(p) for p in payloads]; ms_host = 1e3 * (time.time() - t0)
+  t0 = time.time(); tf_bundle.crc32c(host); ms_one = 1e3 * (time.time() - t0)
+  print('tf_bundle.crc32c, same bytes           : %8.2f ms record by record, %8.2f ms in a single call (%.0f MB/s)'
+        % (ms_host, ms_one, total / ms_one / 1e3))
+  ratio = max(ms_c) / min(ms_p)
+  print('records: bar %s, slowest kernel run %.4f ms / fastest parallel-entropy run %.4f ms = %.4f (allowed 0.1)'
+        % ('met' if ratio <= 0.1 else 'MISSED', max(ms_c), min(ms_p), ratio))
+
+
+LEGS = {'jpeg': jpeg_leg, 'jpeg_progressive': jpeg_progressive_leg, 'jpeg_parallel': jpeg_parallel_leg, 'records': records_leg}
+if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] in LEGS:
+  LEGS[sys.argv[sys.argv.index('--only') + 1]]()
   sys.exit(0)
 
 rng = np.random.default_rng(0)
