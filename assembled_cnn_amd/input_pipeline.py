@@ -177,7 +177,7 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
                      windows: Optional[List[dict]] = None, autoaugment_type: Optional[str] = None,
                      augment: Optional[np.ndarray] = None, dct_method: str = '',
                      jpeg_fallback=None, jpeg_progressive: bool = False,
-                     jpeg_entropy: str = 'sequential') -> torch.Tensor:
+                     jpeg_entropy: str = 'sequential', jpeg_parse: str = 'host', jpeg_resident=None) -> torch.Tensor:
   """The imagenet* branches of data_util.preprocess_image for a batch of decoded images; float32 NHWC on `device`.
   `windows` overrides the sampled / computed windows (tests share them with the oracle).
   `autoaugment_type` ('imagenet' | 'good' | 'v0' | 'test'): in training mode the policy runs on the resized image, clipped
@@ -190,9 +190,15 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
   [H, W, 3]` (NotImplementedError without one).  A training crop is a window of the full decode.
   `jpeg_progressive`: decode progressive files on the device as well (opt-in; they go to `jpeg_fallback` otherwise).
   `jpeg_entropy`: 'parallel' decodes each sequential file's scan on all lanes of a workgroup (opt-in, jpeg.py; the same
-  pixels)."""
+  pixels).
+  `jpeg_parse`: 'device' reads the files' headers on the device as well (opt-in, jpeg.pack_device; the same pixels), and
+  `jpeg_resident` then names files that lie on the device already -- records.Batch.payloads -- so that they are not
+  uploaded again; `images` still holds the host bytes, read only for a file the device hands back."""
   if jpeg_entropy not in _jpeg.ENTROPY_MODES:
     raise ValueError('jpeg_entropy must be one of %s, got %r' % (_jpeg.ENTROPY_MODES, jpeg_entropy))
+  if jpeg_parse not in _jpeg.PARSE_MODES:
+    raise ValueError('jpeg_parse must be one of %s, got %r' % (_jpeg.PARSE_MODES, jpeg_parse))
+  _jpeg.check_parse_mode(jpeg_parse, jpeg_resident)
   if autoaugment_type is not None:
     _aa.check_policy_name(autoaugment_type)
   side, crop_type = output_size_and_crop_type(preprocessing_type, is_training, image_size)
@@ -200,8 +206,12 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
     _jpeg.check_dct_method(dct_method)
   # encoded files are decoded on the device into their slots of the packed buffer, decoded arrays (given, or returned by
   # the fallback) travel to theirs in one staged copy; one window and one descriptor per slot
-  pk = _jpeg.pack(images, jpeg_fallback, progressive=jpeg_progressive,
-                  segment_bytes=_jpeg.DEFAULT_SEGMENT_BYTES if jpeg_entropy == 'parallel' else None)
+  segment_bytes = _jpeg.DEFAULT_SEGMENT_BYTES if jpeg_entropy == 'parallel' else None
+  if jpeg_parse == 'device':
+    pk = _jpeg.pack_device(images, device, jpeg_resident, jpeg_fallback, progressive=jpeg_progressive,
+                           segment_bytes=segment_bytes)
+  else:
+    pk = _jpeg.pack(images, jpeg_fallback, progressive=jpeg_progressive, segment_bytes=segment_bytes)
   if windows is None:
     if is_training:
       rng = rng if rng is not None else np.random.default_rng()

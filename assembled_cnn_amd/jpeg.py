@@ -2,9 +2,11 @@
 
 ``parse`` reads the marker segments of one file (ITU-T T.81 annex B): geometry, sampling, quantisation and Huffman tables,
 the byte range of the scan and of each restart interval, and whether the file is one the device path decodes.  ``pack``
-turns a batch of files into the tables ``asm_jpeg_decode`` reads, ``decode_batch`` runs it.  With ``progressive=True``
-(opt-in) a progressive file is read scan by scan and becomes a row of a second group of tables, the ones
-``asm_jpeg_decode_progressive`` reads.  Everything a kernel could
+turns a batch of files into the tables ``asm_jpeg_decode`` reads, ``decode_batch`` runs it.  ``pack_device`` (opt-in)
+makes the sequential rows' tables on the device instead, from files that lie there: asm_jpeg_parse, one read-back of the
+head rows, ``layout_heads``, asm_jpeg_parse_fill; only the files the device does not take come back to ``parse``.
+With ``progressive=True`` (opt-in) a progressive file is read scan by scan and becomes a row of a second
+group of tables, the ones ``asm_jpeg_decode_progressive`` reads.  Everything a kernel could
 trip over in a HEADER (truncated segments, table ids and sizes that disagree) is rejected here with ValueError; what can
 go wrong in the entropy-coded bytes is the kernel's to detect (per-image status, decode_packed raises ValueError).
 
@@ -27,6 +29,7 @@ ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 1
 MAX_SIDE = 8192
 MAX_SCANS = 256         # of one progressive file: the device walks them one after another
 ENTROPY_MODES = ('sequential', 'parallel')
+PARSE_MODES = ('host', 'device')        # who reads the headers: parse / pack here, or asm_jpeg_parse (pack_device)
 # raw file bytes per segment of the segment-parallel entropy stage (entropy='parallel'); the best of the sweep in
 # profiles/jpeg_decode.md
 DEFAULT_SEGMENT_BYTES = 128
@@ -37,6 +40,9 @@ HUFF_DTYPE = np.dtype(lib.JpegHuff)
 TABLES_DTYPE = np.dtype(lib.JpegTables)
 INTERVAL_DTYPE = np.dtype(lib.JpegInterval)
 SCAN_DTYPE = np.dtype(lib.JpegScan)
+HEAD_DTYPE = np.dtype(lib.JpegHead)
+PLACE_DTYPE = np.dtype(lib.JpegPlace)
+SPAN_DTYPE = np.dtype(lib.SpanDesc)
 
 
 def check_dct_method(dct_method: str):
@@ -414,6 +420,11 @@ class Packed:
     self.prog_huff = np.zeros(0, HUFF_DTYPE)
     self.prog_intervals = np.zeros(0, INTERVAL_DTYPE)
     self.prog_total_blocks = self.prog_max_blocks = self.prog_max_pixels = 0
+    # pack_device: the sequential rows' tables as device tensors (files, descs, tables, intervals, segment_first) in place of
+    # the five numpy fields above, their interval count, and asm_jpeg_parse_fill's status word per row
+    self.dev_tables = None
+    self.n_intervals = 0
+    self.fill_status = None
 
 
 def _check_decoded(arr, k) -> np.ndarray:
@@ -549,6 +560,13 @@ def check_segment_bytes(segment_bytes: int) -> int:
   return int(segment_bytes)
 
 
+def check_parse_mode(parse: str, resident=None):
+  if parse not in PARSE_MODES:
+    raise ValueError('parse must be one of %s, got %r' % (PARSE_MODES, parse))
+  if resident is not None and parse != 'device':
+    raise ValueError("resident needs parse='device'")
+
+
 def segment_table(intervals: np.ndarray, segment_bytes: int):
   """(int32 first segment of every interval row, total segments): an interval of b bytes has max(1, ceil(b /
   segment_bytes)) segments and the rows follow each other without a gap (include/asm_hip.h, asm_jpeg_decode_parallel)"""
@@ -559,6 +577,27 @@ def segment_table(intervals: np.ndarray, segment_bytes: int):
   if total >= 2 ** 30:
     raise ValueError('segment_bytes = %d gives %d segments, more than one call takes' % (segment_bytes, total))
   return (ends - counts).astype(np.int32), total
+
+
+def _route(pk: Packed, files, infos, fallback, on_device=()):
+  """Where every entry of a batch goes: a sequential row (pk.dev_index), a progressive row (pk.prog_index) or a decoded
+  array in pk.fallback -- given, or made by ``fallback`` from a file of an unsupported kind (NotImplementedError without
+  one).  on_device: entries that are sequential rows without an info (pack_device).  Returns the rows' files as arrays."""
+  arrays = [None] * len(files)
+  for k, (f, info) in enumerate(zip(files, infos)):
+    if k in on_device:
+      pk.dev_index.append(k)
+    elif info is None:
+      pk.fallback[k] = _check_decoded(f, k)
+    elif info.unsupported is not None:
+      if fallback is None:
+        raise NotImplementedError('entry %d: %s is not decoded on the device and no fallback was given'
+                                  % (k, info.unsupported))
+      pk.fallback[k] = _check_decoded(fallback(bytes(f) if not isinstance(f, np.ndarray) else f.tobytes()), k)
+    else:
+      arrays[k] = _as_array(f)
+      (pk.prog_index if info.progressive else pk.dev_index).append(k)
+  return arrays
 
 
 def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[List[JpegInfo]] = None,
@@ -575,18 +614,7 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
   n = len(files)
   if infos is None:
     infos = [parse(f, progressive) if is_encoded(f) else None for f in files]
-  arrays = [None] * n
-  for k, (f, info) in enumerate(zip(files, infos)):
-    if info is None:
-      pk.fallback[k] = _check_decoded(f, k)
-    elif info.unsupported is not None:
-      if fallback is None:
-        raise NotImplementedError('entry %d: %s is not decoded on the device and no fallback was given'
-                                  % (k, info.unsupported))
-      pk.fallback[k] = _check_decoded(fallback(bytes(f) if not isinstance(f, np.ndarray) else f.tobytes()), k)
-    else:
-      arrays[k] = _as_array(f)
-      (pk.prog_index if info.progressive else pk.dev_index).append(k)
+  arrays = _route(pk, files, infos, fallback)
   # output slots, 16-byte aligned (the src layout of asm_resize_crop_flip): the device-decoded entries first (sequential
   # rows, then progressive rows), then the already decoded ones back to back, so that those travel in one host-to-device
   # copy
@@ -596,6 +624,112 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
   pk.host_begin = int(pk.offsets[hosted[0]]) if hosted else total
   pk.total_bytes = max(total, 16)
   _pack_sequential(pk, infos, arrays)
+  if pk.prog_index:
+    _pack_progressive(pk, infos, arrays)
+  return pk
+
+
+def layout_heads(heads: np.ndarray, sizes=None, tail=(), segment_bytes: Optional[int] = None):
+  """The host's part between asm_jpeg_parse and asm_jpeg_parse_fill, pure numpy.  heads: HEAD_DTYPE [n], row k the head row
+  of batch entry k; the entries of class 0 become the sequential rows, in batch order.  sizes: (height, width) of every
+  entry (those of the class-0 entries are taken from their head rows); tail: the other entries in the order of their
+  output slots (progressive rows, then the hosted ones).  Returns (PLACE_DTYPE [rows] placement table, batch index of each
+  row, int64 slot offset of every entry, bytes of all slots, totals): pack's slot layout, block offsets, first_interval
+  and first segment, with totals = dict(total_blocks, max_blocks, max_pixels, n_intervals, total_segments)."""
+  heads = np.asarray(heads).view(HEAD_DTYPE).reshape(-1)
+  n = len(heads)
+  rows = np.flatnonzero(heads['cls'] == 0)
+  h = heads[rows]
+  hw = np.zeros((n, 2), np.int64)
+  if sizes is not None and n:
+    hw[:] = np.asarray(sizes, dtype=np.int64).reshape(n, 2)
+  hw[rows, 0], hw[rows, 1] = h['height'], h['width']
+  order = [int(k) for k in rows] + [int(k) for k in tail]
+  if sorted(order) != list(range(n)):
+    raise ValueError('layout_heads: the class-0 rows and `tail` must name every entry once')
+  offsets, total = slot_layout(hw[:, 0] * hw[:, 1] * 3, order)
+  width, height, hs, vs = (h[f].astype(np.int64) for f in ('width', 'height', 'hs', 'vs'))
+  n_mcus = -(-width // (8 * hs)) * -(-height // (8 * vs))
+  blocks = n_mcus * np.where(h['ncomp'] == 3, hs * vs + 2, 1)
+  n_iv = h['n_intervals'].astype(np.int64)
+  n_seg = h['n_segments'].astype(np.int64) if segment_bytes is not None else np.zeros(len(h), np.int64)
+  totals = dict(total_blocks=int(blocks.sum()), max_blocks=int(blocks.max(initial=0)),
+                max_pixels=int((width * height).max(initial=0)), n_intervals=int(n_iv.sum()),
+                total_segments=int(n_seg.sum()))
+  if totals['total_segments'] >= 2 ** 30:
+    raise ValueError('segment_bytes = %d gives %d segments, more than one call takes' % (segment_bytes,
+                                                                                        totals['total_segments']))
+  if totals['n_intervals'] >= 2 ** 31:
+    raise ValueError('%d restart intervals, more than one call takes' % totals['n_intervals'])
+  place = np.zeros(len(rows), PLACE_DTYPE)
+  place['span'] = rows
+  place['first_interval'] = np.cumsum(n_iv) - n_iv
+  place['first_segment'] = np.cumsum(n_seg) - n_seg
+  place['coef_offset'] = (np.cumsum(blocks) - blocks) * 64
+  place['dst_offset'] = offsets[rows]
+  return place, order[:len(rows)], offsets, total, totals
+
+
+def pack_device(files: Sequence, device, resident=None, fallback: Optional[Callable] = None, progressive: bool = False,
+                segment_bytes: Optional[int] = None) -> Packed:
+  """``pack`` with the headers read on the device: the sequential rows' tables come back as device tensors
+  (``dev_tables``) that ``decode_packed`` hands to the same kernels, with `files` = the buffer the whole files lie in.
+  resident = (1-D uint8 device buffer, int64 [n, 2] offset and length of every entry's bytes in it): the files are there
+  already (records.RecordDataset(keep_payloads=True)); files[k] is then read only for an entry the device hands back.
+  Without it the whole files travel up in one staged copy, at 16-byte slots; a decoded array is then allowed as in pack,
+  with `resident` it raises ValueError.  Two launches around ONE synchronisation (the head rows, 72 bytes a file).
+  A file the device does not give class 0 goes through ``parse`` here exactly as in ``pack``: the same progressive rows,
+  fallback calls, NotImplementedError and ValueError.  Slots, offsets and every decoded byte equal pack's."""
+  pk = Packed()
+  if segment_bytes is not None:
+    pk.segment_bytes = check_segment_bytes(segment_bytes)
+  n = len(files)
+  dev = torch.device(device)
+  encoded = [is_encoded(f) for f in files]
+  spans = np.zeros(n, SPAN_DTYPE)
+  if resident is not None:
+    buf, where = resident
+    where = np.asarray(where.cpu() if isinstance(where, torch.Tensor) else where, dtype=np.int64)
+    if (not isinstance(buf, torch.Tensor) or buf.dim() != 1 or buf.dtype != torch.uint8 or buf.device.type != dev.type or
+        (dev.index is not None and buf.device.index != dev.index)):
+      raise ValueError('resident: the buffer must be a 1-D uint8 tensor on %s' % dev)
+    if where.shape != (n, 2):
+      raise ValueError('resident: one (offset, length) per entry, got shape %s for %d entries' % (where.shape, n))
+    for k, e in enumerate(encoded):
+      if not e:
+        raise ValueError('entry %d: a decoded image cannot be resident' % k)
+    spans['offset'], spans['length'] = where[:, 0], where[:, 1]
+  else:
+    whole = [_as_array(f) for f, e in zip(files, encoded) if e]
+    spans['length'][encoded] = [a.size for a in whole]
+    spans['offset'], total = slot_layout(spans['length'])
+    buf = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+    stage_into(buf, whole, spans['offset'][encoded])
+  spans_dev = upload_table(spans, dev)
+  heads_dev, tables_dev = ops.jpeg_parse(buf, spans_dev, n, pk.segment_bytes)
+  heads = heads_dev.cpu().numpy().view(HEAD_DTYPE)        # the path's one synchronisation
+  on_device = set(int(k) for k in np.flatnonzero(heads['cls'] == 0))
+  infos = [None] * n
+  for k in range(n):
+    if encoded[k] and k not in on_device:
+      infos[k] = parse(files[k], progressive)
+      if infos[k].unsupported is None and not infos[k].progressive:
+        raise lib.AsmError('entry %d: asm_jpeg_parse refused (class %d) a file the host parser accepts'
+                           % (k, int(heads['cls'][k])))
+  arrays = _route(pk, files, infos, fallback, on_device)
+  pk.sizes = [(int(heads['height'][k]), int(heads['width'][k])) if k in on_device else
+              pk.fallback[k].shape[:2] if k in pk.fallback else (infos[k].height, infos[k].width) for k in range(n)]
+  hosted = sorted(pk.fallback)
+  place, rows, pk.offsets, total, totals = layout_heads(heads, pk.sizes, pk.prog_index + hosted, pk.segment_bytes)
+  assert rows == pk.dev_index
+  pk.host_begin = int(pk.offsets[hosted[0]]) if hosted else total
+  pk.total_bytes = max(total, 16)
+  pk.total_blocks, pk.max_blocks, pk.max_pixels = totals['total_blocks'], totals['max_blocks'], totals['max_pixels']
+  pk.n_intervals, pk.total_segments = totals['n_intervals'], totals['total_segments']
+  descs, tables, intervals, first, pk.fill_status = ops.jpeg_parse_fill(
+      buf, spans_dev, n, heads_dev, tables_dev, upload_table(place, dev), len(place), pk.n_intervals, pk.total_segments,
+      pk.segment_bytes)
+  pk.dev_tables = (buf, descs, tables, intervals, first)
   if pk.prog_index:
     _pack_progressive(pk, infos, arrays)
   return pk
@@ -629,15 +763,20 @@ def decode_packed(pk: Packed, device, stages: int = 3, check: bool = True, retur
   dev = torch.device(device)
   dst = torch.empty(pk.total_bytes, dtype=torch.uint8, device=dev)
   status = ws = prog_status = prog_ws = info = None
+  if pk.dev_tables is not None:           # pack_device: the tables are on the device already
+    tabs, n_iv = pk.dev_tables, pk.n_intervals
+  else:
+    host = (pk.files, pk.descs, pk.tables, pk.intervals) + ((pk.segment_first,) if entropy == 'parallel' else ())
+    tabs, n_iv = tuple(upload_table(t, dev) for t in host) if pk.dev_index else (), len(pk.intervals)
   if pk.dev_index and entropy == 'parallel':
-    tabs = (pk.files, pk.descs, pk.tables, pk.intervals, pk.segment_first)
-    status, ws, info = ops.jpeg_decode_parallel(*(upload_table(t, dev) for t in tabs), len(pk.dev_index), len(pk.intervals),
-                                                pk.total_segments, pk.segment_bytes, pk.total_blocks, pk.max_blocks,
-                                                pk.max_pixels, dst, stages=stages, info=True)
+    status, ws, info = ops.jpeg_decode_parallel(*tabs[:5], len(pk.dev_index), n_iv, pk.total_segments, pk.segment_bytes,
+                                                pk.total_blocks, pk.max_blocks, pk.max_pixels, dst, stages=stages,
+                                                info=True)
   elif pk.dev_index:
-    status, ws = ops.jpeg_decode(*(upload_table(t, dev) for t in (pk.files, pk.descs, pk.tables, pk.intervals)),
-                                 len(pk.dev_index), len(pk.intervals), pk.total_blocks, pk.max_blocks, pk.max_pixels, dst,
+    status, ws = ops.jpeg_decode(*tabs[:4], len(pk.dev_index), n_iv, pk.total_blocks, pk.max_blocks, pk.max_pixels, dst,
                                  stages=stages)
+  if status is not None and pk.fill_status is not None:
+    status = status | pk.fill_status       # a row asm_jpeg_parse_fill refused (ASM_JPEG_EDESC)
   if pk.prog_index:
     if return_workspace and ws is not None:
       ws = ws.clone()       # both calls use the stream's one scratch buffer
@@ -659,20 +798,27 @@ def decode_packed(pk: Packed, device, stages: int = 3, check: bool = True, retur
 
 
 def decode_batch(files: Sequence, device, fallback: Optional[Callable] = None, dct_method: str = '',
-                 progressive: bool = False, entropy: str = 'sequential', segment_bytes: Optional[int] = None):
+                 progressive: bool = False, entropy: str = 'sequential', segment_bytes: Optional[int] = None,
+                 parse: str = 'host', resident=None):
   """Encoded files -> (packed uint8 device buffer, byte offsets, [(height, width)]): image k is
   buffer[offsets[k] : offsets[k] + 3 * h * w] viewed as [h, w, 3].  Raises ValueError naming the files whose
   entropy-coded data is corrupt, NotImplementedError for an unsupported kind without ``fallback``.
   progressive: decode progressive files on the device too (they need no fallback then).
   entropy: 'parallel' decodes each sequential file's scan on all lanes of a workgroup, in segments of segment_bytes
-  (default DEFAULT_SEGMENT_BYTES); the pixels are the same."""
+  (default DEFAULT_SEGMENT_BYTES); the pixels are the same.
+  parse: 'device' reads the headers on the device too (pack_device; opt-in, every result is the same); resident: the
+  (buffer, spans) of files that lie on the device already (parse='device' only)."""
   check_dct_method(dct_method)
   if entropy not in ENTROPY_MODES:
     raise ValueError('entropy must be one of %s, got %r' % (ENTROPY_MODES, entropy))
+  check_parse_mode(parse, resident)
   if entropy == 'parallel':
     segment_bytes = DEFAULT_SEGMENT_BYTES if segment_bytes is None else segment_bytes
   elif segment_bytes is not None:
     raise ValueError("segment_bytes needs entropy='parallel'")
-  pk = pack(files, fallback, progressive=progressive, segment_bytes=segment_bytes)
+  if parse == 'device':
+    pk = pack_device(files, device, resident, fallback, progressive=progressive, segment_bytes=segment_bytes)
+  else:
+    pk = pack(files, fallback, progressive=progressive, segment_bytes=segment_bytes)
   dst = decode_packed(pk, device, entropy=entropy)[0]
   return dst, pk.offsets, pk.sizes

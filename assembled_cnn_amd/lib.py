@@ -87,6 +87,24 @@ assert C.sizeof(SpanDesc) == 24
 SPAN_EDESC, SPAN_EMISMATCH = 1, 2      # asm_crc32c_spans' status bits
 
 
+class JpegHead(C.Structure):
+  """struct asm_jpeg_head"""
+  _fields_ = [(n, C.c_int32) for n in ('cls', 'width', 'height', 'ncomp', 'hs', 'vs', 'restart_interval', 'n_intervals')] + [
+      (n, C.c_int64) for n in ('scan_begin', 'scan_bytes', 'n_segments')] + [
+      ('qsel', C.c_uint8 * 4), ('dcsel', C.c_uint8 * 4), ('acsel', C.c_uint8 * 4), ('reserved', C.c_int32)]
+
+
+class JpegPlace(C.Structure):
+  """struct asm_jpeg_place"""
+  _fields_ = [('span', C.c_int32), ('first_interval', C.c_int32), ('first_segment', C.c_int32), ('reserved', C.c_int32),
+              ('coef_offset', C.c_int64), ('dst_offset', C.c_int64)]
+
+
+assert (C.sizeof(JpegHead), C.sizeof(JpegPlace)) == (72, 32)
+# asm_jpeg_parse's class bits (diagnostics; 0 = a file asm_jpeg_decode takes)
+JPEG_PNOTJPEG, JPEG_PHEADER, JPEG_PKIND, JPEG_PNOEOI, JPEG_PSPAN, JPEG_PLIMIT = 1, 2, 4, 8, 16, 32
+
+
 class ConvDesc(C.Structure):
   """struct asm_conv_desc"""
   _fields_ = [('N', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('C', C.c_int32),
@@ -283,6 +301,8 @@ SIGNATURES = {
     'asm_jpeg_decode_progressive': (_I, [_P, C.c_int64, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, _I, _I, _P, C.c_int64, _P,
                                          _P, C.c_int64, _I, _P]),
     'asm_crc32c_spans': (_I, [_P, C.c_int64, _P, _I, _P, _P, _P]),
+    'asm_jpeg_parse': (_I, [_P, C.c_int64, _P, _I, _I, _P, _P, _P]),
+    'asm_jpeg_parse_fill': (_I, [_P, C.c_int64, _P, _I, _P, _P, _P, _I, _I, C.c_int64, _I, _P, _P, _P, _P, _P, _P]),
     'asm_model_plan': (_I, [C.POINTER(ModelCfg), _I, _I, _I, C.POINTER(PlanEntry), _I, C.POINTER(PlanSummary)]),
 }
 

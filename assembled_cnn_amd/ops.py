@@ -1103,6 +1103,59 @@ def crc32c_spans(buf_u8, spans_dev, n):
   return crc, status
 
 
+def _segment_bytes_arg(segment_bytes) -> int:
+  return 0 if segment_bytes is None else int(segment_bytes)
+
+
+def jpeg_parse(buf_u8, spans_dev, n, segment_bytes=None):
+  """asm_jpeg_parse: buf_u8 a 1-D uint8 device buffer that holds whole JPEG files, spans_dev a uint8 device view of n packed
+  struct asm_span_desc (the byte range of each file).  One launch, no synchronisation.  Returns (uint8 device view of n
+  struct asm_jpeg_head, uint8 device view of n struct asm_jpeg_tables): per file its class -- 0 where asm_jpeg_decode takes
+  it -- with what jpeg.layout_heads needs to place its rows, and its table block.  segment_bytes: also count the segments
+  of asm_jpeg_decode_parallel."""
+  if buf_u8.dim() != 1 or buf_u8.dtype != torch.uint8 or spans_dev.dtype != torch.uint8:
+    raise ValueError('jpeg_parse: buffer and descriptor table are 1-D uint8 tensors')
+  if n < 0 or spans_dev.numel() != C.sizeof(_lib.SpanDesc) * n:
+    raise ValueError('jpeg_parse: descriptor table must hold %d bytes' % (C.sizeof(_lib.SpanDesc) * max(n, 0)))
+  heads = torch.empty(max(n, 1) * C.sizeof(_lib.JpegHead), dtype=torch.uint8, device=buf_u8.device)
+  tables = torch.empty(max(n, 1) * C.sizeof(_lib.JpegTables), dtype=torch.uint8, device=buf_u8.device)
+  if n:
+    check(L().asm_jpeg_parse(_ptr(buf_u8), buf_u8.numel(), _ptr(spans_dev), n, _segment_bytes_arg(segment_bytes), _ptr(heads),
+                             _ptr(tables), _stream()), 'jpeg_parse')
+  return heads[:n * C.sizeof(_lib.JpegHead)], tables[:n * C.sizeof(_lib.JpegTables)]
+
+
+def jpeg_parse_fill(buf_u8, spans_dev, n_spans, heads_dev, tables_dev, place_dev, n_rows, n_intervals, total_segments,
+                    segment_bytes=None):
+  """asm_jpeg_parse_fill: the second launch behind jpeg_parse -- place_dev a uint8 device view of n_rows struct
+  asm_jpeg_place (jpeg.layout_heads).  Returns uint8 device views of the n_rows struct asm_jpeg_desc, n_rows struct
+  asm_jpeg_tables and n_intervals struct asm_jpeg_interval, the int32 [n_intervals] segment table (None without
+  segment_bytes) and the int32 [n_rows] status (0 or JPEG_EDESC): the tables of jpeg_decode / jpeg_decode_parallel with
+  files = buf_u8."""
+  for t, size, count, what in ((spans_dev, C.sizeof(_lib.SpanDesc), n_spans, 'n_spans'),
+                               (heads_dev, C.sizeof(_lib.JpegHead), n_spans, 'n_spans'),
+                               (tables_dev, C.sizeof(_lib.JpegTables), n_spans, 'n_spans'),
+                               (place_dev, C.sizeof(_lib.JpegPlace), n_rows, 'n_rows')):
+    if count < 0 or t.dtype != torch.uint8 or t.numel() != size * count:
+      raise ValueError('jpeg_parse_fill: table sizes do not match %s = %d' % (what, count))
+  if n_intervals < 0 or total_segments < 0:
+    raise ValueError('jpeg_parse_fill: n_intervals = %d, total_segments = %d' % (n_intervals, total_segments))
+  dev = buf_u8.device
+  descs = torch.empty(max(n_rows, 1) * C.sizeof(_lib.JpegDesc), dtype=torch.uint8, device=dev)
+  tables = torch.empty(max(n_rows, 1) * C.sizeof(_lib.JpegTables), dtype=torch.uint8, device=dev)
+  intervals = torch.empty(max(n_intervals, 1) * C.sizeof(_lib.JpegInterval), dtype=torch.uint8, device=dev)
+  first = torch.empty(max(n_intervals, 1), dtype=torch.int32, device=dev) if segment_bytes is not None else None
+  status = torch.empty(max(n_rows, 1), dtype=torch.int32, device=dev)
+  if n_rows:
+    check(L().asm_jpeg_parse_fill(_ptr(buf_u8), buf_u8.numel(), _ptr(spans_dev), n_spans, _ptr(heads_dev), _ptr(tables_dev),
+                                  _ptr(place_dev), n_rows, n_intervals, total_segments, _segment_bytes_arg(segment_bytes),
+                                  _ptr(descs), _ptr(tables), _ptr(intervals), _ptr(first), _ptr(status), _stream()),
+          'jpeg_parse_fill')
+  return (descs[:n_rows * C.sizeof(_lib.JpegDesc)], tables[:n_rows * C.sizeof(_lib.JpegTables)],
+          intervals[:n_intervals * C.sizeof(_lib.JpegInterval)], None if first is None else first[:n_intervals],
+          status[:n_rows])
+
+
 # ---------------------------------------------------------------------------------------------------
 # retrieval evaluation (metric/recall_metric.py)
 # ---------------------------------------------------------------------------------------------------

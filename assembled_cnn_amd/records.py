@@ -342,6 +342,9 @@ class Batch(NamedTuple):
   labels: torch.Tensor                  # int32 [B], or float32 [B, 2 * num_classes] with return_logits
   filenames: List[bytes]
   origins: List[Tuple[str, int]]        # (shard, byte position of the record in it)
+  # keep_payloads: (the dataset's uint8 device staging buffer, int64 [B, 2] offset and length of each record's image/encoded
+  # bytes in it), valid until the next batch is drawn: preprocess_batch(..., jpeg_parse='device', jpeg_resident=payloads)
+  payloads: Optional[Tuple[torch.Tensor, np.ndarray]] = None
 
 
 def _shuffled(items: Iterator, buffer_size: int, rng: np.random.Generator) -> Iterator:
@@ -410,12 +413,17 @@ class RecordDataset(object):
   ``verify``: 'device' -- the batch's payloads go through this module's pinned staging buffer to ``device`` in one copy and
   ops.crc32c_spans checks them against the stored crcs; the status is read before the batch is yielded.  'host' -- the same
   through tf_bundle.crc32c (slow: CPU tests and tools).  'none' -- no check.  A mismatch raises ValueError naming the shard
-  and the record's byte position."""
+  and the record's byte position.
+
+  ``keep_payloads``: the batch's payloads go to ``device`` under every ``verify`` mode (which then only decides about the
+  checksum launch and its read-back) and ``Batch.payloads`` names the encoded images in that buffer, so that the JPEG
+  decoder reads them where they are instead of uploading them again.  The buffer is the dataset's own and is refilled by
+  the next batch."""
 
   def __init__(self, filenames: Sequence[str], is_training: bool, batch_size: int, shuffle_buffer: int,
                num_train_files: Optional[int] = None, num_epochs: int = 1, cycle_length: int = 20,
                drop_remainder: bool = False, return_logits: bool = False, num_classes: int = 1001,
-               seed: Optional[int] = None, verify: str = 'device', device='cuda'):
+               seed: Optional[int] = None, verify: str = 'device', device='cuda', keep_payloads: bool = False):
     if verify not in VERIFY_MODES:
       raise ValueError('verify must be one of %s, got %r' % (VERIFY_MODES, verify))
     if batch_size < 1 or cycle_length < 1 or num_epochs < 0 or (is_training and shuffle_buffer < 1):
@@ -425,8 +433,9 @@ class RecordDataset(object):
     self.num_train_files = len(self.filenames) if num_train_files is None else int(num_train_files)
     self.num_epochs, self.cycle_length, self.drop_remainder = int(num_epochs), int(cycle_length), bool(drop_remainder)
     self.return_logits, self.num_classes, self.seed = bool(return_logits), int(num_classes), seed
-    self.verify, self.device = verify, torch.device(device)
+    self.verify, self.device, self.keep_payloads = verify, torch.device(device), bool(keep_payloads)
     self._host = self._dev = None         # grow-only staging buffers of the device check
+    self._uploaded = None                 # event behind the last asynchronous copy out of the pinned buffer
 
   def records(self) -> Iterator[Tuple[RecordFile, int]]:
     """(shard, record index) in the order the batches are cut from"""
@@ -456,23 +465,35 @@ class RecordDataset(object):
       if mask_crc(crc32c(f.payload(i))) != int(f.stored[i]):
         raise self._mismatch(f, i, 'payload checksum mismatch')
 
-  def _verify_device(self, recs):
-    n = len(recs)
+  def _upload(self, recs):
+    """the batch's payloads at 16-byte slots -> the pinned staging buffer -> ONE asynchronous copy to the device buffer;
+    returns (device view of the slots, int64 slot offsets, int64 payload lengths)"""
     lengths = np.array([f.lengths[i] for f, i in recs], dtype=np.int64)
     offsets, total = staging.slot_layout(lengths)
     total = max(total, 16)
     pin = self.device.type == 'cuda'
+    if self._uploaded is not None:
+      self._uploaded.synchronize()         # the previous batch's copy still reads the pinned buffer
+      self._uploaded = None
     if self._host is None or self._host.numel() < total:
       self._host = torch.empty(int(total * 1.25) + 4096, dtype=torch.uint8, pin_memory=pin)
       self._dev = torch.empty(self._host.numel(), dtype=torch.uint8, device=self.device)
     host = self._host.numpy()
     for (f, i), o, ln in zip(recs, offsets, lengths):
       host[int(o):int(o) + int(ln)] = f.payload(i)
+    dev = self._dev[:total]
+    dev.copy_(self._host[:total], non_blocking=True)
+    if pin:
+      self._uploaded = torch.cuda.Event()
+      self._uploaded.record()
+    return dev, offsets, lengths
+
+  def _verify_device(self, recs, uploaded):
+    n = len(recs)
+    dev, offsets, lengths = uploaded
     spans = np.zeros(n, dtype=SPAN_DTYPE)
     spans['offset'], spans['length'], spans['flags'] = offsets, lengths, 1
     spans['expect_masked'] = [f.stored[i] for f, i in recs]
-    dev = self._dev[:total]
-    dev.copy_(self._host[:total], non_blocking=True)
     _, status = ops.crc32c_spans(dev, staging.upload_table(spans, self.device), n)
     status = status.cpu().numpy()          # waits for the copy as well: the staging buffer is free for the next batch
     for (f, i), st in zip(recs, status):
@@ -480,11 +501,12 @@ class RecordDataset(object):
         raise self._mismatch(f, i, 'payload checksum mismatch' if st == _lib.SPAN_EMISMATCH else 'span status %d' % st)
 
   def _batch(self, recs) -> Batch:
+    uploaded = self._upload(recs) if self.verify == 'device' or self.keep_payloads else None
     if self.verify == 'device':
-      self._verify_device(recs)
+      self._verify_device(recs, uploaded)
     elif self.verify == 'host':
       self._verify_host(recs)
-    encoded, labels, names, origins = [], [], [], []
+    encoded, labels, names, origins, spans = [], [], [], [], []
     for f, i in recs:
       payload = f.payload(i)
       try:
@@ -493,7 +515,13 @@ class RecordDataset(object):
       except ValueError as err:
         raise ValueError('%s: record at byte %d: %s' % (f.name, int(f.starts[i]), err))
       encoded.append(payload[b:e])
+      spans.append((b, e - b))
       names.append(name)
       origins.append((f.name, int(f.starts[i])))
     lab = np.stack(labels).astype(np.float32) if self.return_logits else np.asarray(labels, dtype=np.int32)
-    return Batch(encoded, torch.from_numpy(lab), names, origins)
+    payloads = None
+    if self.keep_payloads:
+      where = np.array(spans, dtype=np.int64).reshape(-1, 2)
+      where[:, 0] += uploaded[1]             # the record's slot + the image's position in the record
+      payloads = (uploaded[0], where)
+    return Batch(encoded, torch.from_numpy(lab), names, origins, payloads)

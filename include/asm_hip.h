@@ -36,7 +36,8 @@ extern "C" {
 #define ASM_EHIP (-3)
 
 /* Changes when an existing struct or signature changes.  Additions keep it: asm_jpeg_decode_progressive,
- * asm_jpeg_scan, asm_jpeg_decode_parallel, asm_crc32c_spans and asm_span_desc came in under 11. */
+ * asm_jpeg_scan, asm_jpeg_decode_parallel, asm_crc32c_spans, asm_span_desc, asm_jpeg_parse and asm_jpeg_parse_fill came in
+ * under 11. */
 #define ASM_ABI_VERSION 11
 
 const char* asm_last_error(void);
@@ -794,6 +795,63 @@ typedef struct asm_span_desc {
 } asm_span_desc;                           /* 24 bytes */
 int asm_crc32c_spans(const uint8_t* buf, int64_t buf_bytes, const asm_span_desc* spans, int n, uint32_t* crc,
                      int32_t* status, void* stream);
+
+/* JPEG headers on the device (declared here for asm_span_desc): the tables of asm_jpeg_decode / asm_jpeg_decode_parallel made from whole files that already lie
+ * in device memory (assembled_cnn_amd/jpeg.py pack_device; DESIGN.md 1.2 has the rules), in two launches around one small
+ * read-back.  The entropy and pixel kernels then run unchanged with `files` = buf.
+ *
+ * asm_jpeg_parse: one 256-lane workgroup per span reads the file buf[offset, offset + length) -- SOI, marker segments, the
+ * extent of the scan and of its restart intervals -- and writes one head row and one table block per span.
+ *   buf, buf_bytes, spans, n   as for asm_crc32c_spans (an asm_span_desc's flags and expect_masked are ignored)
+ *   segment_bytes  0, or a multiple of 16 in 16..65536: also count the segments asm_jpeg_decode_parallel cuts the file into
+ *   heads      n asm_jpeg_head, written by the call.  cls == 0: a file asm_jpeg_decode takes, exactly where jpeg.parse
+ *              neither raises nor calls the file unsupported; the other fields then hold what the host needs to place the
+ *              file's rows.  Otherwise cls is a bit set of ASM_JPEG_P* (diagnostics only; the host parses such a file
+ *              itself) and the other fields are zero.
+ *   tables     n asm_jpeg_tables, written by the call: for cls == 0 the block jpeg.pack makes for the file, byte for byte
+ *              (every defined quantisation table, Huffman tables in slots of first use, zero elsewhere); else all zero
+ * asm_jpeg_parse_fill: one workgroup per row of `place` (the class-0 files in batch order, laid out by the host from the head
+ * rows) writes the row's asm_jpeg_desc, copies its table block into row order and writes its interval rows and, for
+ * segment_bytes != 0, its segment_first entries in restart order.  scan_offset, byte_begin and byte_end are positions in buf.
+ *   n_spans    rows of spans, heads and tables; n_rows: rows of place, descs, tables_out and status
+ *   n_intervals, total_segments   rows of `intervals` / `segment_first`, and the bound of the segment indices
+ *   status     int32 [n_rows], written by the call: 0, or ASM_JPEG_EDESC for a place row that names no class-0 head row or
+ *              does not fit the tables, and for a scan whose interval or segment count disagrees with its head row (the bytes
+ *              changed between the launches).  Such a row's descriptor is all zero and nothing is written outside the row's
+ *              own ranges; OR the word into asm_jpeg_decode's status.
+ * Both: n == 0 (n_rows == 0) returns ASM_OK without a launch; null pointers (segment_first may be null for segment_bytes
+ * == 0), negative counts, another segment_bytes and buf_bytes outside 0 .. 2^40 - 1 are ASM_EINVAL, before any launch. */
+#define ASM_JPEG_PNOTJPEG 1   /* no SOI (also: an empty or one-byte span)                                             */
+#define ASM_JPEG_PHEADER 2    /* a marker segment the host refuses: truncated, ids or sizes that disagree              */
+#define ASM_JPEG_PKIND 4      /* a kind the sequential decoder does not take: progressive, CMYK, 16-bit DQT, ...      */
+#define ASM_JPEG_PNOEOI 8     /* the scan does not end in a marker that leads to EOI                                   */
+#define ASM_JPEG_PSPAN 16     /* the span does not lie inside buf: nothing was read                                    */
+#define ASM_JPEG_PLIMIT 32    /* more than 2^31 - 1 restart intervals                                                  */
+typedef struct asm_jpeg_head {
+  int32_t cls;                             /* 0, or a bit set of ASM_JPEG_P*                                       */
+  int32_t width, height, ncomp, hs, vs;    /* as in asm_jpeg_desc                                                  */
+  int32_t restart_interval;
+  int32_t n_intervals;                     /* restart intervals of the scan, >= 1                                  */
+  int64_t scan_begin, scan_bytes;          /* the entropy-coded bytes, relative to the span's first byte           */
+  int64_t n_segments;                      /* for segment_bytes; 0 when that is 0                                  */
+  uint8_t qsel[4], dcsel[4], acsel[4];     /* as in asm_jpeg_desc                                                  */
+  int32_t reserved;
+} asm_jpeg_head;                           /* 72 bytes */
+typedef struct asm_jpeg_place {
+  int32_t span;                            /* the file's row of spans / heads / tables                             */
+  int32_t first_interval;                  /* its first row of the interval table                                  */
+  int32_t first_segment;                   /* its first segment (0 when segment_bytes == 0)                        */
+  int32_t reserved;
+  int64_t coef_offset;                     /* asm_jpeg_desc's coef_offset and plane_offset                         */
+  int64_t dst_offset;
+} asm_jpeg_place;                          /* 32 bytes */
+int asm_jpeg_parse(const uint8_t* buf, int64_t buf_bytes, const asm_span_desc* spans, int n, int segment_bytes,
+                   asm_jpeg_head* heads, asm_jpeg_tables* tables, void* stream);
+int asm_jpeg_parse_fill(const uint8_t* buf, int64_t buf_bytes, const asm_span_desc* spans, int n_spans,
+                        const asm_jpeg_head* heads, const asm_jpeg_tables* tables, const asm_jpeg_place* place, int n_rows,
+                        int n_intervals, int64_t total_segments, int segment_bytes, asm_jpeg_desc* descs,
+                        asm_jpeg_tables* tables_out, asm_jpeg_interval* intervals, int32_t* segment_first, int32_t* status,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Flag surface and topology planner. asm_model_cfg carries the flags of nets/hparams_config.py:30-292 (+

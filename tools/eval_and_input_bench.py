@@ -3,7 +3,8 @@
 kernel), the device JPEG decoder in front of it, and evaluation-mode inference with the on-device metrics (BASELINE
 configs 1 and 3-eval).  `--only jpeg` runs the JPEG leg alone, `--only jpeg_progressive` the progressive-file leg,
 `--only jpeg_parallel` the sequential entropy stage against the segment-parallel one, `--only records` the record
-checksum kernel against that stage and the assembly of a batch out of TFRecord shards."""
+checksum kernel against that stage and the assembly of a batch out of TFRecord shards, `--only jpeg_device_parse` the
+device header parse against the host parse."""
 import os, sys, time
 import numpy as np
 import torch
@@ -313,7 +314,86 @@ def records_leg(n=256):
         % ('met' if ratio <= 0.1 else 'MISSED', max(ms_c), min(ms_p), ratio))
 
 
-LEGS = {'jpeg': jpeg_leg, 'jpeg_progressive': jpeg_progressive_leg, 'jpeg_parallel': jpeg_parallel_leg, 'records': records_leg}
+def jpeg_device_parse_leg(n=256):
+  """Headers on the device (asm_jpeg_parse, layout on the host, asm_jpeg_parse_fill) against the host parse + pack, on the
+  files of jpeg_leg and their 1024-file continuation, in one run.  Outputs are compared equal first.  Then, the two paths
+  alternating, three runs each: whole decode_batch(entropy='parallel') with parse='host' and parse='device' (host clock
+  around a call that ends in the status read-back); the two parse launches alone (device events); and the
+  records-to-pixels path, preprocess_batch on a RecordDataset batch with and without jpeg_resident."""
+  import tempfile
+  from assembled_cnn_amd import jpeg, records
+  many = photographic_files(4 * n, np.random.default_rng(1))       # the first n are jpeg_leg's files
+  sb = jpeg.DEFAULT_SEGMENT_BYTES
+  for files in (many[:n], many):
+    k = len(files)
+    ref = jpeg.decode_batch(files, 'cuda', entropy='parallel', parse='host')
+    got = jpeg.decode_batch(files, 'cuda', entropy='parallel', parse='device')
+    torch.cuda.synchronize()
+    assert np.array_equal(ref[1], got[1]) and ref[2] == got[2], 'the device parse lays the batch out differently'
+    used = torch.zeros(ref[0].numel(), dtype=torch.bool, device='cuda')
+    for o, (h, w) in zip(ref[1], ref[2]):
+      used[int(o):int(o) + h * w * 3] = True
+    assert torch.equal(ref[0][used], got[0][used]), 'the device parse decodes different pixels'
+    ms = {'host': [], 'device': []}
+    for _ in range(3):       # alternating
+      for parse in ('host', 'device'):
+        t0 = time.time(); jpeg.decode_batch(files, 'cuda', entropy='parallel', parse=parse); torch.cuda.synchronize()
+        ms[parse].append(1e3 * (time.time() - t0))
+    print('whole decode_batch(entropy=parallel), %d files (mean %.1f KB), ms per batch, three alternating runs:'
+          % (k, sum(map(len, files)) / k / 1e3))
+    for parse in ('host', 'device'):
+      print('  parse=%-6s: %s  (best %6.0f img/s)' % (parse, ' '.join('%8.2f' % m for m in ms[parse]), k / min(ms[parse]) * 1e3))
+    print('  fastest device / fastest host: %.3f' % (min(ms['device']) / min(ms['host'])))
+    # the two launches alone, on the files staged as pack_device stages them
+    arrays = [np.frombuffer(f, np.uint8) for f in files]
+    spans = np.zeros(k, jpeg.SPAN_DTYPE)
+    spans['length'] = [a.size for a in arrays]
+    spans['offset'], total = staging.slot_layout(spans['length'])
+    host = np.zeros(total, np.uint8)
+    for a, o in zip(arrays, spans['offset']):
+      host[int(o):int(o) + a.size] = a
+    bd, sd = torch.from_numpy(host).cuda(), staging.upload_table(spans, 'cuda')
+    heads_dev, tables_dev = ops.jpeg_parse(bd, sd, k, sb)
+    heads = heads_dev.cpu().numpy().view(jpeg.HEAD_DTYPE)
+    assert not heads['cls'].any()
+    t0 = time.time(); place, _, _, _, totals = jpeg.layout_heads(heads, None, (), sb); ms_layout = 1e3 * (time.time() - t0)
+    pd = staging.upload_table(place, 'cuda')
+    fill = lambda: ops.jpeg_parse_fill(bd, sd, k, heads_dev, tables_dev, pd, k, totals['n_intervals'], totals['total_segments'], sb)
+    assert not fill()[4].any()
+    ms_a = [ev(lambda: ops.jpeg_parse(bd, sd, k, sb), iters=5) for _ in range(3)]
+    ms_b = [ev(fill, iters=5) for _ in range(3)]
+    t0 = time.time(); pk = jpeg.pack(files, segment_bytes=sb); ms_pack = 1e3 * (time.time() - t0)
+    print('  asm_jpeg_parse alone      : %s ms per batch' % ' '.join('%8.3f' % m for m in ms_a))
+    print('  asm_jpeg_parse_fill alone : %s ms per batch' % ' '.join('%8.3f' % m for m in ms_b))
+    print('  layout_heads (host, numpy): %8.3f ms; jpeg.pack (parse + pack, host) of the same files: %8.2f ms' % (ms_layout, ms_pack))
+  # records to pixels
+  files = many[:n]
+  payloads = [records.encode_example({'image/encoded': [f], 'image/filename': [b'n%08d.JPEG' % i],
+                                      'image/class/label': np.array([i % 1000 + 1])}) for i, f in enumerate(files)]
+  with tempfile.TemporaryDirectory() as d:
+    for s in range(4):
+      records.write_records(os.path.join(d, 'validation-%05d-of-00004' % s), payloads[s::4])
+    names = records.get_filenames(False, d)
+    ms = {False: [], True: []}
+    outs = {}
+    for keep in (False, True, False, True, False, True):       # alternating, three runs each
+      ds = records.RecordDataset(names, False, n, 1, cycle_length=4, verify='device', device='cuda', keep_payloads=keep)
+      torch.cuda.synchronize()
+      t0 = time.time()
+      b = next(iter(ds))
+      kw = dict(jpeg_parse='device', jpeg_resident=b.payloads) if keep else {}
+      out = P.preprocess_batch(b.encoded, False, 'cuda', jpeg_entropy='parallel', **kw)
+      torch.cuda.synchronize()
+      ms[keep].append(1e3 * (time.time() - t0))
+      outs[keep] = out
+    assert torch.equal(outs[False], outs[True]), 'the resident path gives different pixels'
+    print('records to pixels, %d records (RecordDataset verify=device + preprocess_batch eval 224, jpeg_entropy=parallel), ms per batch:' % n)
+    print('  host parse, second upload      : %s  (best %6.0f img/s)' % (' '.join('%8.2f' % m for m in ms[False]), n / min(ms[False]) * 1e3))
+    print('  keep_payloads + jpeg_resident  : %s  (best %6.0f img/s)' % (' '.join('%8.2f' % m for m in ms[True]), n / min(ms[True]) * 1e3))
+    print('  fastest resident / fastest host: %.3f' % (min(ms[True]) / min(ms[False])))
+
+
+LEGS = {'jpeg_device_parse': jpeg_device_parse_leg, 'jpeg': jpeg_leg, 'jpeg_progressive': jpeg_progressive_leg, 'jpeg_parallel': jpeg_parallel_leg, 'records': records_leg}
 if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] in LEGS:
   LEGS[sys.argv[sys.argv.index('--only') + 1]]()
   sys.exit(0)
