@@ -194,11 +194,7 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
   `jpeg_parse`: 'device' reads the files' headers on the device as well (opt-in, jpeg.pack_device; the same pixels), and
   `jpeg_resident` then names files that lie on the device already -- records.Batch.payloads -- so that they are not
   uploaded again; `images` still holds the host bytes, read only for a file the device hands back."""
-  if jpeg_entropy not in _jpeg.ENTROPY_MODES:
-    raise ValueError('jpeg_entropy must be one of %s, got %r' % (_jpeg.ENTROPY_MODES, jpeg_entropy))
-  if jpeg_parse not in _jpeg.PARSE_MODES:
-    raise ValueError('jpeg_parse must be one of %s, got %r' % (_jpeg.PARSE_MODES, jpeg_parse))
-  _jpeg.check_parse_mode(jpeg_parse, jpeg_resident)
+  segment_bytes = _jpeg.check_modes(jpeg_entropy, None, jpeg_parse, jpeg_resident, prefix='jpeg_')
   if autoaugment_type is not None:
     _aa.check_policy_name(autoaugment_type)
   side, crop_type = output_size_and_crop_type(preprocessing_type, is_training, image_size)
@@ -206,7 +202,6 @@ def preprocess_batch(images: Sequence[np.ndarray], is_training: bool, device, im
     _jpeg.check_dct_method(dct_method)
   # encoded files are decoded on the device into their slots of the packed buffer, decoded arrays (given, or returned by
   # the fallback) travel to theirs in one staged copy; one window and one descriptor per slot
-  segment_bytes = _jpeg.DEFAULT_SEGMENT_BYTES if jpeg_entropy == 'parallel' else None
   if jpeg_parse == 'device':
     pk = _jpeg.pack_device(images, device, jpeg_resident, jpeg_fallback, progressive=jpeg_progressive,
                            segment_bytes=segment_bytes)

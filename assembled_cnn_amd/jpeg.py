@@ -69,6 +69,13 @@ def _as_array(data) -> np.ndarray:
   return np.frombuffer(bytes(data) if isinstance(data, memoryview) else data, dtype=np.uint8)
 
 
+def mcu_grid(width, height, ncomp, hs, vs):
+  """(MCUs across, MCUs down, 8x8 blocks of all components, each padded to whole MCUs) of an image with luma sampling
+  hs x vs; Python ints or numpy integer arrays alike"""
+  mcus_x, mcus_y = -(-width // (8 * hs)), -(-height // (8 * vs))
+  return mcus_x, mcus_y, mcus_x * mcus_y * ((ncomp == 3) * (hs * vs + 1) + 1)
+
+
 class ScanInfo:
   """One scan of a progressive file, as ``parse(..., progressive=True)`` found it."""
   __slots__ = ('components', 'ss', 'se', 'ah', 'al', 'huffman', 'restart_interval', 'begin', 'end', 'intervals', 'rst')
@@ -128,7 +135,7 @@ class JpegInfo:
   @property
   def n_blocks(self) -> int:
     """8x8 blocks of all components, each padded to whole MCUs"""
-    return self.n_mcus * (self.hs * self.vs + 2 if self.ncomp == 3 else 1)
+    return mcu_grid(self.width, self.height, self.ncomp, self.hs, self.vs)[2]
 
 
 def _u16(a: np.ndarray, at: int) -> int:
@@ -343,8 +350,7 @@ def parse(data, progressive: bool = False) -> JpegInfo:
   for (_, _, _, tq) in info.components:
     if tq not in info.qtables:
       raise ValueError('quantisation table %d is not defined' % tq)
-  info.mcus_x = -(-info.width // (8 * info.hs))
-  info.mcus_y = -(-info.height // (8 * info.vs))
+  info.mcus_x, info.mcus_y, _ = mcu_grid(info.width, info.height, info.ncomp, info.hs, info.vs)
   if info.scans is not None:
     why = _check_progression(info)
     return unsupported(why) if why else info
@@ -457,16 +463,17 @@ def _byte_pool(chunks):
   return pool, offsets[:-1]
 
 
-def _fill_rows(pk: Packed, index, infos, bodies):
-  """What a sequential and a progressive group fill alike for its images `index` (batch indices in row order, their bytes
-  in `bodies`): the byte pool and, per row, the offsets into it, into coefficients, planes and dst, the geometry, qsel and
-  the quantisation tables.  Returns (descs, tables, pool, each body's offset in it, total_blocks, max_blocks, max_pixels)."""
+def _fill_rows(pk: Packed, group, index, infos, bodies):
+  """What a sequential (group '') and a progressive group ('prog_') fill alike for its images `index` (batch indices in row
+  order, their bytes in `bodies`): the byte pool and, per row, the offsets into it, into coefficients, planes and dst, the
+  geometry, qsel and the quantisation tables.  Sets the group's files, descs, tables, total_blocks, max_blocks and
+  max_pixels in pk and returns each body's offset in the pool."""
   descs = np.zeros(len(index), DESC_DTYPE)
   tables = np.zeros(len(index), TABLES_DTYPE)
   pool, offsets = _byte_pool(bodies)
   blocks_at = max_blocks = max_pixels = 0
   for row, k in enumerate(index):
-    info, d = infos[k], descs[row]
+    info, d, n_blocks = infos[k], descs[row], infos[k].n_blocks
     d['scan_offset'], d['scan_bytes'] = offsets[row], bodies[row].size
     d['coef_offset'] = d['plane_offset'] = blocks_at * 64
     d['dst_offset'] = pk.offsets[k]
@@ -476,18 +483,20 @@ def _fill_rows(pk: Packed, index, infos, bodies):
       d['qsel'][c] = tq
     for tq, q in info.qtables.items():
       tables[row]['quant'][tq] = q
-    blocks_at += info.n_blocks
-    max_blocks = max(max_blocks, info.n_blocks)
+    blocks_at += n_blocks
+    max_blocks = max(max_blocks, n_blocks)
     max_pixels = max(max_pixels, info.width * info.height)
-  return descs, tables, pool, offsets, blocks_at, max_blocks, max_pixels
+  for field, value in (('files', pool), ('descs', descs), ('tables', tables), ('total_blocks', blocks_at),
+                       ('max_blocks', max_blocks), ('max_pixels', max_pixels)):
+    setattr(pk, group + field, value)
+  return offsets
 
 
-def _pack_sequential(pk: Packed, infos, arrays):
+def _pack_sequential(pk: Packed, files, infos):
   """The sequential rows' tables: per image one descriptor, its (at most two per class) Huffman tables and its rows of
   the interval table; with pk.segment_bytes also the segment table of asm_jpeg_decode_parallel."""
-  bodies = [arrays[k][infos[k].scan_begin:infos[k].scan_end] for k in pk.dev_index]
-  (pk.descs, pk.tables, pk.files, offsets, pk.total_blocks, pk.max_blocks,
-   pk.max_pixels) = _fill_rows(pk, pk.dev_index, infos, bodies)
+  bodies = [_as_array(files[k])[infos[k].scan_begin:infos[k].scan_end] for k in pk.dev_index]
+  offsets = _fill_rows(pk, '', pk.dev_index, infos, bodies)
   n_iv, iv_rows = 0, []
   for row, k in enumerate(pk.dev_index):
     info, d, t = infos[k], pk.descs[row], pk.tables[row]
@@ -514,13 +523,12 @@ def _pack_sequential(pk: Packed, infos, arrays):
     pk.segment_first, pk.total_segments = segment_table(pk.intervals, pk.segment_bytes)
 
 
-def _pack_progressive(pk: Packed, infos, arrays):
+def _pack_progressive(pk: Packed, files, infos):
   """The progressive rows' tables: per image one descriptor (its first_interval / n_intervals name its rows of the scan
   table), per scan one row, one pool entry per Huffman table a scan reads, and the scans' interval rows."""
   # every scan of the image, the marker segments between them included
-  bodies = [arrays[k][infos[k].scans[0].begin:infos[k].scans[-1].end] for k in pk.prog_index]
-  (pk.prog_descs, pk.prog_tables, pk.prog_files, offsets, pk.prog_total_blocks, pk.prog_max_blocks,
-   pk.prog_max_pixels) = _fill_rows(pk, pk.prog_index, infos, bodies)
+  bodies = [_as_array(files[k])[infos[k].scans[0].begin:infos[k].scans[-1].end] for k in pk.prog_index]
+  offsets = _fill_rows(pk, 'prog_', pk.prog_index, infos, bodies)
   n_scans, n_iv = 0, 0
   scan_rows, huffs, iv_rows = [], [], []
   for row, k in enumerate(pk.prog_index):
@@ -560,11 +568,19 @@ def check_segment_bytes(segment_bytes: int) -> int:
   return int(segment_bytes)
 
 
-def check_parse_mode(parse: str, resident=None):
+def check_modes(entropy: str, segment_bytes, parse: str, resident, prefix: str = '') -> Optional[int]:
+  """The mode arguments of decode_batch (prefix '') and preprocess_batch (prefix 'jpeg_', as its arguments are called):
+  ValueError for a bad one, else the segment_bytes to pack with -- DEFAULT_SEGMENT_BYTES for entropy='parallel' when none
+  was given.  Its range is pack's to check."""
+  if entropy not in ENTROPY_MODES:
+    raise ValueError('%sentropy must be one of %s, got %r' % (prefix, ENTROPY_MODES, entropy))
   if parse not in PARSE_MODES:
-    raise ValueError('parse must be one of %s, got %r' % (PARSE_MODES, parse))
+    raise ValueError('%sparse must be one of %s, got %r' % (prefix, PARSE_MODES, parse))
   if resident is not None and parse != 'device':
     raise ValueError("resident needs parse='device'")
+  if segment_bytes is not None and entropy != 'parallel':
+    raise ValueError("segment_bytes needs entropy='parallel'")
+  return DEFAULT_SEGMENT_BYTES if segment_bytes is None and entropy == 'parallel' else segment_bytes
 
 
 def segment_table(intervals: np.ndarray, segment_bytes: int):
@@ -579,15 +595,12 @@ def segment_table(intervals: np.ndarray, segment_bytes: int):
   return (ends - counts).astype(np.int32), total
 
 
-def _route(pk: Packed, files, infos, fallback, on_device=()):
-  """Where every entry of a batch goes: a sequential row (pk.dev_index), a progressive row (pk.prog_index) or a decoded
-  array in pk.fallback -- given, or made by ``fallback`` from a file of an unsupported kind (NotImplementedError without
-  one).  on_device: entries that are sequential rows without an info (pack_device).  Returns the rows' files as arrays."""
-  arrays = [None] * len(files)
+def _route(pk: Packed, files, infos, fallback):
+  """Where every entry of a batch goes by what the header reader found (`infos`; None for a decoded array): a sequential
+  row (pk.dev_index), a progressive row (pk.prog_index) or a decoded array in pk.fallback -- given, or made by
+  ``fallback`` from a file of an unsupported kind (NotImplementedError without one)."""
   for k, (f, info) in enumerate(zip(files, infos)):
-    if k in on_device:
-      pk.dev_index.append(k)
-    elif info is None:
+    if info is None:
       pk.fallback[k] = _check_decoded(f, k)
     elif info.unsupported is not None:
       if fallback is None:
@@ -595,9 +608,48 @@ def _route(pk: Packed, files, infos, fallback, on_device=()):
                                   % (k, info.unsupported))
       pk.fallback[k] = _check_decoded(fallback(bytes(f) if not isinstance(f, np.ndarray) else f.tobytes()), k)
     else:
-      arrays[k] = _as_array(f)
       (pk.prog_index if info.progressive else pk.dev_index).append(k)
-  return arrays
+
+
+class _HostHeaders:
+  """The header reader of ``pack``: parse, slot_layout, _pack_sequential."""
+
+  def __init__(self, infos):
+    self.infos = infos
+
+  def read(self, files, progressive, segment_bytes):
+    if self.infos is not None:
+      return self.infos
+    return [parse(f, progressive) if is_encoded(f) else None for f in files]
+
+  def layout(self, pk, tail):
+    return slot_layout([h * w * 3 for h, w in pk.sizes], pk.dev_index + tail)
+
+  sequential = staticmethod(_pack_sequential)
+
+
+def _pack(reader, files, fallback, progressive, segment_bytes) -> Packed:
+  """What pack and pack_device share.  `reader` reads the headers (-> per entry a JpegInfo, the _HeadInfo of a file whose
+  headers stay on the device, or None for a decoded array), lays out the output slots (-> offsets, total bytes) and makes
+  the sequential rows' tables."""
+  pk = Packed()
+  if segment_bytes is not None:
+    pk.segment_bytes = check_segment_bytes(segment_bytes)
+  infos = reader.read(files, progressive, pk.segment_bytes)
+  _route(pk, files, infos, fallback)
+  # output slots, 16-byte aligned (the src layout of asm_resize_crop_flip): the device-decoded entries first (sequential
+  # rows, then progressive rows), then the already decoded ones back to back, so that those travel in one host-to-device
+  # copy
+  pk.sizes = [(infos[k].height, infos[k].width) if k not in pk.fallback else pk.fallback[k].shape[:2]
+              for k in range(len(files))]
+  hosted = sorted(pk.fallback)
+  pk.offsets, total = reader.layout(pk, pk.prog_index + hosted)
+  pk.host_begin = int(pk.offsets[hosted[0]]) if hosted else total
+  pk.total_bytes = max(total, 16)
+  reader.sequential(pk, files, infos)
+  if pk.prog_index:
+    _pack_progressive(pk, files, infos)
+  return pk
 
 
 def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[List[JpegInfo]] = None,
@@ -608,25 +660,7 @@ def pack(files: Sequence, fallback: Optional[Callable] = None, infos: Optional[L
   progressive: progressive files the device decodes become rows of a second group (the prog_* fields, the tables of
   asm_jpeg_decode_progressive); `infos`, when given, must then have been parsed with the flag too.
   segment_bytes: also fill the segment table of asm_jpeg_decode_parallel for the sequential rows (entropy='parallel')."""
-  pk = Packed()
-  if segment_bytes is not None:
-    pk.segment_bytes = check_segment_bytes(segment_bytes)
-  n = len(files)
-  if infos is None:
-    infos = [parse(f, progressive) if is_encoded(f) else None for f in files]
-  arrays = _route(pk, files, infos, fallback)
-  # output slots, 16-byte aligned (the src layout of asm_resize_crop_flip): the device-decoded entries first (sequential
-  # rows, then progressive rows), then the already decoded ones back to back, so that those travel in one host-to-device
-  # copy
-  pk.sizes = [(infos[k].height, infos[k].width) if k not in pk.fallback else pk.fallback[k].shape[:2] for k in range(n)]
-  hosted = sorted(pk.fallback)
-  pk.offsets, total = slot_layout([h * w * 3 for h, w in pk.sizes], pk.dev_index + pk.prog_index + hosted)
-  pk.host_begin = int(pk.offsets[hosted[0]]) if hosted else total
-  pk.total_bytes = max(total, 16)
-  _pack_sequential(pk, infos, arrays)
-  if pk.prog_index:
-    _pack_progressive(pk, infos, arrays)
-  return pk
+  return _pack(_HostHeaders(infos), files, fallback, progressive, segment_bytes)
 
 
 def layout_heads(heads: np.ndarray, sizes=None, tail=(), segment_bytes: Optional[int] = None):
@@ -648,9 +682,8 @@ def layout_heads(heads: np.ndarray, sizes=None, tail=(), segment_bytes: Optional
   if sorted(order) != list(range(n)):
     raise ValueError('layout_heads: the class-0 rows and `tail` must name every entry once')
   offsets, total = slot_layout(hw[:, 0] * hw[:, 1] * 3, order)
-  width, height, hs, vs = (h[f].astype(np.int64) for f in ('width', 'height', 'hs', 'vs'))
-  n_mcus = -(-width // (8 * hs)) * -(-height // (8 * vs))
-  blocks = n_mcus * np.where(h['ncomp'] == 3, hs * vs + 2, 1)
+  width, height, ncomp, hs, vs = (h[f].astype(np.int64) for f in ('width', 'height', 'ncomp', 'hs', 'vs'))
+  blocks = mcu_grid(width, height, ncomp, hs, vs)[2]
   n_iv = h['n_intervals'].astype(np.int64)
   n_seg = h['n_segments'].astype(np.int64) if segment_bytes is not None else np.zeros(len(h), np.int64)
   totals = dict(total_blocks=int(blocks.sum()), max_blocks=int(blocks.max(initial=0)),
@@ -670,6 +703,71 @@ def layout_heads(heads: np.ndarray, sizes=None, tail=(), segment_bytes: Optional
   return place, order[:len(rows)], offsets, total, totals
 
 
+class _HeadInfo:
+  """What the host keeps of a file asm_jpeg_parse gave class 0: its size.  Routed as the JpegInfo of a sequential file;
+  the rest of its headers stays on the device."""
+  __slots__ = ('height', 'width')
+  unsupported, progressive = None, False
+
+  def __init__(self, height, width):
+    self.height, self.width = height, width
+
+
+class _DeviceHeaders:
+  """The header reader of ``pack_device``: asm_jpeg_parse and the one read-back, layout_heads, asm_jpeg_parse_fill."""
+
+  def __init__(self, device, resident):
+    self.dev, self.resident = device, resident
+
+  def read(self, files, progressive, segment_bytes):
+    n, dev = len(files), torch.device(self.dev)
+    encoded = [is_encoded(f) for f in files]
+    spans = np.zeros(n, SPAN_DTYPE)
+    if self.resident is not None:
+      buf, where = self.resident
+      where = np.asarray(where.cpu() if isinstance(where, torch.Tensor) else where, dtype=np.int64)
+      if (not isinstance(buf, torch.Tensor) or buf.dim() != 1 or buf.dtype != torch.uint8 or buf.device.type != dev.type or
+          (dev.index is not None and buf.device.index != dev.index)):
+        raise ValueError('resident: the buffer must be a 1-D uint8 tensor on %s' % dev)
+      if where.shape != (n, 2):
+        raise ValueError('resident: one (offset, length) per entry, got shape %s for %d entries' % (where.shape, n))
+      for k, e in enumerate(encoded):
+        if not e:
+          raise ValueError('entry %d: a decoded image cannot be resident' % k)
+      spans['offset'], spans['length'] = where[:, 0], where[:, 1]
+    else:
+      whole = [_as_array(f) for f, e in zip(files, encoded) if e]
+      spans['length'][encoded] = [a.size for a in whole]
+      spans['offset'], total = slot_layout(spans['length'])
+      buf = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+      stage_into(buf, whole, spans['offset'][encoded])
+    self.buf, self.spans_dev = buf, upload_table(spans, dev)
+    self.heads_dev, self.tables_dev = ops.jpeg_parse(buf, self.spans_dev, n, segment_bytes)
+    self.heads = heads = self.heads_dev.cpu().numpy().view(HEAD_DTYPE)        # the path's one synchronisation
+    infos = [None] * n
+    for k, (cls, height, width) in enumerate(zip(heads['cls'].tolist(), heads['height'].tolist(), heads['width'].tolist())):
+      if cls == 0:
+        infos[k] = _HeadInfo(height, width)
+      elif encoded[k]:
+        infos[k] = parse(files[k], progressive)
+        if infos[k].unsupported is None and not infos[k].progressive:
+          raise lib.AsmError('entry %d: asm_jpeg_parse refused (class %d) a file the host parser accepts' % (k, cls))
+    return infos
+
+  def layout(self, pk, tail):
+    self.place, rows, offsets, total, totals = layout_heads(self.heads, pk.sizes, tail, pk.segment_bytes)
+    assert rows == pk.dev_index
+    pk.total_blocks, pk.max_blocks, pk.max_pixels = totals['total_blocks'], totals['max_blocks'], totals['max_pixels']
+    pk.n_intervals, pk.total_segments = totals['n_intervals'], totals['total_segments']
+    return offsets, total
+
+  def sequential(self, pk, files, infos):
+    descs, tables, intervals, first, pk.fill_status = ops.jpeg_parse_fill(
+        self.buf, self.spans_dev, len(files), self.heads_dev, self.tables_dev, upload_table(self.place, self.dev),
+        len(self.place), pk.n_intervals, pk.total_segments, pk.segment_bytes)
+    pk.dev_tables = (self.buf, descs, tables, intervals, first)
+
+
 def pack_device(files: Sequence, device, resident=None, fallback: Optional[Callable] = None, progressive: bool = False,
                 segment_bytes: Optional[int] = None) -> Packed:
   """``pack`` with the headers read on the device: the sequential rows' tables come back as device tensors
@@ -680,59 +778,7 @@ def pack_device(files: Sequence, device, resident=None, fallback: Optional[Calla
   with `resident` it raises ValueError.  Two launches around ONE synchronisation (the head rows, 72 bytes a file).
   A file the device does not give class 0 goes through ``parse`` here exactly as in ``pack``: the same progressive rows,
   fallback calls, NotImplementedError and ValueError.  Slots, offsets and every decoded byte equal pack's."""
-  pk = Packed()
-  if segment_bytes is not None:
-    pk.segment_bytes = check_segment_bytes(segment_bytes)
-  n = len(files)
-  dev = torch.device(device)
-  encoded = [is_encoded(f) for f in files]
-  spans = np.zeros(n, SPAN_DTYPE)
-  if resident is not None:
-    buf, where = resident
-    where = np.asarray(where.cpu() if isinstance(where, torch.Tensor) else where, dtype=np.int64)
-    if (not isinstance(buf, torch.Tensor) or buf.dim() != 1 or buf.dtype != torch.uint8 or buf.device.type != dev.type or
-        (dev.index is not None and buf.device.index != dev.index)):
-      raise ValueError('resident: the buffer must be a 1-D uint8 tensor on %s' % dev)
-    if where.shape != (n, 2):
-      raise ValueError('resident: one (offset, length) per entry, got shape %s for %d entries' % (where.shape, n))
-    for k, e in enumerate(encoded):
-      if not e:
-        raise ValueError('entry %d: a decoded image cannot be resident' % k)
-    spans['offset'], spans['length'] = where[:, 0], where[:, 1]
-  else:
-    whole = [_as_array(f) for f, e in zip(files, encoded) if e]
-    spans['length'][encoded] = [a.size for a in whole]
-    spans['offset'], total = slot_layout(spans['length'])
-    buf = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
-    stage_into(buf, whole, spans['offset'][encoded])
-  spans_dev = upload_table(spans, dev)
-  heads_dev, tables_dev = ops.jpeg_parse(buf, spans_dev, n, pk.segment_bytes)
-  heads = heads_dev.cpu().numpy().view(HEAD_DTYPE)        # the path's one synchronisation
-  on_device = set(int(k) for k in np.flatnonzero(heads['cls'] == 0))
-  infos = [None] * n
-  for k in range(n):
-    if encoded[k] and k not in on_device:
-      infos[k] = parse(files[k], progressive)
-      if infos[k].unsupported is None and not infos[k].progressive:
-        raise lib.AsmError('entry %d: asm_jpeg_parse refused (class %d) a file the host parser accepts'
-                           % (k, int(heads['cls'][k])))
-  arrays = _route(pk, files, infos, fallback, on_device)
-  pk.sizes = [(int(heads['height'][k]), int(heads['width'][k])) if k in on_device else
-              pk.fallback[k].shape[:2] if k in pk.fallback else (infos[k].height, infos[k].width) for k in range(n)]
-  hosted = sorted(pk.fallback)
-  place, rows, pk.offsets, total, totals = layout_heads(heads, pk.sizes, pk.prog_index + hosted, pk.segment_bytes)
-  assert rows == pk.dev_index
-  pk.host_begin = int(pk.offsets[hosted[0]]) if hosted else total
-  pk.total_bytes = max(total, 16)
-  pk.total_blocks, pk.max_blocks, pk.max_pixels = totals['total_blocks'], totals['max_blocks'], totals['max_pixels']
-  pk.n_intervals, pk.total_segments = totals['n_intervals'], totals['total_segments']
-  descs, tables, intervals, first, pk.fill_status = ops.jpeg_parse_fill(
-      buf, spans_dev, n, heads_dev, tables_dev, upload_table(place, dev), len(place), pk.n_intervals, pk.total_segments,
-      pk.segment_bytes)
-  pk.dev_tables = (buf, descs, tables, intervals, first)
-  if pk.prog_index:
-    _pack_progressive(pk, infos, arrays)
-  return pk
+  return _pack(_DeviceHeaders(device, resident), files, fallback, progressive, segment_bytes)
 
 
 def _raise_corrupt(status_rows):
@@ -809,13 +855,7 @@ def decode_batch(files: Sequence, device, fallback: Optional[Callable] = None, d
   parse: 'device' reads the headers on the device too (pack_device; opt-in, every result is the same); resident: the
   (buffer, spans) of files that lie on the device already (parse='device' only)."""
   check_dct_method(dct_method)
-  if entropy not in ENTROPY_MODES:
-    raise ValueError('entropy must be one of %s, got %r' % (ENTROPY_MODES, entropy))
-  check_parse_mode(parse, resident)
-  if entropy == 'parallel':
-    segment_bytes = DEFAULT_SEGMENT_BYTES if segment_bytes is None else segment_bytes
-  elif segment_bytes is not None:
-    raise ValueError("segment_bytes needs entropy='parallel'")
+  segment_bytes = check_modes(entropy, segment_bytes, parse, resident)
   if parse == 'device':
     pk = pack_device(files, device, resident, fallback, progressive=progressive, segment_bytes=segment_bytes)
   else:

@@ -1018,16 +1018,33 @@ def autoaugment(images_f32, descs_dev, subtract_mean):
   return out
 
 
+def _check_tables(text, *tables, uint8=False):
+  """tables: (device table, bytes per struct, count).  ValueError(text) unless every table holds exactly count structs,
+  which a negative count never does; uint8: and is a byte tensor."""
+  if any((uint8 and t.dtype != torch.uint8) or t.numel() * t.element_size() != size * count for t, size, count in tables):
+    raise ValueError(text)
+
+
+def _rows(n, device, dtype=torch.int32, *row):
+  """A [n, *row] device tensor that may be empty: rows [0, n) of an allocation of at least one row"""
+  return torch.empty((max(n, 1),) + row, dtype=dtype, device=device)[:n]
+
+
+def _struct_rows(n, device, struct):
+  """the uint8 device view of a table of n `struct` that the library fills"""
+  return _rows(n, device, torch.uint8, C.sizeof(struct)).flatten()
+
+
 def _jpeg_begin(name, counts, descs_dev, tables_dev, rows, dst, workspace_fn, *workspace_args):
   """What the three JPEG wrappers do first.  counts: the call's counts by name, n first, in the order of the error text;
   rows: (device table, bytes per row, name of its count) beside the n descriptors and n asm_jpeg_tables.  Returns (int32
   [n] device status, workspace); for n = 0 the workspace is None and the library is not called.  workspace_fn /
   workspace_args: the library's *_workspace_bytes (without asm_) and its arguments."""
-  rows = ((descs_dev, C.sizeof(_lib.JpegDesc), 'n'), (tables_dev, C.sizeof(_lib.JpegTables), 'n')) + rows
-  if any(t.numel() * t.element_size() != size * counts[c] for t, size, c in rows):
-    raise ValueError('%s: table sizes do not match %s' % (name, ', '.join('%s = %d' % kv for kv in counts.items())))
   n = counts['n']
-  status = torch.empty((max(n, 1),), dtype=torch.int32, device=dst.device)[:n]
+  _check_tables('%s: table sizes do not match %s' % (name, ', '.join('%s = %d' % kv for kv in counts.items())),
+                (descs_dev, C.sizeof(_lib.JpegDesc), n), (tables_dev, C.sizeof(_lib.JpegTables), n),
+                *((t, size, counts[c]) for t, size, c in rows))
+  status = _rows(n, dst.device)
   if n == 0:
     return status, None
   need = C.c_int64(0)
@@ -1060,7 +1077,7 @@ def jpeg_decode_parallel(files_u8, descs_dev, tables_dev, intervals_dev, segment
   rows = ((intervals_dev, C.sizeof(_lib.JpegInterval), 'n_intervals'), (segment_first_dev, 4, 'n_intervals'))
   status, ws = _jpeg_begin('jpeg_decode_parallel', dict(n=n, n_intervals=n_intervals), descs_dev, tables_dev, rows, dst,
                            'jpeg_decode_parallel_workspace_bytes', total_blocks, total_segments)
-  info_dev = torch.zeros((max(n, 1), 2), dtype=torch.int32, device=dst.device)[:n] if info else None
+  info_dev = _rows(n, dst.device, torch.int32, 2).zero_() if info else None
   if n:
     check(L().asm_jpeg_decode_parallel(_ptr(files_u8), files_u8.numel(), _ptr(descs_dev), _ptr(tables_dev),
                                        _ptr(intervals_dev), _ptr(segment_first_dev), n, n_intervals, total_segments,
@@ -1093,10 +1110,9 @@ def crc32c_spans(buf_u8, spans_dev, n):
   per span).  records.RecordDataset reads the status and raises for a corrupt record."""
   if buf_u8.dim() != 1 or buf_u8.dtype != torch.uint8 or spans_dev.dtype != torch.uint8:
     raise ValueError('crc32c_spans: buffer and descriptor table are 1-D uint8 tensors')
-  if n < 0 or spans_dev.numel() != C.sizeof(_lib.SpanDesc) * n:
-    raise ValueError('crc32c_spans: descriptor table must hold %d bytes' % (C.sizeof(_lib.SpanDesc) * max(n, 0)))
-  out = torch.empty((2, max(n, 1)), dtype=torch.int32, device=buf_u8.device)[:, :n]
-  crc, status = out[0], out[1]
+  _check_tables('crc32c_spans: descriptor table must hold %d bytes' % (C.sizeof(_lib.SpanDesc) * max(n, 0)),
+                (spans_dev, C.sizeof(_lib.SpanDesc), n))
+  crc, status = _rows(n, buf_u8.device), _rows(n, buf_u8.device)
   if n:
     check(L().asm_crc32c_spans(_ptr(buf_u8), buf_u8.numel(), _ptr(spans_dev), n, _ptr(crc), _ptr(status), _stream()),
           'crc32c_spans')
@@ -1115,14 +1131,13 @@ def jpeg_parse(buf_u8, spans_dev, n, segment_bytes=None):
   of asm_jpeg_decode_parallel."""
   if buf_u8.dim() != 1 or buf_u8.dtype != torch.uint8 or spans_dev.dtype != torch.uint8:
     raise ValueError('jpeg_parse: buffer and descriptor table are 1-D uint8 tensors')
-  if n < 0 or spans_dev.numel() != C.sizeof(_lib.SpanDesc) * n:
-    raise ValueError('jpeg_parse: descriptor table must hold %d bytes' % (C.sizeof(_lib.SpanDesc) * max(n, 0)))
-  heads = torch.empty(max(n, 1) * C.sizeof(_lib.JpegHead), dtype=torch.uint8, device=buf_u8.device)
-  tables = torch.empty(max(n, 1) * C.sizeof(_lib.JpegTables), dtype=torch.uint8, device=buf_u8.device)
+  _check_tables('jpeg_parse: descriptor table must hold %d bytes' % (C.sizeof(_lib.SpanDesc) * max(n, 0)),
+                (spans_dev, C.sizeof(_lib.SpanDesc), n))
+  heads, tables = _struct_rows(n, buf_u8.device, _lib.JpegHead), _struct_rows(n, buf_u8.device, _lib.JpegTables)
   if n:
     check(L().asm_jpeg_parse(_ptr(buf_u8), buf_u8.numel(), _ptr(spans_dev), n, _segment_bytes_arg(segment_bytes), _ptr(heads),
                              _ptr(tables), _stream()), 'jpeg_parse')
-  return heads[:n * C.sizeof(_lib.JpegHead)], tables[:n * C.sizeof(_lib.JpegTables)]
+  return heads, tables
 
 
 def jpeg_parse_fill(buf_u8, spans_dev, n_spans, heads_dev, tables_dev, place_dev, n_rows, n_intervals, total_segments,
@@ -1132,28 +1147,24 @@ def jpeg_parse_fill(buf_u8, spans_dev, n_spans, heads_dev, tables_dev, place_dev
   asm_jpeg_tables and n_intervals struct asm_jpeg_interval, the int32 [n_intervals] segment table (None without
   segment_bytes) and the int32 [n_rows] status (0 or JPEG_EDESC): the tables of jpeg_decode / jpeg_decode_parallel with
   files = buf_u8."""
-  for t, size, count, what in ((spans_dev, C.sizeof(_lib.SpanDesc), n_spans, 'n_spans'),
-                               (heads_dev, C.sizeof(_lib.JpegHead), n_spans, 'n_spans'),
-                               (tables_dev, C.sizeof(_lib.JpegTables), n_spans, 'n_spans'),
-                               (place_dev, C.sizeof(_lib.JpegPlace), n_rows, 'n_rows')):
-    if count < 0 or t.dtype != torch.uint8 or t.numel() != size * count:
-      raise ValueError('jpeg_parse_fill: table sizes do not match %s = %d' % (what, count))
+  _check_tables('jpeg_parse_fill: table sizes do not match n_spans = %d' % n_spans,
+                (spans_dev, C.sizeof(_lib.SpanDesc), n_spans), (heads_dev, C.sizeof(_lib.JpegHead), n_spans),
+                (tables_dev, C.sizeof(_lib.JpegTables), n_spans), uint8=True)
+  _check_tables('jpeg_parse_fill: table sizes do not match n_rows = %d' % n_rows,
+                (place_dev, C.sizeof(_lib.JpegPlace), n_rows), uint8=True)
   if n_intervals < 0 or total_segments < 0:
     raise ValueError('jpeg_parse_fill: n_intervals = %d, total_segments = %d' % (n_intervals, total_segments))
   dev = buf_u8.device
-  descs = torch.empty(max(n_rows, 1) * C.sizeof(_lib.JpegDesc), dtype=torch.uint8, device=dev)
-  tables = torch.empty(max(n_rows, 1) * C.sizeof(_lib.JpegTables), dtype=torch.uint8, device=dev)
-  intervals = torch.empty(max(n_intervals, 1) * C.sizeof(_lib.JpegInterval), dtype=torch.uint8, device=dev)
-  first = torch.empty(max(n_intervals, 1), dtype=torch.int32, device=dev) if segment_bytes is not None else None
-  status = torch.empty(max(n_rows, 1), dtype=torch.int32, device=dev)
+  descs, tables = _struct_rows(n_rows, dev, _lib.JpegDesc), _struct_rows(n_rows, dev, _lib.JpegTables)
+  intervals = _struct_rows(n_intervals, dev, _lib.JpegInterval)
+  first = _rows(n_intervals, dev) if segment_bytes is not None else None
+  status = _rows(n_rows, dev)
   if n_rows:
     check(L().asm_jpeg_parse_fill(_ptr(buf_u8), buf_u8.numel(), _ptr(spans_dev), n_spans, _ptr(heads_dev), _ptr(tables_dev),
                                   _ptr(place_dev), n_rows, n_intervals, total_segments, _segment_bytes_arg(segment_bytes),
                                   _ptr(descs), _ptr(tables), _ptr(intervals), _ptr(first), _ptr(status), _stream()),
           'jpeg_parse_fill')
-  return (descs[:n_rows * C.sizeof(_lib.JpegDesc)], tables[:n_rows * C.sizeof(_lib.JpegTables)],
-          intervals[:n_intervals * C.sizeof(_lib.JpegInterval)], None if first is None else first[:n_intervals],
-          status[:n_rows])
+  return descs, tables, intervals, first, status
 
 
 # ---------------------------------------------------------------------------------------------------

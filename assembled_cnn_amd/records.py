@@ -434,8 +434,8 @@ class RecordDataset(object):
     self.num_epochs, self.cycle_length, self.drop_remainder = int(num_epochs), int(cycle_length), bool(drop_remainder)
     self.return_logits, self.num_classes, self.seed = bool(return_logits), int(num_classes), seed
     self.verify, self.device, self.keep_payloads = verify, torch.device(device), bool(keep_payloads)
-    self._host = self._dev = None         # grow-only staging buffers of the device check
-    self._uploaded = None                 # event behind the last asynchronous copy out of the pinned buffer
+    self._staging = staging.Staging()     # its own: a record upload and a pixel upload do not wait on each other's buffer
+    self._dev = None                      # grow-only device buffer the payloads are copied to
 
   def records(self) -> Iterator[Tuple[RecordFile, int]]:
     """(shard, record index) in the order the batches are cut from"""
@@ -471,21 +471,10 @@ class RecordDataset(object):
     lengths = np.array([f.lengths[i] for f, i in recs], dtype=np.int64)
     offsets, total = staging.slot_layout(lengths)
     total = max(total, 16)
-    pin = self.device.type == 'cuda'
-    if self._uploaded is not None:
-      self._uploaded.synchronize()         # the previous batch's copy still reads the pinned buffer
-      self._uploaded = None
-    if self._host is None or self._host.numel() < total:
-      self._host = torch.empty(int(total * 1.25) + 4096, dtype=torch.uint8, pin_memory=pin)
-      self._dev = torch.empty(self._host.numel(), dtype=torch.uint8, device=self.device)
-    host = self._host.numpy()
-    for (f, i), o, ln in zip(recs, offsets, lengths):
-      host[int(o):int(o) + int(ln)] = f.payload(i)
+    if self._dev is None or self._dev.numel() < total:
+      self._dev = torch.empty(int(total * 1.25) + 4096, dtype=torch.uint8, device=self.device)
     dev = self._dev[:total]
-    dev.copy_(self._host[:total], non_blocking=True)
-    if pin:
-      self._uploaded = torch.cuda.Event()
-      self._uploaded.record()
+    self._staging.stage_into(dev, [f.payload(i) for f, i in recs], offsets)
     return dev, offsets, lengths
 
   def _verify_device(self, recs, uploaded):

@@ -1,11 +1,9 @@
-"""Host-to-device staging of the input path: the 16-byte slot layout of a packed batch, the grow-only host buffer the
-decoded pixels are gathered in (pinned for a GPU), its one asynchronous copy, and the upload of a descriptor table."""
+"""Host-to-device staging of the input path: the 16-byte slot layout of a packed batch, the grow-only host buffer a batch's
+bytes are gathered in (pinned for a GPU) with its one asynchronous copy (Staging), and the upload of a descriptor table."""
 from __future__ import annotations
 
 import numpy as np
 import torch
-
-_STAGING = {}     # pin (bool) -> buffer; 'event' -> the last asynchronous copy out of the pinned one
 
 
 def slot_layout(nbytes, order=None):
@@ -19,30 +17,40 @@ def slot_layout(nbytes, order=None):
   return offsets, int(padded.sum())
 
 
-def fill(nbytes: int, arrays, offsets, pin: bool) -> torch.Tensor:
-  """uint8 arrays -> the first `nbytes` of the staging buffer, each at its offset (one memcpy per array; copies if not
-  contiguous).  The buffer is re-used across batches (a fresh 150 MB allocation costs more in page faults than the copy
-  itself), so the previous batch must have been consumed; for the pinned one that is waited for here."""
-  ev = _STAGING.get('event')
-  if pin and ev is not None:
-    ev.synchronize()            # the previous batch's asynchronous H2D copy reads this buffer
-  buf = _STAGING.get(pin)
-  if buf is None or buf.numel() < nbytes:
-    buf = _STAGING[pin] = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, pin_memory=pin)
-  host = buf.numpy()
-  for a, o in zip(arrays, offsets):
-    host[int(o):int(o) + a.size] = a.reshape(-1)
-  return buf[:nbytes]
+class Staging:
+  """A grow-only host buffer per pin state and the event behind the last asynchronous copy out of the pinned one.  Two
+  instances share nothing, so their users never wait for each other's copy."""
+
+  def __init__(self):
+    self._bufs = {}       # pin (bool) -> buffer
+    self._event = None    # the last asynchronous copy out of the pinned buffer
+
+  def fill(self, nbytes: int, arrays, offsets, pin: bool) -> torch.Tensor:
+    """uint8 arrays -> the first `nbytes` of the staging buffer, each at its offset (one memcpy per array; copies if not
+    contiguous).  The buffer is re-used across batches (a fresh 150 MB allocation costs more in page faults than the copy
+    itself), so the previous batch must have been consumed; for the pinned one that is waited for here."""
+    if pin and self._event is not None:
+      self._event.synchronize()   # the previous batch's asynchronous H2D copy reads this buffer
+    buf = self._bufs.get(pin)
+    if buf is None or buf.numel() < nbytes:
+      buf = self._bufs[pin] = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, pin_memory=pin)
+    host = buf.numpy()
+    for a, o in zip(arrays, offsets):
+      host[int(o):int(o) + a.size] = a if a.ndim == 1 else a.reshape(-1)    # (a view of a mapped shard is slow to reshape)
+    return buf[:nbytes]
+
+  def stage_into(self, region: torch.Tensor, arrays, offsets):
+    """Decoded uint8 arrays -> the staging buffer at `offsets` -> ONE host-to-device copy into `region` (a uint8 device view
+    whose first byte is offset 0).  The copy is asynchronous: the next user of the pinned buffer waits for its event."""
+    region.copy_(self.fill(region.numel(), arrays, offsets, region.is_cuda), non_blocking=True)
+    if region.is_cuda:
+      self._event = torch.cuda.Event()
+      self._event.record()
 
 
-def stage_into(region: torch.Tensor, arrays, offsets):
-  """Decoded uint8 arrays -> the staging buffer at `offsets` -> ONE host-to-device copy into `region` (a uint8 device view
-  whose first byte is offset 0).  The copy is asynchronous: the next user of the pinned buffer waits for its event."""
-  region.copy_(fill(region.numel(), arrays, offsets, region.is_cuda), non_blocking=True)
-  if region.is_cuda:
-    ev = torch.cuda.Event()
-    ev.record()
-    _STAGING['event'] = ev
+_DEFAULT = Staging()      # the pixel path's (pack_batch, decode_packed, pack_device)
+fill = _DEFAULT.fill
+stage_into = _DEFAULT.stage_into
 
 
 def upload_table(array: np.ndarray, device) -> torch.Tensor:
