@@ -1,5 +1,5 @@
 """Guard-band plumbing and element-wise bounds shared by the GPU edge-shape modules (tests/test_gpu_rows_edges.py,
-tests/test_gpu_pool_edges.py, tests/test_gpu_bn_edges.py, tests/test_gpu_step_edges.py).  A plain module, not a conftest: the test modules import what they use, the autouse fixture
+tests/test_gpu_pool_edges.py, tests/test_gpu_bn_edges.py, tests/test_gpu_step_edges.py, tests/test_gpu_conv_exact.py).  A plain module, not a conftest: the test modules import what they use, the autouse fixture
 ``_release_inputs`` included.
 
 * ``Out``: an output between two 4 KiB flanks of the byte 0xA5 which must survive the call; the output itself starts as 0xA5,
@@ -63,6 +63,19 @@ class Out(object):
     a = a.double().numpy()
     assert np.isfinite(a).all() and (np.abs(a) < 1e29).all() if a.size else True, 'NaN or huge value in an output'
     return a
+
+
+class Work(Out):
+  """a workspace of exactly ``nbytes`` bytes between the flanks; ``p`` is a null pointer for an empty one.  The kernel may
+  leave anything inside; ``check_flanks`` tells whether it stayed inside."""
+
+  def __init__(self, nbytes):
+    Out.__init__(self, (int(nbytes),), torch.uint8)
+    self.nbytes = int(nbytes)
+
+  @property
+  def p(self):
+    return ptr(self.t) if self.nbytes else 0
 
 
 def dev(a, dtype=torch.float32):
