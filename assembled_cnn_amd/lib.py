@@ -87,6 +87,20 @@ assert C.sizeof(SpanDesc) == 24
 SPAN_EDESC, SPAN_EMISMATCH = 1, 2      # asm_crc32c_spans' status bits
 
 
+class ExampleRow(C.Structure):
+  """struct asm_example_row"""
+  _fields_ = [('cls', C.c_int32), ('label', C.c_int32), ('enc_offset', C.c_int64), ('name_offset', C.c_int64),
+              ('logit_offset', C.c_int64), ('enc_length', C.c_int32), ('name_length', C.c_int32),
+              ('logit_count', C.c_int32), ('n_boxes', C.c_int32)]
+
+
+assert C.sizeof(ExampleRow) == 48
+EXAMPLE_WINDOW = 1024                  # ASM_EXAMPLE_WINDOW: bytes of asm_example_parse's window
+# asm_example_parse's class bits (diagnostics; 0 = a record records._proto accepts) and asm_example_label_rows' status
+EXAMPLE_PSPAN, EXAMPLE_PMALFORMED, EXAMPLE_PSCHEMA, EXAMPLE_PFORM = 1, 2, 4, 8
+EXAMPLE_LSKIP, EXAMPLE_LRANGE = 1, 2
+
+
 class JpegHead(C.Structure):
   """struct asm_jpeg_head"""
   _fields_ = [(n, C.c_int32) for n in ('cls', 'width', 'height', 'ncomp', 'hs', 'vs', 'restart_interval', 'n_intervals')] + [
@@ -301,6 +315,8 @@ SIGNATURES = {
     'asm_jpeg_decode_progressive': (_I, [_P, C.c_int64, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_int64, _I, _I, _P, C.c_int64, _P,
                                          _P, C.c_int64, _I, _P]),
     'asm_crc32c_spans': (_I, [_P, C.c_int64, _P, _I, _P, _P, _P]),
+    'asm_example_parse': (_I, [_P, C.c_int64, _P, _I, _P, _P]),
+    'asm_example_label_rows': (_I, [_P, C.c_int64, _P, _I, _I, _P, _I, _P, _P]),
     'asm_jpeg_parse': (_I, [_P, C.c_int64, _P, _I, _I, _P, _P, _P]),
     'asm_jpeg_parse_fill': (_I, [_P, C.c_int64, _P, _I, _P, _P, _P, _I, _I, C.c_int64, _I, _P, _P, _P, _P, _P, _P]),
     'asm_model_plan': (_I, [C.POINTER(ModelCfg), _I, _I, _I, C.POINTER(PlanEntry), _I, C.POINTER(PlanSummary)]),

@@ -1119,6 +1119,44 @@ def crc32c_spans(buf_u8, spans_dev, n):
   return crc, status
 
 
+def example_parse(buf_u8, spans_dev, n):
+  """asm_example_parse: buf_u8 a 1-D uint8 device buffer that holds serialised tf.train.Example protos, spans_dev a uint8
+  device view of n packed struct asm_span_desc (the byte range of each).  One launch, no synchronisation.  Returns the
+  uint8 device view of n struct asm_example_row: per record its class -- 0 where records._proto accepts it -- and then the
+  positions of the image, the filename and the logits in buf_u8, the label and the number of boxes."""
+  if buf_u8.dim() != 1 or buf_u8.dtype != torch.uint8 or spans_dev.dtype != torch.uint8:
+    raise ValueError('example_parse: buffer and descriptor table are 1-D uint8 tensors')
+  _check_tables('example_parse: descriptor table must hold %d bytes' % (C.sizeof(_lib.SpanDesc) * max(n, 0)),
+                (spans_dev, C.sizeof(_lib.SpanDesc), n))
+  rows = _struct_rows(n, buf_u8.device, _lib.ExampleRow)
+  if n:
+    check(L().asm_example_parse(_ptr(buf_u8), buf_u8.numel(), _ptr(spans_dev), n, _ptr(rows), _stream()), 'example_parse')
+  return rows
+
+
+def example_label_rows(buf_u8, rows_dev, n, num_classes, out=None):
+  """asm_example_label_rows behind example_parse: the float32 [n, 2 * num_classes] rows concat(one_hot(label), logits) of
+  knowledge distillation, the logits copied bit for bit out of buf_u8.  Returns (out, int32 [n] device status); a row whose
+  status is not 0 (EXAMPLE_LSKIP, EXAMPLE_LRANGE) is left as it was -- uninitialised in a fresh `out`: the caller fills it."""
+  if buf_u8.dim() != 1 or buf_u8.dtype != torch.uint8:
+    raise ValueError('example_label_rows: the buffer is a 1-D uint8 tensor')
+  _check_tables('example_label_rows: the row table must hold %d bytes' % (C.sizeof(_lib.ExampleRow) * max(n, 0)),
+                (rows_dev, C.sizeof(_lib.ExampleRow), n), uint8=True)
+  if num_classes < 1:
+    raise ValueError('example_label_rows: num_classes = %d' % num_classes)
+  if out is None:
+    out = _rows(n, buf_u8.device, torch.float32, 2 * num_classes)
+  if out.dim() != 2 or out.dtype != torch.float32 or out.shape[0] != n or out.stride(1) != 1 or out.stride(0) < 2 * num_classes:
+    raise ValueError('example_label_rows: out is float32 [n, >= 2 * num_classes] with unit column stride')
+  status = _rows(n, buf_u8.device)
+  if n:
+    if not out.is_cuda and not _IS_DOUBLE:
+      raise _lib.AsmError('assembled_cnn_amd ops need GPU tensors (no CPU fallback)')
+    check(L().asm_example_label_rows(_ptr(buf_u8), buf_u8.numel(), _ptr(rows_dev), n, num_classes, out.data_ptr(),
+                                     out.stride(0), _ptr(status), _stream()), 'example_label_rows')
+  return out, status
+
+
 def _segment_bytes_arg(segment_bytes) -> int:
   return 0 if segment_bytes is None else int(segment_bytes)
 

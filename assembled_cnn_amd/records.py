@@ -11,7 +11,8 @@ functions/input_fns.py:33-94, utils/data_util.py:161-265 and :389-473), read int
 
 TensorFlow's record reader verifies the CRC-32C behind every payload.  Here a batch's payloads are gathered into a pinned
 staging buffer of this module's own, copied to the device once and checked there by one launch (``ops.crc32c_spans``):
-the host checksum (tf_bundle.crc32c, ~70 MB/s) cannot keep up with a training step.  DESIGN.md section 1.3 has the rules.
+the host checksum (tf_bundle.crc32c, ~70 MB/s) cannot keep up with a training step.  With ``parse='device'`` the Examples
+are walked there too (``ops.example_parse``, ``ops.example_label_rows``).  DESIGN.md section 1.3 has the rules.
 """
 from __future__ import annotations
 
@@ -29,6 +30,8 @@ from .tf_bundle import _crc32c_bytes, _put_varint, crc32c, mask_crc
 
 SPAN_DTYPE = np.dtype(_lib.SpanDesc)
 VERIFY_MODES = ('device', 'host', 'none')
+PARSE_MODES = ('host', 'device')
+ROW_DTYPE = np.dtype(_lib.ExampleRow)
 _HEADER, _FOOTER = 12, 4
 
 
@@ -306,6 +309,20 @@ def _kd_label(label, logit, num_classes: int) -> np.ndarray:
   return row
 
 
+def proto_row(buf, base: int = 0):
+  """_proto's result as the row asm_example_parse writes for a class-0 record whose first byte lies at ``base`` (one
+  ROW_DTYPE record), and the logit values.  The values need not lie packed in the payload, so ``logit_offset`` is ``base``:
+  the caller has the values.  Raises what _proto raises."""
+  (b, e), label, bbox, _, logit = _proto(buf)
+  nb, ne = _fixed(_example(buf), 'image/filename', 'bytes', (0, 0))
+  row = np.zeros((), dtype=ROW_DTYPE)
+  row['label'], row['logit_count'], row['n_boxes'] = label, logit.size, bbox.shape[1]
+  row['enc_offset'], row['enc_length'] = base + b, e - b
+  row['name_offset'], row['name_length'] = base + nb, ne - nb
+  row['logit_offset'] = base
+  return row, logit
+
+
 def parse_record_sup(payload, return_logits: bool = False, num_classes: int = 1001) -> dict:
   """data_util.parse_record_sup (:210-235) up to the image preprocessing, which runs on the device for a whole batch
   (preprocess_batch): {'image': the encoded bytes, 'label': int32, or with return_logits the float32 [2 * num_classes]
@@ -418,14 +435,23 @@ class RecordDataset(object):
   ``keep_payloads``: the batch's payloads go to ``device`` under every ``verify`` mode (which then only decides about the
   checksum launch and its read-back) and ``Batch.payloads`` names the encoded images in that buffer, so that the JPEG
   decoder reads them where they are instead of uploading them again.  The buffer is the dataset's own and is refilled by
-  the next batch."""
+  the next batch.
+
+  ``parse``: 'host' -- records._proto record by record.  'device' -- the payloads go to ``device`` as above,
+  ops.example_parse walks every record's Example there and the rows come back with the checksum status behind one wait;
+  a record the device does not classify as plain (asm_example_row.cls != 0) is parsed by the host as before, so results and
+  error texts are the same.  With ``return_logits`` the label rows are written on the device (ops.example_label_rows) and
+  ``Batch.labels`` is that float32 device tensor; without, it is the int32 CPU tensor of 'host'."""
 
   def __init__(self, filenames: Sequence[str], is_training: bool, batch_size: int, shuffle_buffer: int,
                num_train_files: Optional[int] = None, num_epochs: int = 1, cycle_length: int = 20,
                drop_remainder: bool = False, return_logits: bool = False, num_classes: int = 1001,
-               seed: Optional[int] = None, verify: str = 'device', device='cuda', keep_payloads: bool = False):
+               seed: Optional[int] = None, verify: str = 'device', device='cuda', keep_payloads: bool = False,
+               parse: str = 'host'):
     if verify not in VERIFY_MODES:
       raise ValueError('verify must be one of %s, got %r' % (VERIFY_MODES, verify))
+    if parse not in PARSE_MODES:
+      raise ValueError('parse must be one of %s, got %r' % (PARSE_MODES, parse))
     if batch_size < 1 or cycle_length < 1 or num_epochs < 0 or (is_training and shuffle_buffer < 1):
       raise ValueError('batch_size, cycle_length and shuffle_buffer are positive, num_epochs is not negative')
     self.filenames = list(filenames)
@@ -434,6 +460,7 @@ class RecordDataset(object):
     self.num_epochs, self.cycle_length, self.drop_remainder = int(num_epochs), int(cycle_length), bool(drop_remainder)
     self.return_logits, self.num_classes, self.seed = bool(return_logits), int(num_classes), seed
     self.verify, self.device, self.keep_payloads = verify, torch.device(device), bool(keep_payloads)
+    self.parse = parse
     self._staging = staging.Staging()     # its own: a record upload and a pixel upload do not wait on each other's buffer
     self._dev = None                      # grow-only device buffer the payloads are copied to
 
@@ -477,19 +504,88 @@ class RecordDataset(object):
     self._staging.stage_into(dev, [f.payload(i) for f, i in recs], offsets)
     return dev, offsets, lengths
 
-  def _verify_device(self, recs, uploaded):
-    n = len(recs)
-    dev, offsets, lengths = uploaded
-    spans = np.zeros(n, dtype=SPAN_DTYPE)
+  def _span_table(self, recs, uploaded):
+    """the device table of the uploaded payloads' spans, each with the masked crc its record stores"""
+    _, offsets, lengths = uploaded
+    spans = np.zeros(len(recs), dtype=SPAN_DTYPE)
     spans['offset'], spans['length'], spans['flags'] = offsets, lengths, 1
     spans['expect_masked'] = [f.stored[i] for f, i in recs]
-    _, status = ops.crc32c_spans(dev, staging.upload_table(spans, self.device), n)
-    status = status.cpu().numpy()          # waits for the copy as well: the staging buffer is free for the next batch
+    return staging.upload_table(spans, self.device)
+
+  def _checked(self, recs, status):
     for (f, i), st in zip(recs, status):
       if st:
         raise self._mismatch(f, i, 'payload checksum mismatch' if st == _lib.SPAN_EMISMATCH else 'span status %d' % st)
 
+  def _verify_device(self, recs, uploaded):
+    _, status = ops.crc32c_spans(uploaded[0], self._span_table(recs, uploaded), len(recs))
+    self._checked(recs, status.cpu().numpy())   # waits for the copy as well: the staging buffer is free for the next batch
+
+  def _host_row(self, f: RecordFile, i: int, base: int):
+    """proto_row of one record, with the KD row when the dataset returns logits; errors in the batch's wrapper"""
+    try:
+      row, logit = proto_row(_buffer(f.payload(i)), base)
+      return row, _kd_label(row['label'], logit, self.num_classes) if self.return_logits else None
+    except ValueError as err:
+      raise ValueError('%s: record at byte %d: %s' % (f.name, int(f.starts[i]), err))
+
+  def assemble(self, recs, rows: np.ndarray, uploaded=None, label_rows: Optional[torch.Tensor] = None) -> Batch:
+    """(records, their asm_example_row rows) -> Batch, what the host loop of parse='host' makes.  ``rows``: ROW_DTYPE [B],
+    offsets counted from ``uploaded``'s slots (from 0 without it).  A row with cls != 0 is replaced by the host's parse of
+    that record, which raises for it what it raises today.  ``label_rows`` (return_logits): the float32 [B, 2 * num_classes]
+    device tensor asm_example_label_rows wrote for these rows; the rows the host parsed are patched in with one copy.
+    Without it the rows are taken as made by proto_row (their logits do not lie at logit_offset) and parsed here."""
+    slots = uploaded[1] if uploaded is not None else np.zeros(len(recs), np.int64)
+    rows = rows.copy()
+    encoded, names, origins, patched, kd = [], [], [], [], []
+    for k, (f, i) in enumerate(recs):
+      base = int(slots[k])
+      if rows[k]['cls'] != 0 or (self.return_logits and label_rows is None):
+        rows[k], row = self._host_row(f, i, base)
+        patched.append(k)
+        kd.append(row)
+      elif self.return_logits and rows[k]['logit_count'] != self.num_classes:
+        raise ValueError('%s: record at byte %d: image/logit holds %d values, num_classes is %d' % (
+            f.name, int(f.starts[i]), rows[k]['logit_count'], self.num_classes))
+      payload = f.payload(i)
+      b, nb = int(rows[k]['enc_offset']) - base, int(rows[k]['name_offset']) - base
+      encoded.append(payload[b:b + int(rows[k]['enc_length'])])
+      names.append(payload[nb:nb + int(rows[k]['name_length'])].tobytes())
+      origins.append((f.name, int(f.starts[i])))
+    if not self.return_logits:
+      labels = torch.from_numpy(rows['label'].astype(np.int32))
+    elif label_rows is None:
+      labels = torch.from_numpy(np.stack(kd).astype(np.float32))
+    else:
+      labels = label_rows
+      if patched:
+        labels[torch.as_tensor(patched, device=labels.device)] = torch.from_numpy(np.stack(kd)).to(labels.device)
+    payloads = None
+    if self.keep_payloads:
+      payloads = (uploaded[0], np.stack([rows['enc_offset'], rows['enc_length']], axis=1).astype(np.int64))
+    return Batch(encoded, labels, names, origins, payloads)
+
+  def _batch_device(self, recs) -> Batch:
+    """parse='device': the checksum launch (verify='device'), the parse launch and, with return_logits, the label-row launch
+    are enqueued behind the upload; status words and rows come back in one copy behind one wait"""
+    n = len(recs)
+    uploaded = self._upload(recs)
+    dev = uploaded[0]
+    if self.verify == 'host':
+      self._verify_host(recs)
+    spans = self._span_table(recs, uploaded)
+    back = [ops.crc32c_spans(dev, spans, n)[1].view(torch.uint8)] if self.verify == 'device' else []
+    rows_dev = ops.example_parse(dev, spans, n)
+    back.append(rows_dev)
+    label_rows = ops.example_label_rows(dev, rows_dev, n, self.num_classes)[0] if self.return_logits else None
+    host = torch.cat(back).cpu().numpy()          # waits for the copy as well: the staging buffer is free for the next batch
+    if self.verify == 'device':
+      self._checked(recs, host[:4 * n].view(np.int32))
+    return self.assemble(recs, host[host.size - ROW_DTYPE.itemsize * n:].view(ROW_DTYPE), uploaded, label_rows)
+
   def _batch(self, recs) -> Batch:
+    if self.parse == 'device':
+      return self._batch_device(recs)
     uploaded = self._upload(recs) if self.verify == 'device' or self.keep_payloads else None
     if self.verify == 'device':
       self._verify_device(recs, uploaded)

@@ -37,7 +37,7 @@ extern "C" {
 
 /* Changes when an existing struct or signature changes.  Additions keep it: asm_jpeg_decode_progressive,
  * asm_jpeg_scan, asm_jpeg_decode_parallel, asm_crc32c_spans, asm_span_desc, asm_jpeg_parse and asm_jpeg_parse_fill came in
- * under 11. */
+ * under 11, and so did asm_example_parse, asm_example_label_rows and asm_example_row: they only add entry points. */
 #define ASM_ABI_VERSION 11
 
 const char* asm_last_error(void);
@@ -852,6 +852,49 @@ int asm_jpeg_parse_fill(const uint8_t* buf, int64_t buf_bytes, const asm_span_de
                         int n_intervals, int64_t total_segments, int segment_bytes, asm_jpeg_desc* descs,
                         asm_jpeg_tables* tables_out, asm_jpeg_interval* intervals, int32_t* segment_first, int32_t* status,
                         void* stream);
+
+/* tf.train.Example protos on the device (data_util.parse_example_proto, utils/data_util.py:173-208): the payloads of a batch
+ * of records that already lie in device memory, read where they lie (assembled_cnn_amd/records.py, parse='device'; DESIGN.md
+ * 1.3 has the rules).
+ *
+ * asm_example_parse: one workgroup per span walks the serialised Example buf[offset, offset + length) -- varints, fields,
+ * Example / Features / map entry / Feature / list, every feature of every name validated -- and writes one row per span.
+ *   buf, buf_bytes, spans, n   as for asm_crc32c_spans; an asm_span_desc's flags and expect_masked are ignored
+ *   rows   n asm_example_row, written by the call.  cls == 0 only where records._proto accepts the payload; the other fields
+ *          then hold what it returns: the image/encoded and image/filename bytes and the packed little-endian image/logit
+ *          values as positions in buf, the label (low 32 bits of the varint; -1 when absent) and the number of bounding
+ *          boxes.  An absent feature has length / count 0 and the span's own offset.  Otherwise cls is a bit set of
+ *          ASM_EXAMPLE_P* -- diagnostics only: the host parses such a record itself -- and the other fields are zero.
+ *          ASM_EXAMPLE_PFORM stands for legal forms that TensorFlow does not write and the walk leaves to the host: a name
+ *          with a byte >= 0x80, a map entry with two keys or two values, a Feature with two kinds, one of the names that are
+ *          read occurring twice, image/logit in anything but no part or one packed part, a span of 2^31 bytes or more.
+ *   The walk reads through a window of ASM_EXAMPLE_WINDOW bytes; blobs are skipped by their length and never loaded.
+ * asm_example_label_rows: one workgroup per row writes the label row of knowledge distillation, records._kd_label:
+ *   out     float32 [n][ld], ld >= 2 * num_classes.  For a row with cls == 0 and logit_count == num_classes the columns
+ *           [0, num_classes) get one_hot of the label -- all zero for a label outside the range -- and the next num_classes
+ *           columns the logit values bit for bit; status 0.  The other columns of such a row, and every other row, are left
+ *           as they are.
+ *   status  int32 [n], written by the call: 0; ASM_EXAMPLE_LSKIP for a row of another class or another logit count;
+ *           ASM_EXAMPLE_LRANGE for logit bytes that do not lie inside buf, which is checked without overflow.
+ * Both: every read is bounded by the span / the logit bytes; n == 0 returns ASM_OK without a launch; null pointers, n < 0,
+ * num_classes < 1, ld < 2 * num_classes and buf_bytes outside 0 .. 2^40 - 1 are ASM_EINVAL, before any launch. */
+#define ASM_EXAMPLE_WINDOW 1024   /* bytes of the walk's window                                                          */
+#define ASM_EXAMPLE_PSPAN 1       /* the span does not lie inside buf: nothing was read                                  */
+#define ASM_EXAMPLE_PMALFORMED 2  /* a wire-format error                                                                  */
+#define ASM_EXAMPLE_PSCHEMA 4     /* a wrong kind, a wrong value count, bounding-box lists of different lengths          */
+#define ASM_EXAMPLE_PFORM 8       /* legal, but a form the device leaves to the host                                      */
+#define ASM_EXAMPLE_LSKIP 1       /* not a class-0 row with num_classes logits: the row is left as it is                 */
+#define ASM_EXAMPLE_LRANGE 2      /* the logit bytes do not lie inside buf: the row is left as it is                     */
+typedef struct asm_example_row {
+  int32_t cls, label;                      /* 0 or a bit set of ASM_EXAMPLE_P*; image/class/label                  */
+  int64_t enc_offset, name_offset, logit_offset;   /* positions in buf                                            */
+  int32_t enc_length, name_length;         /* bytes                                                                */
+  int32_t logit_count, n_boxes;            /* float values; boxes                                                  */
+} asm_example_row;                         /* 48 bytes */
+int asm_example_parse(const uint8_t* buf, int64_t buf_bytes, const asm_span_desc* spans, int n, asm_example_row* rows,
+                      void* stream);
+int asm_example_label_rows(const uint8_t* buf, int64_t buf_bytes, const asm_example_row* rows, int n, int num_classes,
+                           float* out, int ld, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Flag surface and topology planner. asm_model_cfg carries the flags of nets/hparams_config.py:30-292 (+

@@ -312,6 +312,77 @@ def records_leg(n=256):
   ratio = max(ms_c) / min(ms_p)
   print('records: bar %s, slowest kernel run %.4f ms / fastest parallel-entropy run %.4f ms = %.4f (allowed 0.1)'
         % ('met' if ratio <= 0.1 else 'MISSED', max(ms_c), min(ms_p), ratio))
+  example_parse_part(files, payloads, par)
+
+
+def example_parse_part(files, plain, par, num_classes=1001):
+  """The Examples of a KD dataset (the files of records_leg with filename, label, four boxes and num_classes teacher logits)
+  parsed on the device: asm_example_parse alone and asm_example_label_rows alone (device events around 20 calls),
+  alternating with the segment-parallel entropy stage `par` of the same files, three runs each; then the whole RecordDataset
+  batch with parse='host' against parse='device', each with and without return_logits, alternating, three runs each --
+  and the same for `plain`, records_leg's three-feature records of the same files (int labels only: they hold no logits).
+  Ends with the bar: the two launches together take at most a tenth of the fastest parallel-entropy run."""
+  import tempfile
+  from assembled_cnn_amd import records
+  n = len(files)
+  r = np.random.default_rng(2)
+  box = lambda i: r.random(1 + i % 3).astype(np.float32)       # one to three boxes a record
+  payloads = [records.encode_example({'image/encoded': [f], 'image/filename': [b'n%08d.JPEG' % i],
+                                      'image/class/label': np.array([i % 1000 + 1]),
+                                      'image/object/bbox/ymin': box(i), 'image/object/bbox/xmin': box(i),
+                                      'image/object/bbox/ymax': box(i), 'image/object/bbox/xmax': box(i),
+                                      'image/logit': r.normal(size=num_classes).astype(np.float32)}) for i, f in enumerate(files)]
+  total = sum(map(len, payloads))
+  print('examples: %d KD records (%d logits each), mean payload %.1f KB, %.2f MB in all' % (n, num_classes, total / n / 1e3, total / 1e6))
+  lengths = np.array([len(p) for p in payloads], dtype=np.int64)
+  offsets, nbytes = staging.slot_layout(lengths)
+  host = np.zeros(nbytes, np.uint8)
+  spans = np.zeros(n, dtype=records.SPAN_DTYPE)
+  for p, o in zip(payloads, offsets):
+    host[int(o):int(o) + len(p)] = np.frombuffer(p, np.uint8)
+  spans['offset'], spans['length'] = offsets, lengths
+  bd, sd = torch.from_numpy(host).cuda(), staging.upload_table(spans, 'cuda')
+  rows_dev = ops.example_parse(bd, sd, n)
+  rows = rows_dev.cpu().numpy().view(records.ROW_DTYPE)
+  assert not rows['cls'].any() and (rows['logit_count'] == num_classes).all(), 'a record of the batch is not class 0'
+  out, status = ops.example_label_rows(bd, rows_dev, n, num_classes)
+  want = np.stack([records.parse_record_sup(p, True, num_classes)['label'] for p in payloads])
+  assert not status.any() and out.cpu().numpy().tobytes() == want.tobytes(), 'label rows differ from parse_record_sup'
+  ms_a, ms_b, ms_p = [], [], []
+  for _ in range(3):       # alternating
+    ms_a.append(ev(lambda: ops.example_parse(bd, sd, n), iters=20))
+    ms_b.append(ev(lambda: ops.example_label_rows(bd, rows_dev, n, num_classes, out=out), iters=20))
+    ms_p.append(ev(par, iters=3))
+  print('asm_example_parse alone, ms per batch       : %s' % ' '.join('%8.4f' % m for m in ms_a))
+  print('asm_example_label_rows alone, ms per batch  : %s' % ' '.join('%8.4f' % m for m in ms_b))
+  print('parallel entropy stage, ms per batch        : %s' % ' '.join('%8.4f' % m for m in ms_p))
+  for what, recs, logit_modes in (('KD records', payloads, (False, True)), ('three-feature records', plain, (False,))):
+    with tempfile.TemporaryDirectory() as d:
+      for s in range(4):
+        records.write_records(os.path.join(d, 'train-%05d-of-00004' % s), recs[s::4])
+      names = records.get_filenames(True, d)
+      t0 = time.time(); [records.RecordFile(f) for f in names]; ms_walk = 1e3 * (time.time() - t0)
+      print('%s: walk of the four shards alone (RecordFile): %8.2f ms' % (what, ms_walk))
+      for verify in ('none', 'device'):
+        for logits in logit_modes:
+          ms, labels = {'host': [], 'device': []}, {}
+          its = {parse: iter(records.RecordDataset(names, False, n, 1, cycle_length=4, num_epochs=4, verify=verify, device='cuda',
+                                                   return_logits=logits, num_classes=num_classes, parse=parse)) for parse in ms}
+          for parse in ms:
+            next(its[parse])   # the first batch allocates and pins the staging buffer
+          for _ in range(3):   # alternating
+            for parse in ms:
+              torch.cuda.synchronize()
+              t0 = time.time(); b = next(its[parse]); torch.cuda.synchronize(); ms[parse].append(1e3 * (time.time() - t0))
+              labels[parse] = b.labels.cpu()
+          assert torch.equal(labels['host'], labels['device']), 'the two parse modes give different labels'
+          for parse in ('host', 'device'):
+            print('%s: RecordDataset batch of %d, verify=%-6s return_logits=%-5s parse=%-6s: %s ms per batch'
+                  % (what, n, verify, logits, parse, ' '.join('%8.2f' % m for m in ms[parse])))
+  both = max(a + b for a, b in zip(ms_a, ms_b))
+  ratio = both / min(ms_p)
+  print('examples: bar %s, slowest parse + label rows %.4f ms / fastest parallel-entropy run %.4f ms = %.4f (allowed 0.1)'
+        % ('met' if ratio <= 0.1 else 'MISSED', both, min(ms_p), ratio))
 
 
 def jpeg_device_parse_leg(n=256):
