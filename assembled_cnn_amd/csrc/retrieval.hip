@@ -768,6 +768,19 @@ extern "C" int asm_debug_retrieval_topk_wide_counted(const void* queries, int ld
                              workspace, workspace_bytes, stream, counters3);
 }
 
+// test-only (asm_hip_debug.h): the split plan the two launchers above compute, through the same two functions; nothing is launched
+extern "C" int asm_debug_retrieval_plan(int Q, int N, int K, int wide, int32_t plan[4]) {
+  ASM_REQUIRE(plan && Q > 0 && N > 0 && K > 0, "retrieval_plan: bad arguments (Q=%d N=%d K=%d)", Q, N, K);
+  if (K > (wide ? WIDE_MAX : TOPK_MAX))
+    ASM_FAIL(ASM_ENOTSUP, "retrieval_plan: K = %d is above the cap of %d", K, wide ? WIDE_MAX : TOPK_MAX);
+  int tps = 0;
+  plan[0] = wide ? retrieval_splits(Q, N, &tps, WIDE_TARGET) : retrieval_splits(Q, N, &tps);
+  plan[1] = tps;
+  plan[2] = cdiv(N, BN);
+  plan[3] = wide ? wide_capacity(K) : 0;
+  return ASM_OK;
+}
+
 extern "C" int asm_recall_accumulate(const int32_t* top_idx, int Q, int K, const int32_t* query_labels,
                                      const int32_t* index_labels, int N, int query_base, const int32_t* k_list, int nk,
                                      int32_t* hits, void* stream) {

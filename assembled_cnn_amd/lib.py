@@ -332,6 +332,7 @@ DEBUG_SIGNATURES = {
     'asm_conv2d_wgrad_plan': (_I, [_D, C.POINTER(C.c_int32 * 6)]),
     'asm_debug_last_conv_kernel': (_I, []),
     'asm_debug_retrieval_topk_wide_counted': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P, _P]),
+    'asm_debug_retrieval_plan': (_I, [_I, _I, _I, _I, C.POINTER(C.c_int32 * 4)]),
 }
 
 _lib = None

@@ -547,6 +547,11 @@ int asm_embed_sqnorm(const void* x, int N, int D, int ld, float* sq, void* strea
  * with N < K the unused slots hold -inf / -1.  K is max(k_list) + 1 (:110).  workspace: asm_retrieval_topk_workspace_bytes(Q, N, K)
  * bytes (positive, non-decreasing in each argument; 0 for a non-positive one) for the lists of the index splits the kernel cuts the
  * walk into; the split count depends on (Q, N) alone, so the result is the same on every run.
+ * Non-finite similarities (an embedding that holds +-inf or NaN; the same for asm_retrieval_topk_wide): an index row whose
+ * similarity with a query is NaN is never selected for that query -- the row behaves as if it were absent, and if fewer than K
+ * rows remain the tail holds unused slots; a similarity of -inf is an ordinary value that ranks after every finite one and
+ * before the unused slots (value -inf with its real index, lower index first among several).  The other rows and queries of
+ * the call are unaffected.
  * Errors, all raised before anything is launched: a null pointer, a non-positive size, ld < D or ld % 8 != 0, index_base < 0 or
  * index_base + N beyond int32, a short workspace -> ASM_EINVAL; similarity other than 0 / 1 (the reference's
  * NotImplementedError, :107-108) and K > 64 (asm_last_error names the cap) -> ASM_ENOTSUP. */

@@ -1,9 +1,11 @@
 """Guard-band plumbing and element-wise bounds shared by the GPU edge-shape modules (tests/test_gpu_rows_edges.py,
-tests/test_gpu_pool_edges.py, tests/test_gpu_bn_edges.py, tests/test_gpu_step_edges.py, tests/test_gpu_conv_exact.py).  A plain module, not a conftest: the test modules import what they use, the autouse fixture
+tests/test_gpu_pool_edges.py, tests/test_gpu_bn_edges.py, tests/test_gpu_step_edges.py, tests/test_gpu_conv_exact.py,
+tests/test_gpu_retrieval_edges.py).  A plain module, not a conftest: the test modules import what they use, the autouse fixture
 ``_release_inputs`` included.
 
 * ``Out``: an output between two 4 KiB flanks of the byte 0xA5 which must survive the call; the output itself starts as 0xA5,
-  so an element the kernel skips shows.  ``Out.np()`` rejects NaN and huge values.
+  so an element the kernel skips shows.  ``Out.np()`` rejects NaN and huge values; ``Out.np_inf()`` admits the infinities
+  of a top-K output (-inf in an unused slot) and rejects an element that still holds the fill.
 * ``In``: an input between two 4 KiB flanks of NaN (or a huge value where the kernel would drop a NaN silently): a read one
   row or one vector outside the tensor shows up in an output, where ``Out.np()`` rejects it.
 * ``close_*`` / ``exact``: element-wise assertions; each prints the worst error of its case next to its bound under ``-s``.
@@ -62,6 +64,24 @@ class Out(object):
       return a.numpy().astype(np.int64)
     a = a.double().numpy()
     assert np.isfinite(a).all() and (np.abs(a) < 1e29).all() if a.size else True, 'NaN or huge value in an output'
+    return a
+
+  def assert_written(self):
+    """no 4-byte element still holds the fill: 0xA5A5A5A5 is the float -2.9e-16 / the int32 -1515870811"""
+    assert self.t.element_size() == 4
+    words = self.t.contiguous().view(torch.uint8).view(-1, self.t.element_size())
+    assert not bool((words == PATTERN).all(1).any()), 'an output element was never written'
+
+  def np_inf(self):
+    """``np`` for an output that legitimately holds infinities (the -inf of an unused top-K slot): flanks intact, every
+    element written, no NaN and no huge finite value -> float64 (int64 for integer outputs)"""
+    self.check_flanks()
+    self.assert_written()
+    a = self.t.detach().cpu()
+    if a.dtype in (torch.int32, torch.uint8):
+      return a.numpy().astype(np.int64)
+    a = a.double().numpy()
+    assert not np.isnan(a).any() and (np.abs(a[np.isfinite(a)]) < 1e29).all(), 'NaN or huge value in an output'
     return a
 
 
