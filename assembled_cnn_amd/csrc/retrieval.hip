@@ -7,6 +7,11 @@
 //                          query row; it moves O((Q + N) D) bytes where the reference moves O(Q N)
 //                          retrieval_topk_wide_kernel (64 < K <= 1024): the same GEMM and epilogue (retrieval_walk), whose
 //                          survivors go unsorted into a per-query candidate buffer that a radix select cuts back to K
+//                          topk_merge_kernel / topk_merge_wide_kernel: the lists or buffers of a query's splits -> its K best
+//
+// Shared by the two selections: the walk (retrieval_walk, tile_row), the sorted insertion (list_insert: lists in LDS, the merge's
+// output row), the radix select (radix_select: one wave over registers in WideSel::compact, a workgroup over memory in
+// topk_merge_wide_kernel) and, on the host, the plan of a call (RetrievalPlan), the workspace bound and the launcher.
 //
 // Tiling.  A workgroup of four waves owns 128 query rows (wave w: rows 32 w .. 32 w + 31) and walks a contiguous range of
 // 128-row index tiles in ascending order.  Per 64-channel step both tiles go global -> registers -> LDS (the next step's loads
@@ -19,7 +24,7 @@
 // Order.  A list is ordered by (value descending, index ascending) and an entry is inserted only where it is strictly better
 // in that order, which is tf.nn.top_k's "of equal values the lower index first" whatever order the candidates arrive in.
 //
-// Splits.  The index range is cut into S contiguous runs of tiles (retrieval_splits: a pure function of Q, N) so that a small
+// Splits.  The index range is cut into S contiguous runs of tiles (RetrievalPlan: a pure function of the sizes) so that a small
 // Q still fills the chip; every (query tile, split) writes its list to the workspace and topk_merge_kernel combines the S
 // lists of a row in the same order.  Nothing depends on timing: the result is identical from run to run.
 //
@@ -69,9 +74,12 @@ __device__ __forceinline__ u32x4 load_chunk(const bf16_t* base, int row, int nro
   return v;
 }
 
+// accumulator element acc[a][i] of a lane in half lhi of its wave -> index row of the tile (the 32 x 32 x 16 MFMA's layout)
+__device__ __forceinline__ int tile_row(int a, int i, int lhi) { return a * 32 + (i & 3) + 8 * (i >> 2) + 4 * lhi; }
+
 // The walk both selection kernels share: the 128 x 128 x 64 GEMM over this workgroup's run of index tiles and the scale
 // epilogue.  At the end of every index tile a lane holds the 64 similarities of its query in acc (acc[a][i]: index row
-// nb + a*32 + (i&3) + 8*(i>>2) + 4*lhi) and the bit mask `cand` of those that reach sel.threshold(row); sel.insert takes them.
+// nb + tile_row(a, i, lhi)) and the bit mask `cand` (bit a*16 + i) of those that reach sel.threshold(row); sel.insert takes them.
 // One instantiation per selection scheme, so every similarity is the same bits whichever scheme looks at it.
 template <class Sel>
 __device__ __forceinline__ void retrieval_walk(const TopkArgs& p, unsigned char* smem, Sel& sel) {
@@ -153,7 +161,7 @@ __device__ __forceinline__ void retrieval_walk(const TopkArgs& p, unsigned char*
       ++kc;
       continue;
     }
-    // ---- epilogue of one index tile: acc[a][i] is (query l31, index row a*32 + (i&3) + 8*(i>>2) + 4*lhi) ----
+    // ---- epilogue of one index tile: acc[a][i] is (query l31, index row tile_row(a, i, lhi)) ----
     const int nb = tile * BN;
     const float thr = sel.threshold(row);
     unsigned long long cand = 0ull;
@@ -161,7 +169,7 @@ __device__ __forceinline__ void retrieval_walk(const TopkArgs& p, unsigned char*
     for (int a = 0; a < 4; ++a)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int nl = a * 32 + (i & 3) + 8 * (i >> 2) + 4 * lhi;
+        const int nl = tile_row(a, i, lhi);
         const float xv = xn[nl];
         const float sv = p.sim == 0 ? (acc[a][i] * qn) * xv : -((qn + xv) - 2.0f * acc[a][i]);
         acc[a][i] = sv;
@@ -187,6 +195,28 @@ __device__ __forceinline__ float pick(const f32x16 (&acc)[4], int b) {
   return sv;
 }
 
+// (sv, n) into the sorted list of K entries whose entry j is v[j * STRIDE], ix[j * STRIDE] and whose last entry is (thr, thi):
+// false, and nothing done, unless it is strictly better than that one; else the entries it beats move down one place, the last
+// one drops out, and (thr, thi) is the new last entry.  Inlined: the list kernel's list is in LDS, the merge's in memory.
+template <int STRIDE>
+__device__ __forceinline__ bool list_insert(float* v, int* ix, int K, float sv, int n, float& thr, int& thi) {
+  if (!better(sv, n, thr, thi)) return false;
+  int j = K - 1;
+  while (j > 0) {
+    const float pv = v[(j - 1) * STRIDE];
+    const int pi = ix[(j - 1) * STRIDE];
+    if (!better(sv, n, pv, pi)) break;
+    v[j * STRIDE] = pv;
+    ix[j * STRIDE] = pi;
+    --j;
+  }
+  v[j * STRIDE] = sv;
+  ix[j * STRIDE] = n;
+  thr = v[(K - 1) * STRIDE];
+  thi = ix[(K - 1) * STRIDE];
+  return true;
+}
+
 // K <= 64: a sorted list per query, [K][BM] in LDS, whose K-th entry is the threshold
 struct ListSel {
   float* lv;
@@ -204,23 +234,7 @@ struct ListSel {
         while (left != 0ull) {                 // ascending index order; rare once the list is warm
           const int b = __builtin_ctzll(left);
           left &= left - 1ull;
-          const float sv = pick(acc, b);
-          const int n = nb + (b >> 4) * 32 + (b & 3) + 8 * ((b & 15) >> 2) + 4 * lhi;
-          if (better(sv, n, thr, thi)) {
-            int j = K - 1;
-            while (j > 0) {
-              const float pv = lv[(j - 1) * BM + row];
-              const int pi = li[(j - 1) * BM + row];
-              if (!better(sv, n, pv, pi)) break;
-              lv[j * BM + row] = pv;
-              li[j * BM + row] = pi;
-              --j;
-            }
-            lv[j * BM + row] = sv;
-            li[j * BM + row] = n;
-            thr = lv[(K - 1) * BM + row];
-            thi = li[(K - 1) * BM + row];
-          }
+          list_insert<BM>(lv + row, li + row, K, pick(acc, b), nb + tile_row(b >> 4, b & 15, lhi), thr, thi);
         }
       }
       __syncthreads();
@@ -321,6 +335,57 @@ __device__ __forceinline__ void select_digit(const unsigned* hist, int need, int
   binc = __shfl(fb, src);
 }
 
+// Who runs a radix select together: how these threads clear the 256 counts they share, the barrier between two phases, and
+// how the digit select_digit picks reaches every one of them (pick ends behind a barrier: hist may be cleared again).
+struct WaveScope {                            // one wave, hist in LDS
+  unsigned* hist; int lane;
+  __device__ __forceinline__ void clear() const {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) hist[lane + 64 * j] = 0u;
+  }
+  __device__ __forceinline__ void sync() const { wave_sync(); }
+  __device__ __forceinline__ void pick(int need, int& d, int& above, int& binc) const {
+    select_digit(hist, need, lane, d, above, binc);       // every lane gets the result
+    wave_sync();
+  }
+};
+struct GroupScope {                           // a workgroup of 256 threads, hist and the three picked numbers in LDS
+  unsigned* hist; int* picked; int tid;
+  __device__ __forceinline__ void clear() const { hist[tid] = 0u; }
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
+  __device__ __forceinline__ void pick(int need, int& d, int& above, int& binc) const {
+    if (tid < 64) {
+      select_digit(hist, need, tid, d, above, binc);
+      if (tid == 0) { picked[0] = d; picked[1] = above; picked[2] = binc; }
+    }
+    __syncthreads();
+    d = picked[0]; above = picked[1]; binc = picked[2];
+  }
+};
+
+// The radix select over 64-bit keys, 8-bit digits from the top: the prefix (low bits zero) at or above which the need best keys
+// lie, 1 <= need <= number of keys.  each_key(add) calls add(k) for every key of this thread that takes part, once per pass.
+// It stops as soon as a whole digit bin is taken: every key >= prefix is then one of the need best.
+template <class Scope, class EachKey>
+__device__ __forceinline__ u64 radix_select(const Scope& sc, int need, EachKey each_key) {
+  u64 prefix = 0ull;
+#pragma unroll 1
+  for (int shift = 56;; shift -= 8) {
+    sc.clear();
+    sc.sync();
+    const u64 mask = shift == 56 ? 0ull : ~0ull << (shift + 8);
+    each_key([&](u64 k) {
+      if ((k & mask) == prefix) atomicAdd(&sc.hist[(unsigned)(k >> shift) & 255u], 1u);
+    });
+    sc.sync();
+    int d, above, binc;
+    sc.pick(need, d, above, binc);
+    prefix |= (u64)d << shift;
+    need -= above;
+    if (need == binc || shift == 0) return prefix;
+  }
+}
+
 // K <= 1024: per (query, run) an unsorted buffer of B candidates in the workspace, the count and the threshold in registers
 struct WideSel {
   float* wv;            // this wave's first query, this run: row r of the wave is at r * rstride
@@ -350,25 +415,11 @@ struct WideSel {
       key[c] = 0ull;
       if (c * 64 < n && e < n) key[c] = make_key(v[e], ix[e]);
     }
-    u64 prefix = 0ull;
-    int need = K;
-#pragma unroll 1
-    for (int shift = 56;; shift -= 8) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) hist[lane + 64 * j] = 0u;
-      wave_sync();
-      const u64 mask = shift == 56 ? 0ull : ~0ull << (shift + 8);
+    const u64 prefix = radix_select(WaveScope{hist, lane}, K, [&](auto add) {   // the n > K used slots; an unused one is no key
 #pragma unroll
       for (int c = 0; c < WIDE_NCH; ++c)
-        if (c * 64 < n && key[c] != 0ull && (key[c] & mask) == prefix) atomicAdd(&hist[(unsigned)(key[c] >> shift) & 255u], 1u);
-      wave_sync();
-      int d, above, binc;
-      select_digit(hist, need, lane, d, above, binc);
-      wave_sync();
-      prefix |= (u64)d << shift;
-      need -= above;
-      if (need == binc || shift == 0) break;  // the whole bin is taken: every key >= prefix is one of the K best
-    }
+        if (c * 64 < n && key[c] != 0ull) add(key[c]);
+    });
     int out = 0;
 #pragma unroll
     for (int c = 0; c < WIDE_NCH; ++c)
@@ -397,8 +448,8 @@ struct WideSel {
       const int b = __builtin_ctzll(cand);
       cand &= cand - 1ull;
       const float sv = pick(acc, b);
-      const int n = nb + (b >> 4) * 32 + (b & 3) + 8 * ((b & 15) >> 2) + 4 * lhi;
-      if (pos < B) {                          // always: a tile adds at most BN to a count of at most B - BN
+      const int n = nb + tile_row(b >> 4, b & 15, lhi);
+      if (pos < B) {                         // always: a tile adds at most BN to a count of at most B - BN
         v[pos] = sv;
         ix[pos] = n + index_base;
       }
@@ -463,38 +514,16 @@ __global__ __launch_bounds__(256) void topk_merge_wide_kernel(const float* __res
                                                               int* __restrict__ out_idx) {
   __shared__ unsigned hist[256];
   __shared__ u64 keys[WIDE_MAX];
-  __shared__ int pick_d, pick_above, pick_binc, nsel;
+  __shared__ int picked[3], nsel;
   const int tid = threadIdx.x;
   const size_t r = blockIdx.x;
   const float* iv = in_val + r * P * stride;
   const int* ii = in_idx + r * P * stride;
-  u64 prefix = 0ull;
-  int need = K;                               // P * K >= K slots, unused ones (key 0) counted: the K-th may be an unused one
-#pragma unroll 1
-  for (int shift = 56;; shift -= 8) {
-    hist[tid] = 0u;
-    __syncthreads();
-    const u64 mask = shift == 56 ? 0ull : ~0ull << (shift + 8);
+  // all P * K >= K slots, unused ones (key 0) counted: the K-th may be an unused one
+  const u64 prefix = radix_select(GroupScope{hist, picked, tid}, K, [&](auto add) {
     for (int l = 0; l < P; ++l)
-      for (int j = tid; j < K; j += 256) {
-        const u64 k = make_key(iv[l * stride + j], ii[l * stride + j]);
-        if ((k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
-      }
-    __syncthreads();
-    if (tid < 64) {
-      int d, above, binc;
-      select_digit(hist, need, tid, d, above, binc);
-      if (tid == 0) {
-        pick_d = d;
-        pick_above = above;
-        pick_binc = binc;
-      }
-    }
-    __syncthreads();
-    prefix |= (u64)pick_d << shift;
-    need -= pick_above;
-    if (need == pick_binc || shift == 0) break;
-  }
+      for (int j = tid; j < K; j += 256) add(make_key(iv[l * stride + j], ii[l * stride + j]));
+  });
   int n2 = 2;
   while (n2 < K) n2 <<= 1;
   for (int j = tid; j < n2; j += 256) keys[j] = 0ull;
@@ -548,19 +577,8 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
     const float* iv = in_val + ((size_t)r * P + l) * K;
     const int* ii = in_idx + ((size_t)r * P + l) * K;
     for (int e = 0; e < K; ++e) {
-      const float sv = iv[e];
       const int n = ii[e];
-      if (n < 0 || !better(sv, n, thr, thi)) break;     // the list is sorted: what follows is no better
-      int j = K - 1;
-      while (j > 0 && better(sv, n, ov[j - 1], oi[j - 1])) {
-        ov[j] = ov[j - 1];
-        oi[j] = oi[j - 1];
-        --j;
-      }
-      ov[j] = sv;
-      oi[j] = n;
-      thr = ov[K - 1];
-      thi = oi[K - 1];
+      if (n < 0 || !list_insert<1>(ov, oi, K, iv[e], n, thr, thi)) break;     // the list is sorted: what follows is no better
     }
   }
   for (int j = 0; j < K; ++j)
@@ -609,26 +627,50 @@ __global__ __launch_bounds__(256) void recall_accumulate_kernel(const int* __res
   }
 }
 
-inline int retrieval_splits(int Q, int N, int* tiles_per_split, int target = SPLIT_TARGET) {
-  const int qt = cdiv(Q, BM), nt = cdiv(N, BN);
-  int S = cdiv(target, qt);
+// Everything the two selections decide differently on the host, and the split plan of one call: a pure function of
+// (Q, N, K, wide).  For sizes no call may have (one not positive, K above the cap) only name and cap are filled, to refuse with.
+struct RetrievalPlan {
+  const char* name;     // the entry point's, in messages
+  int cap, target;      // largest K; workgroups wanted
+  int B;                // wide selection: capacity of a (query, split) candidate buffer; else 0
+  int lds;              // dynamic LDS of the selection kernel: tiles, |x|^2 row and the lists / the four waves' digit counts
+  int entries;          // (value, index) pairs per (query, split) in the workspace: K or B
+  int S, tiles_per_split, n_tiles;
+};
+inline RetrievalPlan retrieval_plan(int Q, int N, int K, bool wide) {
+  RetrievalPlan p = wide ? RetrievalPlan{"retrieval_topk_wide", WIDE_MAX, WIDE_TARGET}
+                         : RetrievalPlan{"retrieval_topk", TOPK_MAX, SPLIT_TARGET};      // the other members: 0
+  if (Q <= 0 || N <= 0 || K <= 0 || K > p.cap) return p;
+  p.B = wide ? wide_capacity(K) : 0;
+  p.entries = wide ? p.B : K;
+  p.lds = (BM + BN) * PITCH + BN * 4 + (wide ? 4 * 256 * 4 : K * BM * 8);
+  p.n_tiles = cdiv(N, BN);
+  int S = cdiv(p.target, cdiv(Q, BM));         // the splits of one query tile that make `target` workgroups
   if (S > SPLIT_MAX) S = SPLIT_MAX;
-  if (S > nt) S = nt;
-  const int tps = cdiv(nt, S);
-  *tiles_per_split = tps;
-  return cdiv(nt, tps);                        // no empty split
+  if (S > p.n_tiles) S = p.n_tiles;
+  p.tiles_per_split = cdiv(p.n_tiles, S);
+  p.S = cdiv(p.n_tiles, p.tiles_per_split);    // no empty split
+  return p;
+}
+
+// An upper bound of the plan's Q * S * entries * 8 that grows with each of Q, N, entries, so that a workspace sized for the
+// largest call holds every smaller one; the plan's own product does not, S itself shrinks as Q grows
+inline size_t retrieval_workspace_bound(int Q, int N, size_t target, size_t entries) {
+  const size_t qt = cdivz((size_t)Q, BM), nt = cdivz((size_t)N, BN);
+  size_t lists = qt * nt;                      // S <= nt, and qt * S <= target + qt, and S <= SPLIT_MAX
+  if (lists > target + qt) lists = target + qt;
+  if (lists > SPLIT_MAX * qt) lists = SPLIT_MAX * qt;
+  return lists * BM * entries * 8;
 }
 
 }  // namespace
 
-// An upper bound of Q * S * K * 8 that grows with each of Q, N, K (S itself shrinks as Q grows)
 extern "C" size_t asm_retrieval_topk_workspace_bytes(int Q, int N, int K) {
-  if (Q <= 0 || N <= 0 || K <= 0) return 0;
-  const size_t qt = cdivz((size_t)Q, BM), nt = cdivz((size_t)N, BN);
-  size_t lists = qt * nt;                      // S <= nt, and qt * S <= SPLIT_TARGET + qt, and S <= SPLIT_MAX
-  if (lists > SPLIT_TARGET + qt) lists = SPLIT_TARGET + qt;
-  if (lists > SPLIT_MAX * qt) lists = SPLIT_MAX * qt;
-  return lists * BM * (size_t)K * 8;
+  return Q <= 0 || N <= 0 || K <= 0 ? 0 : retrieval_workspace_bound(Q, N, SPLIT_TARGET, K);
+}
+
+extern "C" size_t asm_retrieval_topk_wide_workspace_bytes(int Q, int N, int K) {
+  return Q <= 0 || N <= 0 || K <= 0 ? 0 : retrieval_workspace_bound(Q, N, WIDE_TARGET, wide_capacity(K));
 }
 
 extern "C" int asm_embed_sqnorm(const void* x, int N, int D, int ld, float* sq, void* stream) {
@@ -651,56 +693,6 @@ extern "C" int asm_topk_merge(const float* in_val, const int32_t* in_idx, int ro
   return ASM_OK;
 }
 
-extern "C" int asm_retrieval_topk(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
-                                  const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base,
-                                  float* top_val, int32_t* top_idx, void* workspace, size_t workspace_bytes, void* stream) {
-  ASM_REQUIRE(queries && index && sq_queries && sq_index && top_val && top_idx, "retrieval_topk: null operand");
-  ASM_REQUIRE(Q > 0 && N > 0 && D > 0 && K > 0, "retrieval_topk: sizes must be positive (Q=%d N=%d D=%d K=%d)", Q, N, D, K);
-  ASM_REQUIRE(ldq >= D && ldi >= D && ldq % 8 == 0 && ldi % 8 == 0,
-              "retrieval_topk: rows must be 16-byte multiples of at least D channels (ldq=%d ldi=%d D=%d)", ldq, ldi, D);
-  ASM_REQUIRE(index_base >= 0 && (long long)index_base + N <= 0x7fffffffLL, "retrieval_topk: index_base + N exceeds int32");
-  if (similarity != 0 && similarity != 1)
-    ASM_FAIL(ASM_ENOTSUP, "retrieval_topk: similarity %d (0 cosine, 1 euclidean)", similarity);
-  if (K > TOPK_MAX) ASM_FAIL(ASM_ENOTSUP, "retrieval_topk: K = %d is above the cap of %d", K, TOPK_MAX);
-  ASM_REQUIRE(workspace && workspace_bytes >= asm_retrieval_topk_workspace_bytes(Q, N, K),
-              "retrieval_topk: workspace of %zu bytes, %zu needed", workspace_bytes, asm_retrieval_topk_workspace_bytes(Q, N, K));
-  hipStream_t st = (hipStream_t)stream;
-  TopkArgs a;
-  a.q = (const bf16_t*)queries;
-  a.x = (const bf16_t*)index;
-  a.sqq = sq_queries;
-  a.sqx = sq_index;
-  a.Q = Q; a.N = N; a.D = D; a.ldq = ldq; a.ldi = ldi; a.K = K; a.sim = similarity; a.index_base = index_base;
-  a.n_tiles = cdiv(N, BN);
-  a.S = retrieval_splits(Q, N, &a.tiles_per_split);
-  a.B = 0;
-  a.counters = nullptr;
-  float* ws_val = (float*)workspace;
-  int* ws_idx = (int*)workspace + (size_t)Q * a.S * K;
-  a.out_val = a.S == 1 ? top_val : ws_val;     // one split: its list IS the result
-  a.out_idx = a.S == 1 ? top_idx : ws_idx;
-  const int lds = (BM + BN) * PITCH + BN * 4 + K * BM * 8;
-  static bool attr_done[ASM_MAX_DEVICES] = {};
-  if (hipError_t e = asm_ensure_dyn_lds(retrieval_topk_kernel, lds, attr_done); e != hipSuccess)
-    ASM_FAIL(ASM_EHIP, "retrieval_topk: dynamic LDS opt-in: %s", hipGetErrorString(e));
-  ASM_LAUNCH(retrieval_topk_kernel, dim3(cdiv(Q, BM), a.S), dim3(256), lds, st, a);
-  if (a.S > 1)
-    ASM_LAUNCH(topk_merge_kernel, dim3(cdiv(Q, 256)), dim3(256), 0, st, ws_val, ws_idx, Q, a.S, K, top_val, top_idx);
-  ASM_CHECK_LAUNCH("retrieval_topk");
-  return ASM_OK;
-}
-
-// An upper bound of Q * S * B * 8 (S from WIDE_TARGET, B = wide_capacity(K)) that grows with each of Q, N, K
-extern "C" size_t asm_retrieval_topk_wide_workspace_bytes(int Q, int N, int K) {
-  if (Q <= 0 || N <= 0 || K <= 0) return 0;
-  const size_t qt = cdivz((size_t)Q, BM), nt = cdivz((size_t)N, BN);
-  size_t lists = qt * nt;
-  if (lists > WIDE_TARGET + qt) lists = WIDE_TARGET + qt;
-  if (lists > SPLIT_MAX * qt) lists = SPLIT_MAX * qt;
-  const size_t room = K < WIDE_ROOM_MIN ? WIDE_ROOM_MIN : (K > WIDE_ROOM_MAX ? WIDE_ROOM_MAX : K);
-  return lists * BM * (((size_t)K + room + 63) / 64 * 64) * 8;
-}
-
 extern "C" int asm_topk_merge_wide(const float* in_val, const int32_t* in_idx, int rows, int P, int K, float* out_val,
                                    int32_t* out_idx, void* stream) {
   ASM_REQUIRE(in_val && in_idx && out_val && out_idx && rows > 0 && P > 0 && K > 0,
@@ -714,47 +706,55 @@ extern "C" int asm_topk_merge_wide(const float* in_val, const int32_t* in_idx, i
   return ASM_OK;
 }
 
-static int retrieval_topk_wide(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
-                               const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base, float* top_val,
-                               int32_t* top_idx, void* workspace, size_t workspace_bytes, void* stream,
-                               unsigned long long* counters) {
-  ASM_REQUIRE(queries && index && sq_queries && sq_index && top_val && top_idx, "retrieval_topk_wide: null operand");
-  ASM_REQUIRE(Q > 0 && N > 0 && D > 0 && K > 0, "retrieval_topk_wide: sizes must be positive (Q=%d N=%d D=%d K=%d)", Q, N, D, K);
+// The launcher of both selections: the checks, the plan, the selection kernel and the merge of its S lists per query
+static int retrieval_launch(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
+                            const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base, float* top_val,
+                            int32_t* top_idx, void* workspace, size_t workspace_bytes, void* stream, bool wide,
+                            unsigned long long* counters) {
+  const RetrievalPlan pl = retrieval_plan(Q, N, K, wide);
+  ASM_REQUIRE(queries && index && sq_queries && sq_index && top_val && top_idx, "%s: null operand", pl.name);
+  ASM_REQUIRE(Q > 0 && N > 0 && D > 0 && K > 0, "%s: sizes must be positive (Q=%d N=%d D=%d K=%d)", pl.name, Q, N, D, K);
   ASM_REQUIRE(ldq >= D && ldi >= D && ldq % 8 == 0 && ldi % 8 == 0,
-              "retrieval_topk_wide: rows must be 16-byte multiples of at least D channels (ldq=%d ldi=%d D=%d)", ldq, ldi, D);
-  ASM_REQUIRE(index_base >= 0 && (long long)index_base + N <= 0x7fffffffLL, "retrieval_topk_wide: index_base + N exceeds int32");
-  if (similarity != 0 && similarity != 1)
-    ASM_FAIL(ASM_ENOTSUP, "retrieval_topk_wide: similarity %d (0 cosine, 1 euclidean)", similarity);
-  if (K > WIDE_MAX) ASM_FAIL(ASM_ENOTSUP, "retrieval_topk_wide: K = %d is above the cap of %d", K, WIDE_MAX);
-  ASM_REQUIRE(workspace && workspace_bytes >= asm_retrieval_topk_wide_workspace_bytes(Q, N, K),
-              "retrieval_topk_wide: workspace of %zu bytes, %zu needed", workspace_bytes,
-              asm_retrieval_topk_wide_workspace_bytes(Q, N, K));
+              "%s: rows must be 16-byte multiples of at least D channels (ldq=%d ldi=%d D=%d)", pl.name, ldq, ldi, D);
+  ASM_REQUIRE(index_base >= 0 && (long long)index_base + N <= 0x7fffffffLL, "%s: index_base + N exceeds int32", pl.name);
+  if (similarity != 0 && similarity != 1) ASM_FAIL(ASM_ENOTSUP, "%s: similarity %d (0 cosine, 1 euclidean)", pl.name, similarity);
+  if (K > pl.cap) ASM_FAIL(ASM_ENOTSUP, "%s: K = %d is above the cap of %d", pl.name, K, pl.cap);
+  const size_t need = retrieval_workspace_bound(Q, N, pl.target, pl.entries);
+  ASM_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", pl.name, workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
+  float* ws_val = (float*)workspace;           // [Q][S][entries] values, then as many indices
+  int* ws_idx = (int*)workspace + (size_t)Q * pl.S * pl.entries;
+  const bool direct = !wide && pl.S == 1;      // one split of sorted lists: its list IS the result
   TopkArgs a;
-  a.q = (const bf16_t*)queries;
-  a.x = (const bf16_t*)index;
-  a.sqq = sq_queries;
-  a.sqx = sq_index;
+  a.q = (const bf16_t*)queries; a.x = (const bf16_t*)index; a.sqq = sq_queries; a.sqx = sq_index;
+  a.out_val = direct ? top_val : ws_val; a.out_idx = direct ? top_idx : ws_idx;
   a.Q = Q; a.N = N; a.D = D; a.ldq = ldq; a.ldi = ldi; a.K = K; a.sim = similarity; a.index_base = index_base;
-  a.n_tiles = cdiv(N, BN);
-  a.S = retrieval_splits(Q, N, &a.tiles_per_split, WIDE_TARGET);
-  a.B = wide_capacity(K);
+  a.S = pl.S; a.tiles_per_split = pl.tiles_per_split; a.n_tiles = pl.n_tiles; a.B = pl.B;
   a.counters = counters;
-  a.out_val = (float*)workspace;               // [Q][S][B] candidate values, then as many indices
-  a.out_idx = (int*)workspace + (size_t)Q * a.S * a.B;
-  const int lds = (BM + BN) * PITCH + BN * 4 + 4 * 256 * 4;
-  ASM_LAUNCH(retrieval_topk_wide_kernel, dim3(cdiv(Q, BM), a.S), dim3(256), lds, st, a);
-  ASM_LAUNCH(topk_merge_wide_kernel, dim3(Q), dim3(256), 0, st, (const float*)a.out_val, (const int*)a.out_idx, a.S, K,
-             (size_t)a.B, top_val, top_idx);
-  ASM_CHECK_LAUNCH("retrieval_topk_wide");
+  const dim3 grid(cdiv(Q, BM), pl.S);
+  const int rc = wide ? asm_launch_dyn_lds<retrieval_topk_wide_kernel>(pl.name, grid, dim3(256), pl.lds, st, a)
+                      : asm_launch_dyn_lds<retrieval_topk_kernel>(pl.name, grid, dim3(256), pl.lds, st, a);
+  if (rc != ASM_OK || direct) return rc;
+  if (wide)
+    ASM_LAUNCH(topk_merge_wide_kernel, dim3(Q), dim3(256), 0, st, ws_val, ws_idx, pl.S, K, (size_t)pl.B, top_val, top_idx);
+  else
+    ASM_LAUNCH(topk_merge_kernel, dim3(cdiv(Q, 256)), dim3(256), 0, st, ws_val, ws_idx, Q, pl.S, K, top_val, top_idx);
+  ASM_CHECK_LAUNCH(pl.name);
   return ASM_OK;
+}
+
+extern "C" int asm_retrieval_topk(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
+                                  const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base,
+                                  float* top_val, int32_t* top_idx, void* workspace, size_t workspace_bytes, void* stream) {
+  return retrieval_launch(queries, ldq, index, ldi, sq_queries, sq_index, Q, N, D, similarity, K, index_base, top_val, top_idx,
+                          workspace, workspace_bytes, stream, false, nullptr);
 }
 
 extern "C" int asm_retrieval_topk_wide(const void* queries, int ldq, const void* index, int ldi, const float* sq_queries,
                                        const float* sq_index, int Q, int N, int D, int similarity, int K, int index_base,
                                        float* top_val, int32_t* top_idx, void* workspace, size_t workspace_bytes, void* stream) {
-  return retrieval_topk_wide(queries, ldq, index, ldi, sq_queries, sq_index, Q, N, D, similarity, K, index_base, top_val, top_idx,
-                             workspace, workspace_bytes, stream, nullptr);
+  return retrieval_launch(queries, ldq, index, ldi, sq_queries, sq_index, Q, N, D, similarity, K, index_base, top_val, top_idx,
+                          workspace, workspace_bytes, stream, true, nullptr);
 }
 
 // test-only (asm_hip_debug.h): the same call, adding to three device counters
@@ -764,20 +764,16 @@ extern "C" int asm_debug_retrieval_topk_wide_counted(const void* queries, int ld
                                                      void* workspace, size_t workspace_bytes, void* stream,
                                                      unsigned long long* counters3) {
   ASM_REQUIRE(counters3, "retrieval_topk_wide_counted: null counters");
-  return retrieval_topk_wide(queries, ldq, index, ldi, sq_queries, sq_index, Q, N, D, similarity, K, index_base, top_val, top_idx,
-                             workspace, workspace_bytes, stream, counters3);
+  return retrieval_launch(queries, ldq, index, ldi, sq_queries, sq_index, Q, N, D, similarity, K, index_base, top_val, top_idx,
+                          workspace, workspace_bytes, stream, true, counters3);
 }
 
-// test-only (asm_hip_debug.h): the split plan the two launchers above compute, through the same two functions; nothing is launched
+// test-only (asm_hip_debug.h): the RetrievalPlan the launcher would act on; nothing is launched
 extern "C" int asm_debug_retrieval_plan(int Q, int N, int K, int wide, int32_t plan[4]) {
+  const RetrievalPlan pl = retrieval_plan(Q, N, K, wide != 0);
   ASM_REQUIRE(plan && Q > 0 && N > 0 && K > 0, "retrieval_plan: bad arguments (Q=%d N=%d K=%d)", Q, N, K);
-  if (K > (wide ? WIDE_MAX : TOPK_MAX))
-    ASM_FAIL(ASM_ENOTSUP, "retrieval_plan: K = %d is above the cap of %d", K, wide ? WIDE_MAX : TOPK_MAX);
-  int tps = 0;
-  plan[0] = wide ? retrieval_splits(Q, N, &tps, WIDE_TARGET) : retrieval_splits(Q, N, &tps);
-  plan[1] = tps;
-  plan[2] = cdiv(N, BN);
-  plan[3] = wide ? wide_capacity(K) : 0;
+  if (K > pl.cap) ASM_FAIL(ASM_ENOTSUP, "retrieval_plan: K = %d is above the cap of %d", K, pl.cap);
+  plan[0] = pl.S; plan[1] = pl.tiles_per_split; plan[2] = pl.n_tiles; plan[3] = pl.B;
   return ASM_OK;
 }
 

@@ -1229,71 +1229,74 @@ def embed_sqnorm(x, D=None):
   return sq
 
 
-def retrieval_topk_workspace_bytes(Q, N, K) -> int:
-  return int(L().asm_retrieval_topk_workspace_bytes(Q, N, K))
+def topk_selection(K, selection='auto'):
+  """the top-K kernel for K results, 'list' or 'wide': the one named, or ('auto') the list kernel up to its cap, then the wide"""
+  if selection not in ('auto', 'list', 'wide'):
+    raise ValueError("selection %r (auto | list | wide)" % (selection,))
+  if selection == 'auto':
+    selection = 'list' if K <= TOPK_LIST_MAX else 'wide'
+  cap = TOPK_LIST_MAX if selection == 'list' else TOPK_WIDE_MAX
+  if K > cap:
+    raise NotImplementedError('max(k_list) + 1 = %d is above the cap of %d of the %s selection' % (K, cap, selection))
+  return selection
 
 
-def retrieval_topk(queries, index, sq_queries, sq_index, K, similarity='cosine', index_base=0, D=None):
-  """(top_val float32 [Q, K], top_idx int32 [Q, K]): the K index rows most similar to every query, best first, of equal
-  values the lower index first; top_idx counts from index_base (the first global row of this shard of the index)."""
+def _retrieval_topk(name, queries, index, sq_queries, sq_index, K, similarity, index_base, D):
+  """the body of retrieval_topk and retrieval_topk_wide: `name` is the wrapper's, asm_<name> its entry point"""
   if similarity not in SIMILARITIES:
     raise NotImplementedError('eval_similarity %r (cosine | euclidean)' % (similarity,))   # recall_metric.py:107-108
   Q, Dq, ldq = _emb(queries, D)
   N, Di, ldi = _emb(index, D)
   if Dq != Di:
     raise ValueError('queries have %d channels, the index %d' % (Dq, Di))
-  need = retrieval_topk_workspace_bytes(Q, N, K)
+  need = int(getattr(L(), 'asm_%s_workspace_bytes' % name)(Q, N, K))
   ws = _workspace(need, queries)
   val = empty((Q, K), F32, queries)
   idx = empty((Q, K), torch.int32, queries)
-  check(L().asm_retrieval_topk(_ptr(queries), ldq, _ptr(index), ldi, _ptr(sq_queries), _ptr(sq_index), Q, N, Dq,
-                               SIMILARITIES[similarity], K, index_base, _ptr(val), _ptr(idx), _ptr(ws), need, _stream()),
-        'retrieval_topk')
+  check(getattr(L(), 'asm_' + name)(_ptr(queries), ldq, _ptr(index), ldi, _ptr(sq_queries), _ptr(sq_index), Q, N, Dq,
+                                    SIMILARITIES[similarity], K, index_base, _ptr(val), _ptr(idx), _ptr(ws), need, _stream()),
+        name)
   return val, idx
 
 
-def topk_merge(vals, idxs):
-  """[rows, P, K] sorted lists (float32 values, int32 indices, -1 = unused) -> the K best per row, same order."""
+def _topk_merge(name, vals, idxs):
+  """the body of topk_merge and topk_merge_wide: `name` is the wrapper's, asm_<name> its entry point"""
   rows, P, K = vals.shape
   if tuple(idxs.shape) != (rows, P, K):
     raise ValueError('values and indices differ in shape')
   val = empty((rows, K), F32, vals)
   idx = empty((rows, K), torch.int32, vals)
-  check(L().asm_topk_merge(_ptr(vals), _ptr(idxs), rows, P, K, _ptr(val), _ptr(idx), _stream()), 'topk_merge')
+  check(getattr(L(), 'asm_' + name)(_ptr(vals), _ptr(idxs), rows, P, K, _ptr(val), _ptr(idx), _stream()), name)
   return val, idx
+
+
+def retrieval_topk_workspace_bytes(Q, N, K) -> int:
+  return int(L().asm_retrieval_topk_workspace_bytes(Q, N, K))
 
 
 def retrieval_topk_wide_workspace_bytes(Q, N, K) -> int:
   return int(L().asm_retrieval_topk_wide_workspace_bytes(Q, N, K))
 
 
+def retrieval_topk(queries, index, sq_queries, sq_index, K, similarity='cosine', index_base=0, D=None):
+  """(top_val float32 [Q, K], top_idx int32 [Q, K]): the K index rows most similar to every query, best first, of equal
+  values the lower index first; top_idx counts from index_base (the first global row of this shard of the index)."""
+  return _retrieval_topk('retrieval_topk', queries, index, sq_queries, sq_index, K, similarity, index_base, D)
+
+
 def retrieval_topk_wide(queries, index, sq_queries, sq_index, K, similarity='cosine', index_base=0, D=None):
   """retrieval_topk for K up to TOPK_WIDE_MAX: the same values and order, by a radix select over candidate buffers."""
-  if similarity not in SIMILARITIES:
-    raise NotImplementedError('eval_similarity %r (cosine | euclidean)' % (similarity,))   # recall_metric.py:107-108
-  Q, Dq, ldq = _emb(queries, D)
-  N, Di, ldi = _emb(index, D)
-  if Dq != Di:
-    raise ValueError('queries have %d channels, the index %d' % (Dq, Di))
-  need = retrieval_topk_wide_workspace_bytes(Q, N, K)
-  ws = _workspace(need, queries)
-  val = empty((Q, K), F32, queries)
-  idx = empty((Q, K), torch.int32, queries)
-  check(L().asm_retrieval_topk_wide(_ptr(queries), ldq, _ptr(index), ldi, _ptr(sq_queries), _ptr(sq_index), Q, N, Dq,
-                                    SIMILARITIES[similarity], K, index_base, _ptr(val), _ptr(idx), _ptr(ws), need, _stream()),
-        'retrieval_topk_wide')
-  return val, idx
+  return _retrieval_topk('retrieval_topk_wide', queries, index, sq_queries, sq_index, K, similarity, index_base, D)
+
+
+def topk_merge(vals, idxs):
+  """[rows, P, K] sorted lists (float32 values, int32 indices, -1 = unused) -> the K best per row, same order."""
+  return _topk_merge('topk_merge', vals, idxs)
 
 
 def topk_merge_wide(vals, idxs):
   """[rows, P, K] lists in any internal order (float32 values, int32 indices, -1 = unused) -> the K best per row, sorted."""
-  rows, P, K = vals.shape
-  if tuple(idxs.shape) != (rows, P, K):
-    raise ValueError('values and indices differ in shape')
-  val = empty((rows, K), F32, vals)
-  idx = empty((rows, K), torch.int32, vals)
-  check(L().asm_topk_merge_wide(_ptr(vals), _ptr(idxs), rows, P, K, _ptr(val), _ptr(idx), _stream()), 'topk_merge_wide')
-  return val, idx
+  return _topk_merge('topk_merge_wide', vals, idxs)
 
 
 def recall_accumulate(top_idx, query_labels, index_labels, query_base, k_list_dev, hits):

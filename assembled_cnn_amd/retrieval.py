@@ -35,15 +35,8 @@ class RecallEvaluator(object):
       raise ValueError('k_list must hold positive integers')
     if query_chunk < 1:
       raise ValueError('query_chunk must be positive')
-    if selection not in ('auto', 'list', 'wide'):
-      raise ValueError("selection %r (auto | list | wide)" % (selection,))
-    K = max(self.k_list) + 1                        # :110
-    if selection == 'auto':
-      selection = 'list' if K <= ops.TOPK_LIST_MAX else 'wide'
-    cap = ops.TOPK_LIST_MAX if selection == 'list' else ops.TOPK_WIDE_MAX
-    if K > cap:                                     # before an evaluation set has been embedded
-      raise NotImplementedError('max(k_list) + 1 = %d is above the cap of %d of the %s selection' % (K, cap, selection))
-    self.selection = selection
+    # K = max(k_list) + 1 (:110); a K above the cap is refused here, before an evaluation set has been embedded
+    self.selection = ops.topk_selection(max(self.k_list) + 1, selection)
     self.similarity = similarity
     self.query_chunk = int(query_chunk)
     self.reset()

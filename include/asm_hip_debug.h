@@ -42,7 +42,7 @@ int asm_debug_retrieval_topk_wide_counted(const void* queries, int ldq, const vo
                                           void* stream, unsigned long long* counters3);
 
 /* The plan of the list selection (wide = 0: asm_retrieval_topk) or of the wide one (wide != 0: asm_retrieval_topk_wide) for
- * Q queries, N index rows and K results, from the functions the launchers themselves call:
+ * Q queries, N index rows and K results, read from the RetrievalPlan that the one launcher of both entry points acts on:
  * plan = {S index splits (runs), 128-row tiles per split, tiles in all, capacity B of a (query, run) candidate buffer (0 for
  * the list selection)}.  S == 1 on the list path: the kernel writes the result itself, no merge launch.  The last split holds
  * tiles - (S - 1) * tiles_per_split tiles.  Host only: nothing is launched.  A non-positive size or a null plan -> ASM_EINVAL,

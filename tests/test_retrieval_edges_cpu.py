@@ -43,6 +43,24 @@ def test_plan_query_is_host_only_and_checks_its_arguments():
   assert L.asm_launch_count() == n0
 
 
+def test_a_refusal_names_the_entry_point_that_was_called():
+  """the two entry points share their checks: whichever refuses, the message starts with the name of the one called"""
+  lib, L = _lib()
+  n0 = L.asm_launch_count()
+  p = ctypes.c_void_p(0x1000)                      # never dereferenced: every call below returns before any launch
+  for name, cap in (('asm_retrieval_topk', 64), ('asm_retrieval_topk_wide', 1024)):
+    fn, ws = getattr(L, name), getattr(L, name + '_workspace_bytes')(100, 1000, 6)
+    assert ws > 0
+
+    def refused(q=p, K=6, wb=ws):
+      rc = fn(q, 64, p, 64, p, p, 100, 1000, 64, 0, K, 0, p, p, p, wb, None)
+      return rc, L.asm_last_error()
+    for kw, want in ((dict(q=None), lib.ASM_EINVAL), (dict(wb=ws - 1), lib.ASM_EINVAL), (dict(K=cap + 1), lib.ASM_ENOTSUP)):
+      rc, msg = refused(**kw)
+      assert rc == want and msg.startswith(name[len('asm_'):].encode() + b':'), (name, kw, rc, msg)
+  assert L.asm_launch_count() == n0
+
+
 def test_every_case_takes_the_path_it_claims():
   _, L = _lib()
   seen = set()

@@ -54,7 +54,7 @@ def main():
   ap.add_argument('--counters', action='store_true', help='wide selection: one more, untimed pass through the counting test entry')
   a = ap.parse_args()
   from assembled_cnn_amd import ops
-  wide = a.selection == 'wide' or (a.selection == 'auto' and a.k > ops.TOPK_LIST_MAX)
+  wide = ops.topk_selection(a.k, a.selection) == 'wide'
   topk = ops.retrieval_topk_wide if wide else ops.retrieval_topk
   out = []
   for shape in a.shapes.split(','):
