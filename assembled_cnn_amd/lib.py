@@ -305,6 +305,7 @@ SIGNATURES = {
     'asm_dense_small': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     'asm_dense_small_wgrad': (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _I, _P]),
     'asm_resize_crop_flip': (_I, [_P, C.c_int64, _P, _I, _I, _I, _I, _P, _P]),
+    'asm_preprocess_window': (_I, [_P, C.c_int64, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     'asm_autoaugment_workspace_bytes': (_I, [_I, _I, _I, C.POINTER(C.c_int64)]),
     'asm_autoaugment': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, C.c_int64, _P]),
     'asm_jpeg_decode_workspace_bytes': (_I, [C.c_int64, C.POINTER(C.c_int64)]),

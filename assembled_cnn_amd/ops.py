@@ -999,6 +999,31 @@ def resize_crop_flip(src_u8, descs_dev, n, out_h, out_w, subtract_mean):
   return out
 
 
+SOURCE_BYTES, SOURCE_UNIT = 0, 1                    # ASM_SOURCE_*
+TAIL_NONE, TAIL_MEANS, TAIL_ADD_CLAMP = 0, 1, 2     # ASM_TAIL_*
+
+
+def preprocess_window(src_u8, descs_dev, n, out_h, out_w, source=SOURCE_BYTES, tail=TAIL_NONE, add=None):
+  """asm_preprocess_window: resize_crop_flip with a three-valued per-image flip (0 none, 1 before the resize, 2 after resize
+  and crop), the source as bytes or scaled to [0, 1] before the interpolation, and a tail (none, minus CHANNEL_MEANS, or
+  per-image add [n, 3] float32 on the device -- None adds nothing -- followed by a clamp to [0, 1]).
+  Returns float32 [n, out_h, out_w, 3]."""
+  if descs_dev.numel() != C.sizeof(_lib.ImageDesc) * n:
+    raise ValueError('descriptor table must hold %d bytes' % (C.sizeof(_lib.ImageDesc) * n))
+  if source not in (SOURCE_BYTES, SOURCE_UNIT) or tail not in (TAIL_NONE, TAIL_MEANS, TAIL_ADD_CLAMP):
+    raise ValueError('unknown source mode %r or tail mode %r' % (source, tail))
+  if add is not None:
+    if tail != TAIL_ADD_CLAMP:
+      raise ValueError('an add table needs the add-and-clamp tail')
+    if add.dtype != F32 or tuple(add.shape) != (n, 3) or not add.is_contiguous() or add.device != src_u8.device:
+      raise ValueError('add must be contiguous float32 [%d, 3] on the device of the source' % n)
+  out = torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=src_u8.device)
+  if n:
+    check(L().asm_preprocess_window(_ptr(src_u8), src_u8.numel(), _ptr(descs_dev), n, out_h, out_w, source, tail,
+                                    _ptr(add) if add is not None else None, _ptr(out), _stream()), 'preprocess_window')
+  return out
+
+
 def autoaugment(images_f32, descs_dev, subtract_mean):
   """images_f32: float32 [n, H, W, 3] (resize_crop_flip's output without the mean subtraction); descs_dev: uint8 device
   view of n packed struct asm_augment_desc (autoaugment.sample / autoaugment.descriptor).  Returns the

@@ -37,7 +37,8 @@ extern "C" {
 
 /* Changes when an existing struct or signature changes.  Additions keep it: asm_jpeg_decode_progressive,
  * asm_jpeg_scan, asm_jpeg_decode_parallel, asm_crc32c_spans, asm_span_desc, asm_jpeg_parse and asm_jpeg_parse_fill came in
- * under 11, and so did asm_example_parse, asm_example_label_rows and asm_example_row: they only add entry points. */
+ * under 11, and so did asm_example_parse, asm_example_label_rows, asm_example_row and asm_preprocess_window: they only add
+ * entry points. */
 #define ASM_ABI_VERSION 11
 
 const char* asm_last_error(void);
@@ -610,11 +611,41 @@ typedef struct asm_image_desc {
   int32_t crop_y, crop_x, crop_h, crop_w;  /* window cut from the decoded image before the resize            */
   int32_t resize_h, resize_w;              /* size the window is resized to                                  */
   int32_t out_y, out_x;                    /* top-left of the output inside the resized window               */
-  int32_t flip;                            /* 1: window mirrored left-right before the resize                */
+  int32_t flip;                            /* 1: window mirrored left-right before the resize (asm_preprocess_window:
+                                            * one of ASM_FLIP_*)                                             */
   int32_t reserved;
 } asm_image_desc;                          /* 56 bytes */
 int asm_resize_crop_flip(const uint8_t* src, int64_t src_bytes, const asm_image_desc* descs, int N,
                          int out_h, int out_w, int subtract_mean, float* out, void* stream);
+
+/* The same launch in the general form the reference's other preprocessing types need (utils/data_util.py:346-378:
+ * preprocessing/reid_preprocessing.py:489-540, preprocessing/inception_preprocessing.py:117-144, :204-340).  Descriptors,
+ * window arithmetic, interpolation order and the memory-safety rule are asm_resize_crop_flip's; one launch per ragged
+ * batch, one thread per output pixel.  What it adds:
+ *   desc.flip  ASM_FLIP_*: 0 none; 1 the window mirrored before the resize (asm_resize_crop_flip's flip); 2 the OUTPUT
+ *              mirrored after resize and crop: output column j holds resized column out_x + (out_w - 1 - j)  (reid :516,
+ *              inception :284).
+ *              The legacy resize has no half-pixel centres, so 1 and 2 differ at every non-integer scale.  Any other
+ *              value counts as a window that does not fit: zeros for that image (the table lies on the device, so the
+ *              call cannot refuse it; the host mirror raises ValueError).
+ *   source     ASM_SOURCE_BYTES: taps are float(u8), 0..255.  ASM_SOURCE_UNIT: taps are float(u8) * float32(1.0 / 255)
+ *              BEFORE the interpolation (tf.image.convert_image_dtype: the double 1 / 255 rounded to float32 once, then a
+ *              float32 multiply).
+ *   tail       ASM_TAIL_NONE; ASM_TAIL_MEANS: minus CHANNEL_MEANS; ASM_TAIL_ADD_CLAMP: v = v + add[n][c], then
+ *              min(max(v, 0), 1)  (distort_color_fast).  add: float32 [N][3] on the device, or null: nothing is added and
+ *              only the clamp runs.  With another tail add must be null.
+ * With flip in {0, 1}, ASM_SOURCE_BYTES and tail = subtract_mean the output equals asm_resize_crop_flip's bit for bit.
+ * ASM_EINVAL: as asm_resize_crop_flip, plus an unknown source or tail value and an add table without its tail. */
+#define ASM_FLIP_NONE 0
+#define ASM_FLIP_BEFORE 1
+#define ASM_FLIP_AFTER 2
+#define ASM_SOURCE_BYTES 0
+#define ASM_SOURCE_UNIT 1
+#define ASM_TAIL_NONE 0
+#define ASM_TAIL_MEANS 1
+#define ASM_TAIL_ADD_CLAMP 2
+int asm_preprocess_window(const uint8_t* src, int64_t src_bytes, const asm_image_desc* descs, int N, int out_h, int out_w,
+                          int source, int tail, const float* add, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * AutoAugment (preprocessing/autoaugment.py), applied where the reference applies it: after the resize, on

@@ -4,7 +4,8 @@ kernel), the device JPEG decoder in front of it, and evaluation-mode inference w
 configs 1 and 3-eval).  `--only jpeg` runs the JPEG leg alone, `--only jpeg_progressive` the progressive-file leg,
 `--only jpeg_parallel` the sequential entropy stage against the segment-parallel one, `--only records` the record
 checksum kernel against that stage and the assembly of a batch out of TFRecord shards, `--only jpeg_device_parse` the
-device header parse against the host parse."""
+device header parse against the host parse, `--only preprocess_types` asm_preprocess_window in its ImageNet-equivalent, re-ID and
+Inception forms against asm_resize_crop_flip."""
 import os, sys, time
 import numpy as np
 import torch
@@ -464,7 +465,51 @@ def jpeg_device_parse_leg(n=256):
     print('  fastest resident / fastest host: %.3f' % (min(ms[True]) / min(ms[False])))
 
 
-LEGS = {'jpeg_device_parse': jpeg_device_parse_leg, 'jpeg': jpeg_leg, 'jpeg_progressive': jpeg_progressive_leg, 'jpeg_parallel': jpeg_parallel_leg, 'records': records_leg}
+def preprocess_types_leg(n=256, side=224, iters=500):
+  """asm_preprocess_window against asm_resize_crop_flip on n decoded images of 300..600 pixels a side at side x side (the
+  batch of profiles/autoaugment.md): the old entry point, the new one on the same table (byte source, mean tail), the re-ID
+  training form (whole image, selector / offset / flip-after sampled) and the Inception training form (sampled box, flip
+  after, source scaled to [0, 1], add + clamp).  Same process, alternating, three runs of `iters` launches each."""
+  rng = np.random.default_rng(0)
+  imgs = [rng.integers(0, 256, size=(int(rng.integers(300, 600)), int(rng.integers(300, 600)), 3), dtype=np.uint8) for _ in range(n)]
+  shapes = [im.shape[:2] for im in imgs]
+  tables = {'imagenet': [P.train_window(h, w, side, side, rng) for h, w in shapes],
+            'reid': [P.reid_train_window(h, w, side, rng) for h, w in shapes],
+            'inception': [P.inception_train_window(h, w, side, side, rng) for h, w in shapes]}
+  tables['reid, no flip'] = [dict(w, flip=0) for w in tables['reid']]
+  bd, td = None, {}
+  for k, wins in tables.items():
+    buf, table = P.pack_batch(imgs, wins, side, side)
+    bd, td[k] = buf.cuda(), table.cuda()
+  add = torch.from_numpy(np.stack([P.color_offsets(*P.sample_color_draws(rng)) for _ in range(n)])).cuda()
+  forms = {'resize_crop_flip (imagenet windows, mean-sub)': lambda: ops.resize_crop_flip(bd, td['imagenet'], n, side, side, True),
+           'preprocess_window, the same table and form': lambda: ops.preprocess_window(bd, td['imagenet'], n, side, side, ops.SOURCE_BYTES, ops.TAIL_MEANS),
+           'preprocess_window, re-ID training form': lambda: ops.preprocess_window(bd, td['reid'], n, side, side, ops.SOURCE_BYTES, ops.TAIL_MEANS),
+           'preprocess_window, Inception training form': lambda: ops.preprocess_window(bd, td['inception'], n, side, side, ops.SOURCE_UNIT, ops.TAIL_ADD_CLAMP, add),
+           'resize_crop_flip, the re-ID windows unflipped': lambda: ops.resize_crop_flip(bd, td['reid, no flip'], n, side, side, True)}
+  names = list(forms)
+  assert torch.equal(forms[names[0]](), forms[names[1]]()), 'the new entry point computes other bits than the old one'
+  ms = {k: [] for k in names}
+  for _ in range(3):       # alternating
+    for k in names:
+      ms[k].append(ev(forms[k], iters=iters))
+  out_bytes = n * side * side * 3 * 4
+  print('preprocess types: %d images of 300..600 a side (%.0f MB packed) -> %dx%d float32 (%.0f MB); ms per launch, three alternating '
+        'runs of %d launches, then median and spread' % (n, bd.numel() / 1e6, side, side, out_bytes / 1e6, iters))
+  for k in names:
+    v = sorted(ms[k])
+    print('  %-48s: %s  (%.4f, %.4f)' % (k, ' '.join('%.4f' % m for m in ms[k]), v[1], v[2] - v[0]))
+  area = lambda wins: np.mean([w['crop_h'] * w['crop_w'] / float(h * w_) for w, (h, w_) in zip(wins, shapes)])
+  print('  share of the packed source inside the windows: imagenet %.2f, re-ID %.2f, Inception %.2f'
+        % tuple(area(tables[k]) for k in ('imagenet', 'reid', 'inception')))
+  for ref, against in ((names[0], names[1:4]), (names[4], names[2:3])):
+    old = sorted(ms[ref])
+    bar = old[1] + (old[2] - old[0])
+    print('  bar = median of "%s" + its spread in this process = %.4f ms: %s'
+          % (ref, bar, ', '.join('%s %s' % (k.split(', ')[1], 'within' if sorted(ms[k])[1] <= bar else 'ABOVE') for k in against)))
+
+
+LEGS = {'preprocess_types': preprocess_types_leg, 'jpeg_device_parse': jpeg_device_parse_leg, 'jpeg': jpeg_leg, 'jpeg_progressive': jpeg_progressive_leg, 'jpeg_parallel': jpeg_parallel_leg, 'records': records_leg}
 if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] in LEGS:
   LEGS[sys.argv[sys.argv.index('--only') + 1]]()
   sys.exit(0)
