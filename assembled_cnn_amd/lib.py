@@ -286,6 +286,7 @@ SIGNATURES = {
     'asm_dropblock_apply': (_I, [_P, _P, _P, _P, _I, _P, _I, _I, _P]),
     'asm_eval_rows': (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     'asm_eval_accumulate': (_I, [_P, _P, _P, _I, _P, _P]),
+    'asm_eval_groups': (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     'asm_embed_sqnorm': (_I, [_P, _I, _I, _I, _P, _P]),
     'asm_retrieval_topk_workspace_bytes': (_Z, [_I, _I, _I]),
     'asm_retrieval_topk': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),

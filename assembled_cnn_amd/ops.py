@@ -987,6 +987,22 @@ def eval_accumulate(conf, top1, top5, state33):
         'eval_accumulate')
 
 
+def eval_groups(logits, ld, labels_i32, groups_i32, B, Cn, G, counts, want_pred=False):
+  """asm_eval_groups: arg-max, top-1 and top-5 hit of every row added into counts[group] (int32 [(G + 1), 3] on the device,
+  accumulated into; row G takes the rows whose group id lies outside [0, G)).  One launch, nothing is read back.  Returns
+  the predicted classes (int32 [B], -1 for a row of NaNs) if want_pred, else None."""
+  if counts.dtype != torch.int32 or counts.numel() != (G + 1) * 3:
+    raise ValueError('counts must be int32 [%d, 3]' % (G + 1))
+  if labels_i32.dtype != torch.int32 or groups_i32.dtype != torch.int32 or labels_i32.numel() < B or groups_i32.numel() < B:
+    raise ValueError('labels and groups must be int32 [%d]' % B)
+  if logits.dtype != F32 or logits.numel() < (B - 1) * ld + Cn:
+    raise ValueError('logits must be float32 with %d rows of stride %d' % (B, ld))
+  pred = empty((B,), torch.int32, logits) if want_pred else None
+  check(L().asm_eval_groups(_ptr(logits), ld, _ptr(labels_i32), _ptr(groups_i32), B, Cn, G, _ptr(counts), _ptr(pred),
+                            _stream()), 'eval_groups')
+  return pred
+
+
 def resize_crop_flip(src_u8, descs_dev, n, out_h, out_w, subtract_mean):
   """src_u8: 1-D uint8 device buffer with the decoded images back to back; descs_dev: uint8 device view of
   n packed struct asm_image_desc.  Returns float32 [n, out_h, out_w, 3]."""

@@ -532,6 +532,23 @@ int asm_eval_rows(const float* logits, int ld, const int32_t* labels, int B, int
                   float* top1, float* top5, void* stream);
 int asm_eval_accumulate(const float* conf, const float* top1, const float* top5, int B, float* state33,
                         void* stream);
+/* mce/eval_robustness.py:186-226 for a batch whose rows belong to G groups (group = corruption * 5 + severity - 1):
+ * per row the arg-max class (lowest index among equal maxima: tf.nn.top_k / tf.argmax), top-1 hit, in_top_k(k=5) hit,
+ * added into counts[group].  counts: int32 [(G + 1)][3] = {images, top-1 hits, top-5 hits}; row G collects the rows whose
+ * group id is outside [0, G) (images only, never a hit).  Integer atomics: exact, the same bits on every run.
+ * pred: int32 [B] or null.  One launch; logits: float32 rows of C classes with a row stride ld (elements); columns
+ * C .. ld-1 are never read.  The rules:
+ *   - the arg-max runs over the non-NaN logits of the row, the lowest index winning a tie;
+ *   - a row with no non-NaN logit has pred = -1 and no hit;
+ *   - top-1 hit: pred == label;
+ *   - top-5 hit: the label lies in [0, C), its logit is finite (TensorFlow's in_top_k answers false for a non-finite
+ *     target) and fewer than 5 logits of the row are strictly larger;
+ *   - a label outside [0, C) is never read and never hit;
+ *   - counts is accumulated into, never cleared;
+ *   - a null logits / labels / groups / counts, B, C or G <= 0 and ld < C are ASM_EINVAL, before any launch.
+ * The arg-max is taken of the logits, not of their float32 softmax as the reference does. */
+int asm_eval_groups(const float* logits, int ld, const int32_t* labels, const int32_t* groups, int B, int C, int G,
+                    int32_t* counts, int32_t* pred, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Retrieval evaluation: Recall@K (metric/recall_metric.py; --zeroshot_eval, nets/run_loop_classification.py:439-445).

@@ -5,7 +5,8 @@ configs 1 and 3-eval).  `--only jpeg` runs the JPEG leg alone, `--only jpeg_prog
 `--only jpeg_parallel` the sequential entropy stage against the segment-parallel one, `--only records` the record
 checksum kernel against that stage and the assembly of a batch out of TFRecord shards, `--only jpeg_device_parse` the
 device header parse against the host parse, `--only preprocess_types` asm_preprocess_window in its ImageNet-equivalent, re-ID and
-Inception forms against asm_resize_crop_flip."""
+Inception forms against asm_resize_crop_flip, `--only robustness` the grouped classifier tail of the mCE evaluation against the
+asm_eval_rows + asm_eval_accumulate pair and CorruptionEvaluator.add in images/s."""
 import os, sys, time
 import numpy as np
 import torch
@@ -509,7 +510,82 @@ def preprocess_types_leg(n=256, side=224, iters=500):
           % (ref, bar, ', '.join('%s %s' % (k.split(', ')[1], 'within' if sorted(ms[k])[1] <= bar else 'ABOVE') for k in against)))
 
 
-LEGS = {'preprocess_types': preprocess_types_leg, 'jpeg_device_parse': jpeg_device_parse_leg, 'jpeg': jpeg_leg, 'jpeg_progressive': jpeg_progressive_leg, 'jpeg_parallel': jpeg_parallel_leg, 'records': records_leg}
+def robustness_tail(B, C, G, iters, with_pair):
+  """asm_eval_groups on B x C logits with sorted, random and single-group ids (and the asm_eval_rows + asm_eval_accumulate pair
+  on the same logits): device events around `iters` calls, alternating, three runs each"""
+  rng = np.random.default_rng(0)
+  ld = (C + 7) // 8 * 8
+  z = torch.from_numpy((rng.standard_normal((B, ld)) * 3).astype(np.float32)).cuda()
+  lab = torch.from_numpy(rng.integers(1, C, B).astype(np.int32)).cuda()
+  ids = {'sorted groups': np.sort(rng.integers(0, G, B)), 'random groups': rng.integers(0, G, B), 'one group': np.full(B, 42)}
+  ids = {k: torch.from_numpy(v.astype(np.int32)).cuda() for k, v in ids.items()}
+  counts = torch.zeros((G + 1, 3), dtype=torch.int32, device='cuda')
+  state = torch.zeros((33,), dtype=torch.float32, device='cuda')
+
+  def pair():
+    _, conf, t1, t5 = ops.eval_rows(z, ld, lab, B, C)
+    ops.eval_accumulate(conf, t1, t5, state)
+  forms = {'eval_groups, ' + k: (lambda g=g: ops.eval_groups(z, ld, lab, g, B, C, G, counts)) for k, g in ids.items()}
+  if with_pair:
+    forms['eval_rows + eval_accumulate (one running state)'] = pair
+    # the same hits first: top-1 and top-5 sums of the pair against the pooled counters of one call
+    pair(); forms['eval_groups, random groups']()
+    st, c = state.cpu().numpy(), counts.cpu().numpy().sum(axis=0)
+    assert (int(st[2]), int(st[0]), int(st[1])) == (int(c[0]), int(c[1]), int(c[2])), (st[:3], c)
+  ms = {k: [] for k in forms}
+  for _ in range(3):       # alternating
+    for k in forms:
+      counts.zero_()
+      ms[k].append(ev(forms[k], iters=iters))
+  print('robustness tail: B=%d C=%d ld=%d G=%d (%.1f MB of logits); ms per call, three alternating runs of %d calls, then median '
+        'and spread' % (B, C, ld, G, B * ld * 4 / 1e6, iters))
+  for k in forms:
+    v = sorted(ms[k])
+    print('  %-50s: %s  (%.4f, %.4f)  %.0f GB/s' % (k, ' '.join('%.4f' % m for m in ms[k]), v[1], v[2] - v[0], B * C * 4 / v[1] / 1e6))
+  one, rnd = sorted(ms['eval_groups, one group'])[1], sorted(ms['eval_groups, random groups'])[1]
+  print('  one group / random groups = %.2f (atomic contention: all %d rows on three addresses)' % (one / rnd, B))
+
+
+def robustness_leg(C=1001, G=95, n=256, side=256):
+  """The grouped classifier tail at the evaluation's batch (B = 1024: the time of a call, host side included) and at B = 65536
+  (262 MB of logits: the kernel itself, where contention of the atomics would show).  Then CorruptionEvaluator.add in
+  images/s on n synthetic side x side JPEGs (4:2:0, quality 90) in batches of 64 through an Assemble-ResNet-50, with the default
+  options and with the device header parse + the parallel entropy stage."""
+  import io
+  from assembled_cnn_amd import robustness as R
+  robustness_tail(1024, C, G, 5000, True)
+  robustness_tail(65536, C, G, 200, False)
+  rng = np.random.default_rng(0)
+  from PIL import Image
+  files = []
+  for _ in range(n):
+    low = Image.fromarray(rng.integers(0, 256, size=(side // 24 + 2, side // 24 + 2, 3), dtype=np.uint8)).resize((side, side), Image.BICUBIC)
+    arr = np.clip(np.asarray(low).astype(np.float32) + rng.normal(0, 9, size=(side, side, 3)), 0, 255).astype(np.uint8)
+    b = io.BytesIO()
+    Image.fromarray(arr).save(b, 'JPEG', quality=90, subsampling=2)
+    files.append(b.getvalue())
+  hp = HParams(zero_gamma=True, batch_size=64, resnet_version=2, use_sk_block=True, anti_alias_type='sconv', anti_alias_filter_size=3)
+  tr = Trainer(hp, device='cuda', recorded=False)
+  tr.model.build((side, side))
+  evl = R.CorruptionEvaluator(tr, side)
+  labels, sev = rng.integers(1, C, n), rng.integers(1, 6, n)
+  print('robustness add: %d synthetic %dx%d JPEGs (mean %.1f KB), batches of 64, Assemble-ResNet-50; no ImageNet-C data and no '
+        'published checkpoint here: a rate, not an mCE' % (n, side, side, sum(map(len, files)) / n / 1e3))
+  for what, kw in (('default options', {}), ("jpeg_parse='device', jpeg_entropy='parallel'", dict(jpeg_parse='device', jpeg_entropy='parallel'))):
+    def sweep():
+      for s in range(0, n, 64):
+        evl.add(files[s:s + 64], labels[s:s + 64], 'fog', sev[s:s + 64], **kw)
+      torch.cuda.synchronize()
+    sweep()
+    runs = []
+    for _ in range(3):
+      t0 = time.time(); sweep(); runs.append(n / (time.time() - t0))
+    print('  %-46s: %s img/s' % (what, ' '.join('%.0f' % r for r in runs)))
+  x = torch.randn((64, side, side, 3), device='cuda') * 50
+  print('  the forward alone, batch 64: %.1f ms' % ev(lambda: tr.eval_logits(x), iters=5))
+
+
+LEGS = {'robustness': robustness_leg, 'preprocess_types': preprocess_types_leg, 'jpeg_device_parse': jpeg_device_parse_leg, 'jpeg': jpeg_leg, 'jpeg_progressive': jpeg_progressive_leg, 'jpeg_parallel': jpeg_parallel_leg, 'records': records_leg}
 if '--only' in sys.argv and sys.argv[sys.argv.index('--only') + 1] in LEGS:
   LEGS[sys.argv[sys.argv.index('--only') + 1]]()
   sys.exit(0)
