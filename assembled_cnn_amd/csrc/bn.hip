@@ -849,7 +849,8 @@ __global__ __launch_bounds__(256) void bn_small_bwd_kernel(const bf16_t* __restr
   }
 }
 
-inline unsigned ew_grid(size_t nvec) {
+// the for_each_vec kernels' own cap, half of common.h's ew_grid
+inline unsigned bn_vec_grid(size_t nvec) {
   size_t b = cdivz(nvec, 256);
   return (unsigned)(b < 4096 ? (b ? b : 1) : 4096);
 }
@@ -858,7 +859,7 @@ inline unsigned ew_grid(size_t nvec) {
 template <class... P, class... A>
 void launch_vecs(void (*kernel)(size_t, int, FastDiv, P...), void* stream, int M, int C, A... rest) {
   const size_t nvec = (size_t)M * (C / 8);
-  ASM_LAUNCH(kernel, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, nvec, C, make_fastdiv((unsigned)(C / 8)), rest...);
+  ASM_LAUNCH(kernel, dim3(bn_vec_grid(nvec)), dim3(256), 0, (hipStream_t)stream, nvec, C, make_fastdiv((unsigned)(C / 8)), rest...);
 }
 
 }  // namespace

@@ -186,6 +186,19 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// Sum or maximum over a 256-thread block.  sh: 4 floats of LDS, free for the next call as soon as this one returns (the
+// first barrier guards the previous call's reads).  The four wave partials meet in wave order, sh[0] + sh[1] + sh[2] + sh[3]:
+// a fixed order, the same bits on every run.
+__device__ __forceinline__ float block_reduce(float v, bool is_max, float* sh) {
+  v = is_max ? wave_max(v) : wave_sum(v);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) sh[w] = v;
+  __syncthreads();
+  float r = sh[0];
+  for (int i = 1; i < 4; ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
+  return r;
+}
 
 // ---- invariant integer division (n < 2^31) --------------------------------------------------------
 struct FastDiv {
@@ -241,6 +254,13 @@ static inline int asm_launch_dyn_lds(const char* name, dim3 grid, dim3 block, in
   ASM_CHECK_LAUNCH(name);
   return ASM_OK;
 }
+// The tail of an entry point that makes exactly one launch, without dynamic LDS: launch, check, ASM_OK.
+template <auto KERN, class... A>
+static inline int asm_launch_checked(const char* name, dim3 grid, dim3 block, hipStream_t st, A&&... a) {
+  ASM_LAUNCH(KERN, grid, block, 0, st, std::forward<A>(a)...);
+  ASM_CHECK_LAUNCH(name);
+  return ASM_OK;
+}
 // compute units of the current device (cached per device; 256 on MI355X)
 static inline int asm_num_cus() {
   static int cached[ASM_MAX_DEVICES] = {};
@@ -253,6 +273,11 @@ static inline int asm_num_cus() {
   return cached[dev];
 }
 static inline size_t cdivz(size_t a, size_t b) { return (a + b - 1) / b; }
+// 256-thread blocks of a grid-stride element-wise kernel over n items: one block per 256 items, at least 1, at most 8192
+static inline unsigned ew_grid(size_t n) {
+  size_t b = cdivz(n, 256);
+  return (unsigned)(b < 8192 ? (b ? b : 1) : 8192);
+}
 
 // buffer resource for raw (stride 0) access: out-of-range offsets load 0
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {

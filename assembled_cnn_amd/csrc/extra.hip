@@ -1,19 +1,8 @@
 // Kernels of the "next" rows of the scope table and the remaining loss / pooling variants:
-// DropBlock, GeM pooling, sigmoid cross-entropy, on-device evaluation metrics (top-1 / top-5 / ECE bins).
+// DropBlock, GeM pooling, sigmoid cross-entropy.  (The on-device evaluation metrics are in eval.hip.)
 #include "common.h"
 
 namespace {
-
-__device__ float block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  float r = 0.f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) r += sh[i];
-  return r;
-}
 
 // ---- sigmoid cross-entropy (losses/cls_losses.py:34-38): sum(ce) / sum(onehot) ---------------------------
 __global__ __launch_bounds__(256) void sigmoid_ce_rows_kernel(const float* __restrict__ logits, int ld,
@@ -27,8 +16,8 @@ __global__ __launch_bounds__(256) void sigmoid_ce_rows_kernel(const float* __res
     ce += fmaxf(z, 0.f) - z * t + log1pf(__expf(-fabsf(z)));
     ys += t;
   }
-  ce = block_sum(ce, sh);
-  ys = block_sum(ys, sh);
+  ce = block_reduce(ce, false, sh);
+  ys = block_reduce(ys, false, sh);
   if (threadIdx.x == 0) {
     rows[b * 2] = ce;
     rows[b * 2 + 1] = ys;
@@ -42,8 +31,8 @@ __global__ __launch_bounds__(256) void sigmoid_ce_total_kernel(const float* __re
     ce += rows[b * 2];
     ys += rows[b * 2 + 1];
   }
-  ce = block_sum(ce, sh);
-  ys = block_sum(ys, sh);
+  ce = block_reduce(ce, false, sh);
+  ys = block_reduce(ys, false, sh);
   if (threadIdx.x == 0) {
     out[0] = ce / ys;
     out[1] = ys;
@@ -129,7 +118,7 @@ __global__ __launch_bounds__(256) void dropblock_norm_kernel(const float* __rest
   __shared__ float sh[4];
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) s += keep[i];
-  s = block_sum(s, sh);
+  s = block_reduce(s, false, sh);
   if (threadIdx.x == 0) *scale = (float)n / (s + 1e-8f);   // mask size / (sum + 1e-8) (:245-250)
 }
 // y = [relu]( x * keep[hw,c] * scale ) ; backward: dx = dy * keep * scale * [y > 0]
@@ -163,101 +152,6 @@ __global__ __launch_bounds__(256) void dropblock_apply_kernel(const bf16_t* __re
   }
 }
 
-// ---- evaluation metrics (nets/run_loop_classification.py:208-219, metric/ece_metric.py:171-298) ------------
-// per row: argmax, max softmax probability, top-1 hit, in_top_k(k=5) hit
-__global__ __launch_bounds__(256) void eval_rows_kernel(const float* __restrict__ logits, int ld,
-                                                        const int32_t* __restrict__ labels, int C,
-                                                        int32_t* __restrict__ pred, float* __restrict__ conf,
-                                                        float* __restrict__ top1, float* __restrict__ top5) {
-  __shared__ float shv[4];
-  __shared__ int shi[4];
-  __shared__ float sh[4];
-  const int b = blockIdx.x;
-  const float* z = logits + (size_t)b * ld;
-  const int lab = labels[b];
-  // a label outside [0, C) can never be hit (tf.nn.in_top_k yields False for an out-of-range target): no stray read
-  const bool lab_ok = (unsigned)lab < (unsigned)C;
-  const float zl = lab_ok ? z[lab] : INFINITY;
-  float mx = -INFINITY;
-  int arg = 0x7fffffff;
-  float higher = 0.f;
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const float v = z[c];
-    if (v > mx) {
-      mx = v;
-      arg = c;
-    }
-    higher += (v > zl) ? 1.f : 0.f;   // tf.nn.in_top_k: the target is in the top k unless k others are larger
-  }
-  // block arg-max (lowest index wins ties, like tf.argmax)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(mx, o, 64);
-    const int oa = __shfl_xor(arg, o, 64);
-    if (ov > mx || (ov == mx && oa < arg)) {
-      mx = ov;
-      arg = oa;
-    }
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    shv[w] = mx;
-    shi[w] = arg;
-  }
-  __syncthreads();
-  mx = shv[0];
-  arg = shi[0];
-  for (int i = 1; i < 4; ++i)
-    if (shv[i] > mx || (shv[i] == mx && shi[i] < arg)) {
-      mx = shv[i];
-      arg = shi[i];
-    }
-  float se = 0.f;
-  for (int c = threadIdx.x; c < C; c += 256) se += __expf(z[c] - mx);
-  se = block_sum(se, sh);
-  higher = block_sum(higher, sh);
-  if (threadIdx.x == 0) {
-    pred[b] = arg;
-    conf[b] = 1.0f / se;                      // max of softmax
-    top1[b] = arg == lab ? 1.f : 0.f;
-    top5[b] = (lab_ok && higher < 5.f) ? 1.f : 0.f;
-  }
-}
-// state[0..2] = sum top1, sum top5, count ; state[3..12] correct per bin, [13..22] conf per bin, [23..32] count per bin
-__global__ __launch_bounds__(64) void eval_accumulate_kernel(const float* __restrict__ conf,
-                                                             const float* __restrict__ top1,
-                                                             const float* __restrict__ top5, int B,
-                                                             float* __restrict__ state) {
-  const int t = threadIdx.x;
-  if (t < 3) {
-    float s = 0.f;
-    for (int b = 0; b < B; ++b) s += (t == 0) ? top1[b] : (t == 1 ? top5[b] : 1.f);
-    state[t] += s;
-  } else if (t < 13) {  // ECE bin t-3: (lo, hi] with the reference's epsilon-widened outer edges
-    const int bin = t - 3;
-    const float eps = 1e-7f;
-    const float lo = bin == 0 ? -eps : (float)bin / 10.f;
-    const float hi = bin == 9 ? 1.f + eps : (float)(bin + 1) / 10.f;
-    float cor = 0.f, cs = 0.f, cnt = 0.f;
-    for (int b = 0; b < B; ++b) {
-      const float c = conf[b];
-      if (c > lo && c <= hi) {
-        cor += top1[b];
-        cs += c;
-        cnt += 1.f;
-      }
-    }
-    state[3 + bin] += cor;
-    state[13 + bin] += cs;
-    state[23 + bin] += cnt;
-  }
-}
-
-inline unsigned ew_grid(size_t n) {
-  size_t b = cdivz(n, 256);
-  return (unsigned)(b < 8192 ? (b ? b : 1) : 8192);
-}
-
 }  // namespace
 
 extern "C" int asm_sigmoid_ce(const float* logits, int ld, const float* targets, int B, int C, float loss_scale,
@@ -276,64 +170,41 @@ extern "C" int asm_sigmoid_ce(const float* logits, int ld, const float* targets,
 
 extern "C" int asm_gem_fwd(const void* x, void* y, float* ssum, int N, int HW, int C, float p, void* stream) {
   ASM_REQUIRE(x && y && ssum && N > 0 && HW > 0 && C > 0 && p > 0.f, "gem_fwd: bad arguments");
-  ASM_LAUNCH(gem_fwd_kernel, dim3(cdiv(C, 256), N), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     (bf16_t*)y, ssum, HW, C, p);
-  ASM_CHECK_LAUNCH("gem_fwd");
-  return ASM_OK;
+  return asm_launch_checked<gem_fwd_kernel>("gem_fwd", dim3(cdiv(C, 256), N), 256, (hipStream_t)stream, (const bf16_t*)x,
+                                            (bf16_t*)y, ssum, HW, C, p);
 }
 extern "C" int asm_gem_bwd(const void* x, const void* dy, const float* ssum, void* dx, int N, int HW, int C, float p,
                            void* stream) {
   ASM_REQUIRE(x && dy && ssum && dx && N > 0 && HW > 0 && C > 0 && p > 0.f, "gem_bwd: bad arguments");
-  ASM_LAUNCH(gem_bwd_kernel, dim3((unsigned)cdivz((size_t)N * HW * C, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, (const bf16_t*)dy, ssum, (bf16_t*)dx, N, HW, C, p);
-  ASM_CHECK_LAUNCH("gem_bwd");
-  return ASM_OK;
+  return asm_launch_checked<gem_bwd_kernel>("gem_bwd", (unsigned)cdivz((size_t)N * HW * C, 256), 256, (hipStream_t)stream,
+                                            (const bf16_t*)x, (const bf16_t*)dy, ssum, (bf16_t*)dx, N, HW, C, p);
 }
 
+// both forms of the mask: the Bernoulli mean as an argument (gamma), or with `dev` in device memory (gamma_dev[0])
+static int dropblock_mask(const float* uniform, float gamma, const float* gamma_dev, bool dev, const char* name, int H, int W,
+                          int C, int block_size, float* keep, float* scale, void* stream) {
+  ASM_REQUIRE(uniform && (gamma_dev || !dev) && keep && scale && H >= block_size && W >= block_size && C > 0 && block_size >= 1,
+              "%s: bad arguments (H=%d W=%d block=%d)", name, H, W, block_size);
+  hipStream_t st = (hipStream_t)stream;
+  ASM_LAUNCH(dropblock_mask_kernel, dim3(cdiv(H * W * C, 256)), dim3(256), 0, st, uniform, gamma, gamma_dev, H, W, C,
+             block_size, keep);
+  ASM_LAUNCH(dropblock_norm_kernel, dim3(1), dim3(256), 0, st, keep, H * W * C, scale);
+  ASM_CHECK_LAUNCH(name);
+  return ASM_OK;
+}
 extern "C" int asm_dropblock_mask(const float* uniform, float gamma, int H, int W, int C, int block_size, float* keep,
                                   float* scale, void* stream) {
-  ASM_REQUIRE(uniform && keep && scale && H >= block_size && W >= block_size && C > 0 && block_size >= 1,
-              "dropblock_mask: bad arguments (H=%d W=%d block=%d)", H, W, block_size);
-  hipStream_t st = (hipStream_t)stream;
-  ASM_LAUNCH(dropblock_mask_kernel, dim3(cdiv(H * W * C, 256)), dim3(256), 0, st, uniform, gamma, (const float*)nullptr, H, W,
-                     C, block_size, keep);
-  ASM_LAUNCH(dropblock_norm_kernel, dim3(1), dim3(256), 0, st, keep, H * W * C, scale);
-  ASM_CHECK_LAUNCH("dropblock_mask");
-  return ASM_OK;
+  return dropblock_mask(uniform, gamma, nullptr, false, "dropblock_mask", H, W, C, block_size, keep, scale, stream);
 }
 extern "C" int asm_dropblock_mask_dev(const float* uniform, const float* gamma_dev, int H, int W, int C, int block_size,
                                       float* keep, float* scale, void* stream) {
-  ASM_REQUIRE(uniform && gamma_dev && keep && scale && H >= block_size && W >= block_size && C > 0 && block_size >= 1,
-              "dropblock_mask_dev: bad arguments (H=%d W=%d block=%d)", H, W, block_size);
-  hipStream_t st = (hipStream_t)stream;
-  ASM_LAUNCH(dropblock_mask_kernel, dim3(cdiv(H * W * C, 256)), dim3(256), 0, st, uniform, 0.f, gamma_dev, H, W, C,
-                     block_size, keep);
-  ASM_LAUNCH(dropblock_norm_kernel, dim3(1), dim3(256), 0, st, keep, H * W * C, scale);
-  ASM_CHECK_LAUNCH("dropblock_mask_dev");
-  return ASM_OK;
+  return dropblock_mask(uniform, 0.f, gamma_dev, true, "dropblock_mask_dev", H, W, C, block_size, keep, scale, stream);
 }
 extern "C" int asm_dropblock_apply(const void* x, const float* keep, const float* scale, const void* relu_mask_from,
                                    int relu, void* y, int N, int HWC, void* stream) {
   ASM_REQUIRE(x && keep && scale && y && N > 0 && HWC > 0 && HWC % 8 == 0, "dropblock_apply: bad arguments");
   const size_t nvec = (size_t)N * (HWC / 8);
-  ASM_LAUNCH(dropblock_apply_kernel, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     keep, scale, (const bf16_t*)relu_mask_from, relu, (bf16_t*)y, nvec, (unsigned)(HWC / 8));
-  ASM_CHECK_LAUNCH("dropblock_apply");
-  return ASM_OK;
-}
-
-extern "C" int asm_eval_rows(const float* logits, int ld, const int32_t* labels, int B, int C, int32_t* pred,
-                             float* conf, float* top1, float* top5, void* stream) {
-  ASM_REQUIRE(logits && labels && pred && conf && top1 && top5 && B > 0 && C > 0 && ld >= C, "eval_rows: bad arguments");
-  ASM_LAUNCH(eval_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ld, labels, C, pred, conf,
-                     top1, top5);
-  ASM_CHECK_LAUNCH("eval_rows");
-  return ASM_OK;
-}
-extern "C" int asm_eval_accumulate(const float* conf, const float* top1, const float* top5, int B, float* state33,
-                                   void* stream) {
-  ASM_REQUIRE(conf && top1 && top5 && state33 && B > 0, "eval_accumulate: bad arguments");
-  ASM_LAUNCH(eval_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, conf, top1, top5, B, state33);
-  ASM_CHECK_LAUNCH("eval_accumulate");
-  return ASM_OK;
+  return asm_launch_checked<dropblock_apply_kernel>("dropblock_apply", ew_grid(nvec), 256, (hipStream_t)stream,
+                                                    (const bf16_t*)x, keep, scale, (const bf16_t*)relu_mask_from, relu,
+                                                    (bf16_t*)y, nvec, (unsigned)(HWC / 8));
 }

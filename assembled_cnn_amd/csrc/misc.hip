@@ -15,11 +15,6 @@ extern "C" int asm_abi_version(void) { return ASM_ABI_VERSION; }
 
 namespace {
 
-inline unsigned ew_grid(size_t n) {
-  size_t b = cdivz(n, 256);
-  return (unsigned)(b < 8192 ? (b ? b : 1) : 8192);
-}
-
 // ---- element-wise ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void relu_fwd_kernel(const bf16_t* x, bf16_t* y, size_t nvec) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (size_t)gridDim.x * 256) {
@@ -102,17 +97,6 @@ __global__ void widen_kernel(const bf16_t* x, float* y, size_t n) {
 }
 
 // ---- softmax cross-entropy (+label smoothing, +KD), one block per row --------------------------------
-__device__ float block_reduce(float v, bool is_max, float* sh) {
-  v = is_max ? wave_max(v) : wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) sh[w] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < 4; ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
-  return r;
-}
-
 __global__ __launch_bounds__(256) void softmax_ce_kernel(const float* __restrict__ logits, int ld,
                                                          const float* __restrict__ targets,
                                                          const float* __restrict__ teacher, int B, int C, float eps,
@@ -202,13 +186,35 @@ __global__ __launch_bounds__(256) void mean_kernel(const float* x, int n, float*
 }
 
 // ---- input: mixup + mean subtraction + cast + stem halo ------------------------------------------------
-// out [Bout][H+6][W+6][4] bf16; one thread per output pixel (8 bytes)
-__global__ __launch_bounds__(256) void mixup_meansub_kernel(const void* __restrict__ images, int is_u8, int Bin,
-                                                            int Bout, int H, int W, int mixup_type,
-                                                            const float* __restrict__ lam1,
-                                                            const float* __restrict__ lam2, bf16_t* __restrict__ out) {
+// Image b of a mixup batch is la * in[ia] + (1 - la) * in[ib]; ib < 0 (mixup_type 0): in[ia] as it is.  Type 1 mixes the two
+// halves of the batch into Bout = Bin / 2 images; type 2 keeps Bin images, its second half mixing x1 with reverse(x2).
+struct MixPair {
+  int ia, ib;
+  float la;
+};
+__device__ __forceinline__ MixPair mix_pair(int b, int Bin, int Bout, int mixup_type, const float* lam1, const float* lam2) {
+  if (mixup_type == 1) return {b, Bout + b, lam1[b]};
+  if (mixup_type == 2) {
+    const int half = Bin / 2;
+    if (b < half) return {b, half + b, lam1[b]};
+    return {b - half, Bin - 1 - (b - half), lam2[b - half]};  // x3 = reverse(x2)
+  }
+  return {b, -1, 1.0f};
+}
+// the operand order is part of the result: it decides which products the compiler contracts into FMAs
+__device__ __forceinline__ float mix(float la, float xa, float xb) { return la * xa + (1.0f - la) * xb; }
+
+// one pixel of the stem's input: three channels and a zero fourth, bf16
+__device__ __forceinline__ u32x2 stem_px(const float* r) {
+  const u32x2 o = {pack2bf(r[0], r[1]), pack2bf(r[2], 0.f)};
+  return o;
+}
+// out [B][H+6][W+6][4] bf16 with a zero halo of three pixels; one thread per output pixel (8 bytes); load(b, h, w, r) yields
+// the three values of an inner one
+template <class Load>
+__device__ __forceinline__ void stem_halo_pixel(bf16_t* out, int B, int H, int W, Load load) {
   const int Hp = H + 6, Wp = W + 6;
-  const size_t total = (size_t)Bout * Hp * Wp;
+  const size_t total = (size_t)B * Hp * Wp;
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int wp = (int)(i % Wp);
@@ -218,42 +224,42 @@ __global__ __launch_bounds__(256) void mixup_meansub_kernel(const void* __restri
   const int h = hp - 3, w = wp - 3;
   u32x2 o = {0u, 0u};
   if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) {
-    int ia = b, ib = -1;
-    float la = 1.0f;
-    if (mixup_type == 1) {
-      ia = b; ib = Bout + b; la = lam1[b];
-    } else if (mixup_type == 2) {
-      const int half = Bin / 2;
-      if (b < half) { ia = b; ib = half + b; la = lam1[b]; }
-      else { ia = b - half; ib = Bin - 1 - (b - half); la = lam2[b - half]; }  // x3 = reverse(x2)
-    }
-    float va[3], vb[3] = {0.f, 0.f, 0.f};
-    const size_t pa = (((size_t)ia * H + h) * W + w) * 3;
-    if (is_u8) {
-      const uint8_t* p = reinterpret_cast<const uint8_t*>(images);
-      for (int c = 0; c < 3; ++c) va[c] = (float)p[pa + c];
-      if (ib >= 0) {
-        const size_t pb = (((size_t)ib * H + h) * W + w) * 3;
-        for (int c = 0; c < 3; ++c) vb[c] = (float)p[pb + c];
-      }
-    } else {
-      const float* p = reinterpret_cast<const float*>(images);
-      for (int c = 0; c < 3; ++c) va[c] = p[pa + c];
-      if (ib >= 0) {
-        const size_t pb = (((size_t)ib * H + h) * W + w) * 3;
-        for (int c = 0; c < 3; ++c) vb[c] = p[pb + c];
-      }
-    }
-    const float mean[3] = ASM_CHANNEL_MEANS;
     float r[3];
-    for (int c = 0; c < 3; ++c) {
-      const float xa = va[c] - mean[c];
-      r[c] = ib >= 0 ? la * xa + (1.0f - la) * (vb[c] - mean[c]) : xa;
-    }
-    o.x = pack2bf(r[0], r[1]);
-    o.y = pack2bf(r[2], 0.f);
+    load(b, h, w, r);
+    o = stem_px(r);
   }
   *reinterpret_cast<u32x2*>(out + i * 4) = o;
+}
+// the three channels of pixel (b, h, w) of x [.][H][W][3], T = uint8, float32 or bf16
+__device__ __forceinline__ float as_f32(uint8_t v) { return (float)v; }
+__device__ __forceinline__ float as_f32(float v) { return v; }
+__device__ __forceinline__ float as_f32(bf16_t v) { return bf2f(v); }
+template <class T>
+__device__ __forceinline__ void load_px(const void* x, int b, int h, int w, int H, int W, float* v) {
+  const T* p = reinterpret_cast<const T*>(x) + (((size_t)b * H + h) * W + w) * 3;
+  for (int c = 0; c < 3; ++c) v[c] = as_f32(p[c]);
+}
+template <class T>
+__device__ __forceinline__ void load_px_pair(const void* x, const MixPair& m, int h, int w, int H, int W, float* va, float* vb) {
+  load_px<T>(x, m.ia, h, w, H, W, va);
+  if (m.ib >= 0) load_px<T>(x, m.ib, h, w, H, W, vb);
+}
+
+__global__ __launch_bounds__(256) void mixup_meansub_kernel(const void* __restrict__ images, int is_u8, int Bin,
+                                                            int Bout, int H, int W, int mixup_type,
+                                                            const float* __restrict__ lam1,
+                                                            const float* __restrict__ lam2, bf16_t* __restrict__ out) {
+  stem_halo_pixel(out, Bout, H, W, [&](int b, int h, int w, float* r) {
+    const MixPair m = mix_pair(b, Bin, Bout, mixup_type, lam1, lam2);
+    float va[3], vb[3] = {0.f, 0.f, 0.f};
+    if (is_u8) load_px_pair<uint8_t>(images, m, h, w, H, W, va, vb);
+    else load_px_pair<float>(images, m, h, w, H, W, va, vb);
+    const float mean[3] = ASM_CHANNEL_MEANS;
+    for (int c = 0; c < 3; ++c) {
+      const float xa = va[c] - mean[c];
+      r[c] = m.ib >= 0 ? mix(m.la, xa, vb[c] - mean[c]) : xa;
+    }
+  });
 }
 
 // uint8 input with W % 4 == 0: one 64-thread block per output row, a thread converts four pixels from three aligned dword
@@ -274,17 +280,9 @@ __global__ __launch_bounds__(64) void mixup_meansub_rows_kernel(const uint8_t* _
     orow[threadIdx.x] = z;
     orow[W + 3 + threadIdx.x] = z;
   }
-  int ia = b, ib = -1;
-  float la = 1.0f;
-  if (mixup_type == 1) {
-    ia = b; ib = Bout + b; la = lam1[b];
-  } else if (mixup_type == 2) {
-    const int half = Bin / 2;
-    if (b < half) { ia = b; ib = half + b; la = lam1[b]; }
-    else { ia = b - half; ib = Bin - 1 - (b - half); la = lam2[b - half]; }
-  }
-  const unsigned* pa = reinterpret_cast<const unsigned*>(images + ((size_t)ia * H + h) * W * 3);
-  const unsigned* pb = ib >= 0 ? reinterpret_cast<const unsigned*>(images + ((size_t)ib * H + h) * W * 3) : nullptr;
+  const MixPair m = mix_pair(b, Bin, Bout, mixup_type, lam1, lam2);
+  const unsigned* pa = reinterpret_cast<const unsigned*>(images + ((size_t)m.ia * H + h) * W * 3);
+  const unsigned* pb = m.ib >= 0 ? reinterpret_cast<const unsigned*>(images + ((size_t)m.ib * H + h) * W * 3) : nullptr;
   const float mean[3] = ASM_CHANNEL_MEANS;
   for (int q = threadIdx.x; q < (W >> 2); q += 64) {
     unsigned a[3], bb[3] = {0u, 0u, 0u};
@@ -302,42 +300,19 @@ __global__ __launch_bounds__(64) void mixup_meansub_rows_kernel(const uint8_t* _
         const int byte = px * 3 + c;
         const float xa = (float)((a[byte >> 2] >> ((byte & 3) * 8)) & 0xffu) - mean[c];
         const float xb = (float)((bb[byte >> 2] >> ((byte & 3) * 8)) & 0xffu) - mean[c];
-        r[c] = pb ? la * xa + (1.0f - la) * xb : xa;
+        r[c] = pb ? mix(m.la, xa, xb) : xa;
       }
-      u32x2 o;
-      o.x = pack2bf(r[0], r[1]);
-      o.y = pack2bf(r[2], 0.f);
-      orow[3 + q * 4 + px] = o;
+      orow[3 + q * 4 + px] = stem_px(r);
     }
   }
 }
 
 __global__ __launch_bounds__(256) void stem_pad_kernel(const void* __restrict__ x, int is_f32, bf16_t* __restrict__ out,
                                                        int N, int H, int W) {
-  const int Hp = H + 6, Wp = W + 6;
-  const size_t total = (size_t)N * Hp * Wp;
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int wp = (int)(i % Wp);
-  const size_t t = i / Wp;
-  const int hp = (int)(t % Hp);
-  const int b = (int)(t / Hp);
-  const int h = hp - 3, w = wp - 3;
-  u32x2 o = {0u, 0u};
-  if ((unsigned)h < (unsigned)H && (unsigned)w < (unsigned)W) {
-    const size_t p = (((size_t)b * H + h) * W + w) * 3;
-    float r[3];
-    if (is_f32) {
-      const float* xf = reinterpret_cast<const float*>(x);
-      for (int c = 0; c < 3; ++c) r[c] = xf[p + c];
-    } else {
-      const bf16_t* xb = reinterpret_cast<const bf16_t*>(x);
-      for (int c = 0; c < 3; ++c) r[c] = bf2f(xb[p + c]);
-    }
-    o.x = pack2bf(r[0], r[1]);
-    o.y = pack2bf(r[2], 0.f);
-  }
-  *reinterpret_cast<u32x2*>(out + i * 4) = o;
+  stem_halo_pixel(out, N, H, W, [&](int b, int h, int w, float* r) {
+    if (is_f32) load_px<float>(x, b, h, w, H, W, r);
+    else load_px<bf16_t>(x, b, h, w, H, W, r);
+  });
 }
 
 __global__ void mixup_labels_kernel(const float* y, int Bin, int Bout, int C, int mixup_type, const float* lam1,
@@ -345,17 +320,9 @@ __global__ void mixup_labels_kernel(const float* y, int Bin, int Bout, int C, in
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (size_t)Bout * C) return;
   const int b = (int)(i / C), c = (int)(i - (size_t)b * C);
-  int ia = b, ib = -1;
-  float la = 1.0f;
-  if (mixup_type == 1) {
-    ia = b; ib = Bout + b; la = lam1[b];
-  } else if (mixup_type == 2) {
-    const int half = Bin / 2;
-    if (b < half) { ia = b; ib = half + b; la = lam1[b]; }
-    else { ia = b - half; ib = Bin - 1 - (b - half); la = lam2[b - half]; }
-  }
-  float v = y[(size_t)ia * C + c];
-  if (ib >= 0) v = la * v + (1.0f - la) * y[(size_t)ib * C + c];
+  const MixPair m = mix_pair(b, Bin, Bout, mixup_type, lam1, lam2);
+  float v = y[(size_t)m.ia * C + c];
+  if (m.ib >= 0) v = mix(m.la, v, y[(size_t)m.ib * C + c]);
   out[i] = v;
 }
 
@@ -605,63 +572,48 @@ NaiveArgs naive_args(const asm_conv_desc* d) {
 extern "C" int asm_relu_fwd(const void* x, void* y, size_t n, void* stream) {
   ASM_REQUIRE(x && y, "relu_fwd: null pointer");
   VEC8_OK("relu_fwd");
-  ASM_LAUNCH(relu_fwd_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     (bf16_t*)y, n / 8);
-  ASM_CHECK_LAUNCH("relu_fwd");
-  return ASM_OK;
+  return asm_launch_checked<relu_fwd_kernel>("relu_fwd", ew_grid(n / 8), 256, (hipStream_t)stream, (const bf16_t*)x,
+                                             (bf16_t*)y, n / 8);
 }
 extern "C" int asm_relu_bwd(const void* dy, const void* y, void* dx, size_t n, void* stream) {
   ASM_REQUIRE(dy && y && dx, "relu_bwd: null pointer");
   VEC8_OK("relu_bwd");
-  ASM_LAUNCH(relu_bwd_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy,
-                     (const bf16_t*)y, (bf16_t*)dx, n / 8);
-  ASM_CHECK_LAUNCH("relu_bwd");
-  return ASM_OK;
+  return asm_launch_checked<relu_bwd_kernel>("relu_bwd", ew_grid(n / 8), 256, (hipStream_t)stream, (const bf16_t*)dy,
+                                             (const bf16_t*)y, (bf16_t*)dx, n / 8);
 }
 extern "C" int asm_mask_apply(const void* dy, const uint8_t* mask, void* dx, size_t n, void* stream) {
   ASM_REQUIRE(dy && mask && dx, "mask_apply: null pointer");
   VEC8_OK("mask_apply");
-  ASM_LAUNCH(mask_apply_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, mask,
-                     (bf16_t*)dx, n / 8);
-  ASM_CHECK_LAUNCH("mask_apply");
-  return ASM_OK;
+  return asm_launch_checked<mask_apply_kernel>("mask_apply", ew_grid(n / 8), 256, (hipStream_t)stream, (const bf16_t*)dy,
+                                               mask, (bf16_t*)dx, n / 8);
 }
 extern "C" int asm_add_bf16(const void* a, const void* b, void* out, size_t n, void* stream) {
   ASM_REQUIRE(a && b && out, "add_bf16: null pointer");
   VEC8_OK("add_bf16");
-  ASM_LAUNCH(add_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a,
-                     (const bf16_t*)b, (bf16_t*)out, n / 8);
-  ASM_CHECK_LAUNCH("add_bf16");
-  return ASM_OK;
+  return asm_launch_checked<add_kernel>("add_bf16", ew_grid(n / 8), 256, (hipStream_t)stream, (const bf16_t*)a,
+                                        (const bf16_t*)b, (bf16_t*)out, n / 8);
 }
 extern "C" int asm_bias_add_f32(float* y, const float* bias, int M, int C, int ldy, void* stream) {
   ASM_REQUIRE(y && bias && M > 0 && C > 0 && ldy >= C, "bias_add: bad arguments");
-  ASM_LAUNCH(bias_add_kernel, dim3((unsigned)cdivz((size_t)M * C, 256)), dim3(256), 0, (hipStream_t)stream, y,
-                     bias, M, C, ldy);
-  ASM_CHECK_LAUNCH("bias_add");
-  return ASM_OK;
+  return asm_launch_checked<bias_add_kernel>("bias_add", (unsigned)cdivz((size_t)M * C, 256), 256, (hipStream_t)stream, y,
+                                             bias, M, C, ldy);
 }
 extern "C" int asm_bias_grad_bf16(const void* dz, int M, int C, int ld, float* dbias, void* stream) {
   ASM_REQUIRE(dz && dbias && M > 0 && C > 0 && ld >= C, "bias_grad: bad arguments");
-  ASM_LAUNCH(bias_grad_kernel, dim3(cdiv(C, 32)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dz, M, C,
-                     ld, dbias);
-  ASM_CHECK_LAUNCH("bias_grad");
-  return ASM_OK;
+  return asm_launch_checked<bias_grad_kernel>("bias_grad", cdiv(C, 32), 256, (hipStream_t)stream, (const bf16_t*)dz, M, C,
+                                              ld, dbias);
 }
 extern "C" int asm_cast_f32_to_bf16(const float* x, void* y, size_t n, void* stream) {
   ASM_REQUIRE(x && y, "cast: null pointer");
   if (n == 0) return ASM_OK;
-  ASM_LAUNCH(cast_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
-  ASM_CHECK_LAUNCH("cast");
-  return ASM_OK;
+  return asm_launch_checked<cast_kernel>("cast", ew_grid(n), 256, (hipStream_t)stream, x, (bf16_t*)y, n);
 }
 
 extern "C" int asm_cast_bf16_to_f32(const void* x, float* y, size_t n, void* stream) {
   ASM_REQUIRE(x && y, "cast: null pointer");
   if (n == 0) return ASM_OK;
-  ASM_LAUNCH(widen_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, y, n);
-  ASM_CHECK_LAUNCH("cast_bf16_to_f32");
-  return ASM_OK;
+  return asm_launch_checked<widen_kernel>("cast_bf16_to_f32", ew_grid(n), 256, (hipStream_t)stream, (const bf16_t*)x, y,
+                                          n);
 }
 
 extern "C" int asm_softmax_ce(const float* logits, int ld, const float* targets, const float* teacher, int B, int C,
@@ -670,67 +622,57 @@ extern "C" int asm_softmax_ce(const float* logits, int ld, const float* targets,
   ASM_REQUIRE(logits && targets && loss_rows && B > 0 && C > 0 && ld >= C, "softmax_ce: bad arguments");
   ASM_REQUIRE(!teacher || kd_temp > 0.f, "softmax_ce: teacher given but kd_temp <= 0");
   ASM_REQUIRE(!dlogits || ld_out >= C, "softmax_ce: bad ld_out");
-  ASM_LAUNCH(softmax_ce_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ld, targets, teacher, B, C,
-                     label_smoothing, kd_temp, loss_scale, loss_rows, (bf16_t*)dlogits, ld_out);
-  ASM_CHECK_LAUNCH("softmax_ce");
-  return ASM_OK;
+  return asm_launch_checked<softmax_ce_kernel>("softmax_ce", B, 256, (hipStream_t)stream, logits, ld, targets, teacher, B, C,
+                                               label_smoothing, kd_temp, loss_scale, loss_rows, (bf16_t*)dlogits, ld_out);
 }
 extern "C" int asm_onehot(const int32_t* labels, float* out, int B, int C, void* stream) {
   ASM_REQUIRE(labels && out && B > 0 && C > 0, "onehot: bad arguments");
-  ASM_LAUNCH(onehot_kernel, dim3((unsigned)cdivz((size_t)B * C, 256)), dim3(256), 0, (hipStream_t)stream,
-                     labels, out, B, C);
-  ASM_CHECK_LAUNCH("onehot");
-  return ASM_OK;
+  return asm_launch_checked<onehot_kernel>("onehot", (unsigned)cdivz((size_t)B * C, 256), 256, (hipStream_t)stream, labels,
+                                           out, B, C);
 }
 extern "C" int asm_softmax_rows(const float* x, float* y, int B, int C, float inv_temp, void* stream) {
   ASM_REQUIRE(x && y && B > 0 && C > 0, "softmax_rows: bad arguments");
-  ASM_LAUNCH(softmax_rows_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, y, B, C, inv_temp);
-  ASM_CHECK_LAUNCH("softmax_rows");
-  return ASM_OK;
+  return asm_launch_checked<softmax_rows_kernel>("softmax_rows", B, 256, (hipStream_t)stream, x, y, B, C, inv_temp);
 }
 extern "C" int asm_mean_f32(const float* x, int n, float* out, void* stream) {
   ASM_REQUIRE(x && out && n > 0, "mean: bad arguments");
-  ASM_LAUNCH(mean_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, n, out);
-  ASM_CHECK_LAUNCH("mean");
-  return ASM_OK;
+  return asm_launch_checked<mean_kernel>("mean", 1, 256, (hipStream_t)stream, x, n, out);
 }
 
+// The mixup argument checks of entry point `name`, and the number of images it writes: Bin / 2 for mixup_type 1, else Bin.
+static int mixup_batch(const char* name, int Bin, int mixup_type, const float* lam1, const float* lam2, int* Bout) {
+  ASM_REQUIRE(mixup_type >= 0 && mixup_type <= 2, "%s: mixup_type must be 0, 1 or 2", name);
+  ASM_REQUIRE(mixup_type == 0 || (lam1 && Bin % 2 == 0), "%s: mixup needs lam1 and an even batch", name);
+  ASM_REQUIRE(mixup_type != 2 || lam2, "%s: mixup_type 2 needs lam2", name);
+  *Bout = mixup_type == 1 ? Bin / 2 : Bin;
+  return ASM_OK;
+}
 extern "C" int asm_mixup_meansub(const void* images, int is_u8, int Bin, int H, int W, int mixup_type,
                                  const float* lam1, const float* lam2, void* out, void* stream) {
   ASM_REQUIRE(images && out && Bin > 0 && H > 0 && W > 0, "mixup_meansub: bad arguments");
-  ASM_REQUIRE(mixup_type >= 0 && mixup_type <= 2, "mixup_meansub: mixup_type must be 0, 1 or 2");
-  ASM_REQUIRE(mixup_type == 0 || (lam1 && Bin % 2 == 0), "mixup_meansub: mixup needs lam1 and an even batch");
-  ASM_REQUIRE(mixup_type != 2 || lam2, "mixup_meansub: mixup_type 2 needs lam2");
-  const int Bout = mixup_type == 1 ? Bin / 2 : Bin;
-  const size_t total = (size_t)Bout * (H + 6) * (W + 6);
+  int Bout;
+  if (int rc = mixup_batch("mixup_meansub", Bin, mixup_type, lam1, lam2, &Bout)) return rc;
   if (is_u8 && W % 4 == 0 && (reinterpret_cast<uintptr_t>(images) & 3) == 0)
-    ASM_LAUNCH(mixup_meansub_rows_kernel, dim3((unsigned)(Bout * (H + 6))), dim3(64), 0, (hipStream_t)stream,
-               (const uint8_t*)images, Bin, Bout, H, W, mixup_type, lam1, lam2, (bf16_t*)out);
-  else
-    ASM_LAUNCH(mixup_meansub_kernel, dim3((unsigned)cdivz(total, 256)), dim3(256), 0, (hipStream_t)stream, images,
-               is_u8, Bin, Bout, H, W, mixup_type, lam1, lam2, (bf16_t*)out);
-  ASM_CHECK_LAUNCH("mixup_meansub");
-  return ASM_OK;
+    return asm_launch_checked<mixup_meansub_rows_kernel>("mixup_meansub", (unsigned)(Bout * (H + 6)), 64, (hipStream_t)stream,
+                                                         (const uint8_t*)images, Bin, Bout, H, W, mixup_type, lam1, lam2,
+                                                         (bf16_t*)out);
+  const size_t total = (size_t)Bout * (H + 6) * (W + 6);
+  return asm_launch_checked<mixup_meansub_kernel>("mixup_meansub", (unsigned)cdivz(total, 256), 256, (hipStream_t)stream,
+                                                  images, is_u8, Bin, Bout, H, W, mixup_type, lam1, lam2, (bf16_t*)out);
 }
 extern "C" int asm_stem_pad_input(const void* x, int x_is_f32, void* xp, int N, int H, int W, void* stream) {
   ASM_REQUIRE(x && xp && N > 0 && H > 0 && W > 0, "stem_pad_input: bad arguments");
   const size_t total = (size_t)N * (H + 6) * (W + 6);
-  ASM_LAUNCH(stem_pad_kernel, dim3((unsigned)cdivz(total, 256)), dim3(256), 0, (hipStream_t)stream, x, x_is_f32,
-                     (bf16_t*)xp, N, H, W);
-  ASM_CHECK_LAUNCH("stem_pad_input");
-  return ASM_OK;
+  return asm_launch_checked<stem_pad_kernel>("stem_pad_input", (unsigned)cdivz(total, 256), 256, (hipStream_t)stream, x,
+                                             x_is_f32, (bf16_t*)xp, N, H, W);
 }
 extern "C" int asm_mixup_labels(const float* y, int Bin, int C, int mixup_type, const float* lam1, const float* lam2,
                                 float* out, void* stream) {
   ASM_REQUIRE(y && out && Bin > 0 && C > 0, "mixup_labels: bad arguments");
-  ASM_REQUIRE(mixup_type >= 0 && mixup_type <= 2, "mixup_labels: mixup_type must be 0, 1 or 2");
-  ASM_REQUIRE(mixup_type == 0 || (lam1 && Bin % 2 == 0), "mixup_labels: mixup needs lam1 and an even batch");
-  ASM_REQUIRE(mixup_type != 2 || lam2, "mixup_labels: mixup_type 2 needs lam2");
-  const int Bout = mixup_type == 1 ? Bin / 2 : Bin;
-  ASM_LAUNCH(mixup_labels_kernel, dim3((unsigned)cdivz((size_t)Bout * C, 256)), dim3(256), 0,
-                     (hipStream_t)stream, y, Bin, Bout, C, mixup_type, lam1, lam2, out);
-  ASM_CHECK_LAUNCH("mixup_labels");
-  return ASM_OK;
+  int Bout;
+  if (int rc = mixup_batch("mixup_labels", Bin, mixup_type, lam1, lam2, &Bout)) return rc;
+  return asm_launch_checked<mixup_labels_kernel>("mixup_labels", (unsigned)cdivz((size_t)Bout * C, 256), 256,
+                                                 (hipStream_t)stream, y, Bin, Bout, C, mixup_type, lam1, lam2, out);
 }
 
 extern "C" int asm_sgd_momentum(float* w, float* accum, const float* grad, void* w_bf16, size_t n, float lr,
@@ -741,10 +683,8 @@ extern "C" int asm_sgd_momentum(float* w, float* accum, const float* grad, void*
                   (reinterpret_cast<uintptr_t>(w_bf16) & 7) == 0,
               "sgd_momentum: w, accum and grad must be 16-byte aligned, w_bf16 8-byte aligned");
   if (n == 0) return ASM_OK;
-  ASM_LAUNCH(sgd_kernel, dim3(ew_grid(cdivz(n, 4))), dim3(256), 0, (hipStream_t)stream, w, accum, grad,
-                     (bf16_t*)w_bf16, n, lr, momentum, weight_decay, grad_scale);
-  ASM_CHECK_LAUNCH("sgd_momentum");
-  return ASM_OK;
+  return asm_launch_checked<sgd_kernel>("sgd_momentum", ew_grid(cdivz(n, 4)), 256, (hipStream_t)stream, w, accum, grad,
+                                        (bf16_t*)w_bf16, n, lr, momentum, weight_decay, grad_scale);
 }
 
 extern "C" int asm_filter_transpose(const void* w_krsc, void* w_crsk, int K, int R, int S, int C, int ldk,
@@ -753,79 +693,63 @@ extern "C" int asm_filter_transpose(const void* w_krsc, void* w_crsk, int K, int
               "filter_transpose: bad arguments");
   if (ldk == 0) ldk = K;
   const size_t n = (size_t)K * R * S * C;
-  ASM_LAUNCH(filter_transpose_kernel, dim3((unsigned)cdivz(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)w_krsc, (bf16_t*)w_crsk, K, R * S, C, ldk);
-  ASM_CHECK_LAUNCH("filter_transpose");
-  return ASM_OK;
+  return asm_launch_checked<filter_transpose_kernel>("filter_transpose", (unsigned)cdivz(n, 256), 256, (hipStream_t)stream,
+                                                     (const bf16_t*)w_krsc, (bf16_t*)w_crsk, K, R * S, C, ldk);
 }
 extern "C" int asm_stem_pack_filter(const float* w_krsc3, void* w_packed, int K, int ksize, void* stream) {
   ASM_REQUIRE(w_krsc3 && w_packed && K > 0 && (ksize == 3 || ksize == 7), "stem_pack_filter: bad arguments");
   const int L = (4 * ksize + 7) & ~7;
-  ASM_LAUNCH(stem_pack_kernel, dim3(cdiv(K * ksize * L, 256)), dim3(256), 0, (hipStream_t)stream, w_krsc3,
-                     (bf16_t*)w_packed, K, ksize, L);
-  ASM_CHECK_LAUNCH("stem_pack_filter");
-  return ASM_OK;
+  return asm_launch_checked<stem_pack_kernel>("stem_pack_filter", cdiv(K * ksize * L, 256), 256, (hipStream_t)stream,
+                                              w_krsc3, (bf16_t*)w_packed, K, ksize, L);
 }
 extern "C" int asm_stem_unpack_grad(const float* dw_packed, float* dw_krsc3, int K, int ksize, void* stream) {
   ASM_REQUIRE(dw_packed && dw_krsc3 && K > 0 && (ksize == 3 || ksize == 7), "stem_unpack_grad: bad arguments");
   const int L = (4 * ksize + 7) & ~7;
-  ASM_LAUNCH(stem_unpack_kernel, dim3(cdiv(K * ksize * ksize * 3, 256)), dim3(256), 0, (hipStream_t)stream,
-                     dw_packed, dw_krsc3, K, ksize, L);
-  ASM_CHECK_LAUNCH("stem_unpack_grad");
-  return ASM_OK;
+  return asm_launch_checked<stem_unpack_kernel>("stem_unpack_grad", cdiv(K * ksize * ksize * 3, 256), 256,
+                                                (hipStream_t)stream, dw_packed, dw_krsc3, K, ksize, L);
 }
 
 extern "C" int asm_conv2d_fprop_naive(const asm_conv_desc* d, const void* x, const void* w, void* y, void* stream) {
   ASM_REQUIRE(d && x && w && y, "fprop_naive: null pointer");
   NaiveArgs a = naive_args(d);
   const size_t total = (size_t)a.N * a.Ho * a.Wo * a.K;
-  ASM_LAUNCH(naive_fprop_kernel, dim3((unsigned)cdivz(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, (const bf16_t*)w, y, a);
-  ASM_CHECK_LAUNCH("fprop_naive");
-  return ASM_OK;
+  return asm_launch_checked<naive_fprop_kernel>("fprop_naive", (unsigned)cdivz(total, 256), 256, (hipStream_t)stream,
+                                                (const bf16_t*)x, (const bf16_t*)w, y, a);
 }
 extern "C" int asm_conv2d_dgrad_naive(const asm_conv_desc* d, const void* dy, const void* w_krsc, void* dx,
                                       void* stream) {
   ASM_REQUIRE(d && dy && w_krsc && dx, "dgrad_naive: null pointer");
   NaiveArgs a = naive_args(d);
   const size_t total = (size_t)a.N * a.H * a.W * a.C;
-  ASM_LAUNCH(naive_dgrad_kernel, dim3((unsigned)cdivz(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)dy, (const bf16_t*)w_krsc, (bf16_t*)dx, a);
-  ASM_CHECK_LAUNCH("dgrad_naive");
-  return ASM_OK;
+  return asm_launch_checked<naive_dgrad_kernel>("dgrad_naive", (unsigned)cdivz(total, 256), 256, (hipStream_t)stream,
+                                                (const bf16_t*)dy, (const bf16_t*)w_krsc, (bf16_t*)dx, a);
 }
 extern "C" int asm_conv2d_wgrad_naive(const asm_conv_desc* d, const void* x, const void* dy, float* dw, void* stream) {
   ASM_REQUIRE(d && x && dy && dw, "wgrad_naive: null pointer");
   NaiveArgs a = naive_args(d);
   const size_t total = (size_t)a.K * a.R * a.S * a.C;
-  ASM_LAUNCH(naive_wgrad_kernel, dim3((unsigned)cdivz(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, (const bf16_t*)dy, dw, a);
-  ASM_CHECK_LAUNCH("wgrad_naive");
-  return ASM_OK;
+  return asm_launch_checked<naive_wgrad_kernel>("wgrad_naive", (unsigned)cdivz(total, 256), 256, (hipStream_t)stream,
+                                                (const bf16_t*)x, (const bf16_t*)dy, dw, a);
 }
 
 extern "C" int asm_debug_tr_probe(void* out256_i16, void* stream) {
   ASM_REQUIRE(out256_i16, "tr_probe: null pointer");
-  ASM_LAUNCH(tr_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (short*)out256_i16);
-  ASM_CHECK_LAUNCH("tr_probe");
-  return ASM_OK;
+  return asm_launch_checked<tr_probe_kernel>("tr_probe", 1, 64, (hipStream_t)stream, (short*)out256_i16);
 }
 
 extern "C" int asm_filter_transpose_tiled(const void* w_arena, void* wt_arena, const int32_t* table, int nlayers,
                                           int total_tiles, void* stream) {
   ASM_REQUIRE(w_arena && wt_arena && table && nlayers > 0 && total_tiles > 0, "filter_transpose_tiled: bad arguments");
-  ASM_LAUNCH(filter_transpose_tiled_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)w_arena, (bf16_t*)wt_arena, (const int*)table, nlayers);
-  ASM_CHECK_LAUNCH("filter_transpose_tiled");
-  return ASM_OK;
+  return asm_launch_checked<filter_transpose_tiled_kernel>("filter_transpose_tiled", (unsigned)total_tiles, 256,
+                                                           (hipStream_t)stream, (const bf16_t*)w_arena, (bf16_t*)wt_arena,
+                                                           (const int*)table, nlayers);
 }
 
 extern "C" int asm_filter_transpose_batched(const void* w_arena, void* wt_arena, const int32_t* table, int nlayers,
                                             long long total_elems, void* stream) {
   ASM_REQUIRE(w_arena && wt_arena && table && nlayers > 0 && total_elems > 0, "filter_transpose_batched: bad arguments");
-  ASM_LAUNCH(filter_transpose_batched_kernel, dim3((unsigned)cdivz((size_t)total_elems, 256)), dim3(256), 0,
-                     (hipStream_t)stream, (const bf16_t*)w_arena, (bf16_t*)wt_arena, (const int*)table, nlayers,
-                     total_elems);
-  ASM_CHECK_LAUNCH("filter_transpose_batched");
-  return ASM_OK;
+  return asm_launch_checked<filter_transpose_batched_kernel>("filter_transpose_batched",
+                                                             (unsigned)cdivz((size_t)total_elems, 256), 256,
+                                                             (hipStream_t)stream, (const bf16_t*)w_arena, (bf16_t*)wt_arena,
+                                                             (const int*)table, nlayers, total_elems);
 }

@@ -527,7 +527,10 @@ int asm_dropblock_apply(const void* x, const float* keep, const float* scale, co
                         void* y, int N, int HWC, void* stream);
 /* Evaluation metrics (nets/run_loop_classification.py:208-219): per row arg-max, max softmax probability,
  * top-1 hit and tf.nn.in_top_k(k=5) hit; accumulate adds a batch into the 33-float running state
- * {sum top1, sum top5, count, correct[10], confidence[10], count[10]} of metric/ece_metric.py:171-298. */
+ * {sum top1, sum top5, count, correct[10], confidence[10], count[10]} of metric/ece_metric.py:171-298.
+ * pred is the lowest index of the row's largest non-NaN logit (the arg-max rule of asm_eval_groups below): a row with no
+ * logit above -inf predicts the lowest index that holds -inf, and a row of NaNs alone has pred = 0x7fffffff, which is no
+ * class and no hit.  conf of such rows is NaN. */
 int asm_eval_rows(const float* logits, int ld, const int32_t* labels, int B, int C, int32_t* pred, float* conf,
                   float* top1, float* top5, void* stream);
 int asm_eval_accumulate(const float* conf, const float* top1, const float* top5, int B, float* state33,

@@ -1,4 +1,4 @@
-"""asm_eval_groups (csrc/eval_groups.hip) against tests/robustness_ref.eval_groups: equal counters and equal predictions.
+"""asm_eval_groups (csrc/eval.hip) against tests/robustness_ref.eval_groups: equal counters and equal predictions.
 
 Rules of every case:
 * the logits lie between two 4 KiB flanks of 1e30 or NaN and their pad columns C .. ld-1 hold the same poison: a read past a
@@ -134,6 +134,39 @@ def test_known_answer_rows(hip_lib, ld):
   got_c, got_p = _run(z2, 3, np.zeros(3, np.int32), np.asarray([-1, 2, 1], np.int32), 2, np.float32(NAN))
   exact('stray groups', got_c, [[0, 0, 0], [1, 1, 1], [2, 0, 0]])
   exact('stray groups pred', got_p, [0, 0, 0])
+
+
+@pytest.mark.parametrize('pad,misalign', [(3, False), (3, True), (2, False)], ids=['vector', 'scalar_base_off_16', 'scalar_ld'])
+@pytest.mark.parametrize('C', [5, 257])
+def test_the_two_tails_agree(hip_lib, C, pad, misalign):
+  """asm_eval_rows and asm_eval_groups (one arg-max rule, csrc/eval.hip) on the same logits: B = 7 rows, so the second
+  workgroup of four holds three; seeded normal logits, one row with its maximum twice, one label outside [0, C).  ld = C + 3
+  (8, 260) on a 16-byte aligned base takes the 16-byte loads; the same ld on a base off 16 bytes and ld = C + 2 take the
+  scalar ones.  Equal predictions, and with every row in group 0 the counters are {7, sum top1, sum top5} of asm_eval_rows."""
+  B, ld = 7, C + pad
+  r = np.random.default_rng(500 + C)
+  z = r.standard_normal((B, C)).astype(np.float32)
+  z[3, 1] = z[3, C - 2] = 9.0                                   # the tie row: the lower index must win in both
+  labels = np.argmax(z, axis=1).astype(np.int32)
+  labels[1::2] = r.integers(0, C, labels[1::2].size)
+  labels[3], labels[5] = 1, C                                   # a hit on the tie row; a label outside [0, C)
+  groups = np.zeros(B, np.int32)
+  zp = _padded(z, ld, np.float32(1e30)).reshape(-1)
+  buf = torch.full((zp.size + 8,), 1e30, dtype=torch.float32, device=DEV)
+  off = 5 if misalign else 4
+  zt = buf[off:off + zp.size]
+  zt.copy_(torch.from_numpy(zp))
+  assert ptr(zt) % 16 == (4 if misalign else 0)
+  lab, grp = In(labels, torch.int32, flank_value=0), In(groups, torch.int32, flank_value=0)
+  pred_r, conf, top1, top5 = Out((B,), torch.int32), Out((B,), torch.float32), Out((B,), torch.float32), Out((B,), torch.float32)
+  call('asm_eval_rows', ptr(zt), ld, lab.p, B, C, pred_r.p, conf.p, top1.p, top5.p)
+  counts, pred_g = Out((2, 3), torch.int32, init=torch.zeros((2, 3), dtype=torch.int32)), Out((B,), torch.int32)
+  call('asm_eval_groups', ptr(zt), ld, lab.p, grp.p, B, C, 1, counts.p, pred_g.p)
+  conf.np()
+  p, t1, t5 = pred_r.np(), top1.np(), top5.np()
+  assert p[3] == 1 and t1[3] == 1 and t1[5] == 0 and t5[5] == 0 and 0 < t1.sum() < B
+  exact('pred of the two tails', pred_g.np(), p)
+  exact('counters', counts.np(), [[B, int(t1.sum()), int(t5.sum())], [0, 0, 0]])
 
 
 def test_null_pred_and_counters_that_start_non_zero(hip_lib):

@@ -1,6 +1,6 @@
-"""Edge shapes, ties and guard bands of the row, loss, metric, DropBlock and bookkeeping kernels (csrc/extra.hip, the row and
-element kernels of csrc/misc.hip, the partial-sum kernels of csrc/bn.hip) against the plain float64 references of
-tests/rows_ref.py, which tests/test_rows_ref_cpu.py proves against the oracle on the CPU.
+"""Edge shapes, ties and guard bands of the row, loss, metric, DropBlock and bookkeeping kernels (csrc/extra.hip, the row
+metrics of csrc/eval.hip, the row and element kernels of csrc/misc.hip, the partial-sum kernels of csrc/bn.hip) against the
+plain float64 references of tests/rows_ref.py, which tests/test_rows_ref_cpu.py proves against the oracle on the CPU.
 
 Rules of every case:
 * element-wise bounds, never a norm.  bf16 outputs: |out - ref| <= 2^-8 |ref| + 4 * floor -- one bf16 ulp (half for the
@@ -240,6 +240,28 @@ def test_eval_rows_ties_and_label_guard(hip_lib, C):
   close_rel('eval_rows conf C=%d' % C, conf.np(), conf_r)
 
 
+@pytest.mark.parametrize('C', [3, 257])
+def test_eval_rows_degenerate_rows(hip_lib, C):
+  """the arg-max runs over the non-NaN logits and takes the lowest index of the largest (include/asm_hip.h): a row of -inf
+  predicts class 0, -inf with a NaN at index 0 predicts class 1, and a NaN left of a finite row's maximum is passed over.
+  conf of these rows is NaN by definition (exp(-inf + inf), a NaN term in the sum) and stays unasserted."""
+  am = C // 2
+  z = np.full((3, C), -np.inf, np.float32)
+  z[1, 0] = np.nan
+  z[2] = R.rng(7, C).standard_normal(C) * 2
+  z[2, am], z[2, am - 1] = 9.0, np.nan
+  labels = np.array([0, 1, am], np.int32)
+  B, ld = 3, C + 5
+  pred, conf, top1, top5 = Out((B,), torch.int32), Out((B,), torch.float32), Out((B,), torch.float32), Out((B,), torch.float32)
+  call('asm_eval_rows', ptr(dev(padded(z, ld, np.float32(1e30)))), ld, ptr(dev(labels, torch.int32)), B, C, pred.p, conf.p,
+       top1.p, top5.p)
+  conf.check_flanks()
+  top5.np()
+  got = pred.np()
+  exact('eval_rows degenerate pred C=%d' % C, got, [0, 1, am])
+  exact('eval_rows degenerate top1 C=%d' % C, top1.np(), (got == labels).astype(np.float64))
+
+
 # ---- GeM -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('p', [3.0, 2.5])
 @pytest.mark.parametrize('N,HW,C', [(1, 1, 8), (3, 49, 256), (2, 49, 264), (2, 12, 1000), (2, 9, 24)])
@@ -331,16 +353,12 @@ def test_dropblock_apply_forms(hip_lib, bs, H, W, C, kind):
 
 # ---- second trips of the capped grid-stride loops ------------------------------------------------------------------------------------
 def _grid_cap():
-  """the block cap of the element-wise launchers, read from the launcher itself (ew_grid in csrc/misc.hip and csrc/extra.hip)"""
+  """the block cap of the element-wise launchers, read from the launcher itself (ew_grid in csrc/common.h)"""
   here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-  caps = set()
-  for f in ('misc.hip', 'extra.hip'):
-    src = open(os.path.join(here, 'assembled_cnn_amd', 'csrc', f)).read()
-    m = re.search(r'inline unsigned ew_grid\(size_t n\) \{.*?b < (\d+) \?.*?: (\d+)\);', src, re.S)
-    assert m and m.group(1) == m.group(2), 'ew_grid not found in ' + f
-    caps.add(int(m.group(1)))
-  assert len(caps) == 1
-  return caps.pop()
+  src = open(os.path.join(here, 'assembled_cnn_amd', 'csrc', 'common.h')).read()
+  m = re.findall(r'inline unsigned ew_grid\(size_t n\) \{.*?b < (\d+) \?.*?: (\d+)\);', src, re.S)
+  assert len(m) == 1 and m[0][0] == m[0][1], 'ew_grid not found in common.h'
+  return int(m[0][0])
 
 
 def test_dropblock_apply_second_grid_stride_trip(hip_lib):
